@@ -2,7 +2,16 @@
 """bench.py -- the north-star measurement: plink_freq over a synthetic
 1,000,000-variant x 500,000-sample .pgen matrix resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line; nothing else.
+--full adds what the headline figure does not need: the checks of the last step's
+results, the CPU baseline, the store-ceiling probe and, on the default single-GPU
+1 M x 500 k freq run, the other BASELINE configs and the table-function section.
+--dump-outputs DIR writes the last timed step's results (what a caller of the timed
+path receives) as DIR/<name>.npy, float32 or float64, at most 64 MB in all (a fixed,
+seeded sample of rows where an output is larger); the inputs are seeded, so two
+builds can be compared output for output.
 
 One "step" = one full pass of the hot path over the rank's resident variants:
 the genotype-class tally kernel (PgrGetCounts for every variant), the ALT_FREQ /
@@ -21,15 +30,16 @@ scaling: --variants is the whole matrix (the north star's fixed 1 M x 500 k
 file) split into N contiguous ranges; --scaling weak gives every rank its own
 --variants rows.
 
-After the timed region the last step's host-side results are checked (rows tally
-to N, sampled rows equal a host recomputation from the seeded generator, the
-fused pass's per-sample missing counts add up to the per-variant ones) and the
-line carries "verified": true; a failed check exits non-zero without a line.
+With --full, after the timed region the last step's host-side results are checked
+(rows tally to N, sampled rows equal a host recomputation from the seeded generator,
+the fused pass's per-sample missing counts add up to the per-variant ones) and the
+line carries "verified": true; a failed check exits non-zero without a line.  A
+plain run carries "verified": null.
 
 Prints ONE JSON line on rank 0 (see the driver contract), including
   "roofline":     algorithmic HBM bytes of the tally kernel / its mean launch
                   duration (HIP events on the launch stream), against 8 TB/s;
-  "cpu_baseline": the CPU oracle run with the reference's scan structure
+  "cpu_baseline": (--full) the CPU oracle run with the reference's scan structure
                   (T threads claiming 128-variant batches) on a bounded sample.
 
 Other workloads (parity-tested configs, for DESIGN.md / profiles/):
@@ -69,7 +79,12 @@ def parse_args():
     ap.add_argument("--scaling", choices=["weak", "strong"], default="strong",
                     help="strong (default): --variants is the whole matrix, split across the GPUs; "
                          "weak: every GPU holds --variants rows of its own")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget (0 disables)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the checks of the last step's results, "
+                         "the CPU baseline, the store-ceiling probe, the other configs and the table-function section")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget under --full (0 disables)")
     ap.add_argument("--cpu-sample-variants", type=int, default=8192)
     ap.add_argument("--dosage-rate", type=float, default=0.1,
                     help="dosage workloads: fraction of samples with an explicit dosage per variant")
@@ -77,12 +92,18 @@ def parse_args():
     ap.add_argument("--score-no-dosage-sum", action="store_true",
                     help="score workload without NAMED_ALLELE_DOSAGE_SUM (what SELECT IID, SCORE_SUM projects)")
     ap.add_argument("--configs", choices=["auto", "all", "none"], default="auto",
-                    help="auto: the default single-GPU freq run at 1 M x 500 k also times BASELINE configs 2-5 "
-                         "(fused, unpack, score x16 / x1, pca) on the same matrix and attaches them as \"configs\"")
+                    help="under --full, auto: the default single-GPU freq run at 1 M x 500 k also times BASELINE "
+                         "configs 2-5 (fused, unpack, score x16 / x1, pca) on the same matrix and attaches them as "
+                         "\"configs\"")
     ap.add_argument("--config-steps", type=int, default=5, help="timed steps per extra config")
     ap.add_argument("--no-sql", dest="sql", action="store_false",
                     help="skip the table-function section (plink_freq / hardy / missing through the shells)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.configs == "all" and not args.full:
+        ap.error("--configs all runs under --full")
+    return args
 
 
 def cpu_baseline(ds, n_samples, budget_s, sample_variants):
@@ -381,6 +402,71 @@ def verify(args, wl, C, env):
                   file=sys.stderr)
         return bool(ok)
     return None
+
+
+def outputs_of(wl, C, env, budget):
+    """The last timed step's results as a caller of the timed path receives them, {name: array} (the timed region
+    has ended and was synchronised).  The unpack's output is gigabytes: a fixed, seeded sample of the rows of its
+    last launch, at most `budget` bytes once written as float32, and their variant indices."""
+    np, torch, n, m = C.np, C.torch, C.n, C.m
+    if m == 0:
+        return {}
+    if wl in ("freq", "fused"):
+        out = {"counts": env["h_counts"].numpy(), "alt_freq": env["h_freq"].numpy(), "obs_ct": env["h_obs"].numpy()}
+        if wl == "fused":
+            out.update(hwe_lnp=env["h_lnp"].numpy(), sample_missing=env["h_miss"].numpy())
+        return out
+    if wl == "unpack":
+        chunk = env["chunk"]
+        last0 = (m - 1) // chunk * chunk  # the rows of the last launch
+        k = max(1, min(m - last0, budget // (8 * n)))
+        rows = np.sort(np.random.default_rng(SEED + 5).choice(m - last0, size=k, replace=False))
+        idx = torch.from_numpy(rows).to(C.dev)
+        geno = env["d_out"].index_select(0, idx)[:, :n].cpu().numpy()
+        words = env["d_val"].index_select(0, idx).cpu().numpy().view(np.uint8)
+        valid = np.unpackbits(words, axis=1, bitorder="little")[:, :n]
+        return {"genotypes": geno, "valid": valid, "variant": C.v_begin + last0 + rows}
+    if wl == "dosagefreq":
+        return {"dosage_sums": env["h_sums"].numpy()}
+    if wl == "missingsample":
+        return {"sample_missing": env["h_miss"].numpy()[:n]}
+    if wl == "samplecounts":
+        return {"sample_class_counts": env["h_cls"].numpy()[:, :n]}
+    if wl == "ld":
+        return {"pair_sums": env["h_sums"].numpy()}
+    if wl == "pca":
+        return {"eigenvalues": env["pca_ev"][-1], "eigenvectors": env["pca_vec"][0]}
+    out = {"score_sum": env["d_score"].cpu().numpy(), "allele_ct": env["d_ac"].cpu().numpy()}  # score, dosagescore
+    if not env.get("no_dosage_sum"):
+        out["dosage_sum"] = env["d_dos"].cpu().numpy()
+    return out
+
+
+def dump_outputs(np, path, outs, limit, suffix=""):
+    """Writes {name: array} as path/<name><suffix>.npy: integers as float32 where every value is exact in it, float64
+    otherwise.  Over `limit` bytes in all, every output keeps the same share of its rows, a fixed, seeded sample whose
+    indices go to <name><suffix>.rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    conv = {}
+    for name, a in outs.items():
+        a = np.asarray(a)
+        if a.dtype.kind in "iub":
+            exact = a.size == 0 or float(np.abs(a.astype(np.float64)).max()) < 2.0 ** 24
+            a = a.astype(np.float32 if exact else np.float64)
+        elif a.dtype != np.float32:
+            a = a.astype(np.float64)
+        conv[name] = a
+    total = sum(a.nbytes for a in conv.values())
+    share = 1.0
+    if total > limit:
+        share = 0.99 * limit / sum(a.nbytes + 8 * (a.shape[0] if a.ndim else 0) for a in conv.values())
+    for name, a in conv.items():
+        if share < 1.0 and a.ndim:
+            rows = np.sort(np.random.default_rng(SEED + 3).choice(a.shape[0], size=max(1, int(a.shape[0] * share)),
+                                                                   replace=False))
+            np.save(os.path.join(path, f"{name}{suffix}.rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), np.ascontiguousarray(a))
 
 
 def build_workload(args, wl, C, score_cols=None, no_dosage_sum=None):
@@ -868,12 +954,19 @@ def main():
     if dist is not None:
         elapsed = sharding.max_over_ranks(dist, elapsed, dev)
 
-    verified = verify(args, args.workload, C, W.env)
-    if dist is not None:
-        ok = torch.tensor([0 if verified is False else 1], dtype=torch.int32, device=dev)
-        dist.all_reduce(ok, op=dist.ReduceOp.MIN)
-        if int(ok.item()) == 0:
-            verified = False
+    if args.dump_outputs:
+        limit = (64 << 20) // world
+        dump_outputs(np, args.dump_outputs, outputs_of(args.workload, C, W.env, int(0.9 * limit)), limit,
+                     f".rank{rank}" if world > 1 else "")
+
+    verified = None
+    if args.full:
+        verified = verify(args, args.workload, C, W.env)
+        if dist is not None:
+            ok = torch.tensor([0 if verified is False else 1], dtype=torch.int32, device=dev)
+            dist.all_reduce(ok, op=dist.ReduceOp.MIN)
+            if int(ok.item()) == 0:
+                verified = False
     if verified is False:
         raise SystemExit("bench.py: the last step's results failed verification; no line reported")
 
@@ -885,20 +978,20 @@ def main():
     if args.workload == "ld":
         total_units = W.units_per_step * (world if args.scaling == "weak" else 1)  # sample pairs, every rank the same shape
     value = total_units * args.steps / elapsed
-    store_ceiling = store_ceiling_probe(C) if (args.workload == "unpack" and world == 1) else None
+    store_ceiling = store_ceiling_probe(C) if (args.full and args.workload == "unpack" and world == 1) else None
     roofline = roofline_of(args, W, kern_avg_ms, len(kernel_ms), m, n, store_ceiling)
     W_metric, W_dtype = W.metric, W.dtype
 
-    # The default single-GPU run also times the other BASELINE configurations on the same resident matrix
-    # (configs 2-5: read_pgen's unpack, the fused freq + hardy + missing pass, plink_score with 16 columns and with
-    # one, plink_pca over the first 100,000 variants), each verified like its own --workload run, a few steps each.
+    # The default single-GPU run under --full also times the other BASELINE configurations on the same resident
+    # matrix (configs 2-5: read_pgen's unpack, the fused freq + hardy + missing pass, plink_score with 16 columns and
+    # with one, plink_pca over the first 100,000 variants), each verified like its own --workload run, a few steps each.
     configs = None
     sql_expect = None
-    if args.workload in ("freq", "fused") and m:
+    want_all = args.full and (args.configs == "all" or (args.configs == "auto" and args.workload == "freq" and world == 1
+                                                        and args.variants == 1_000_000 and n == 500_000))
+    if want_all and args.workload in ("freq", "fused") and m:
         hc = W.env["h_counts"].numpy().astype(np.int64).sum(axis=0)
         sql_expect = {"hom_ref": int(hc[0]), "het": int(hc[1]), "hom_alt": int(hc[2]), "missing": int(hc[3])}
-    want_all = args.configs == "all" or (args.configs == "auto" and args.workload == "freq" and world == 1
-                                         and args.variants == 1_000_000 and n == 500_000)
     if want_all and rank == 0:
         configs = {}
         primary_env = W.env
@@ -926,7 +1019,7 @@ def main():
         del primary_env
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         cpu = cpu_baseline(ds, n, args.cpu_seconds, args.cpu_sample_variants)
 
     sql = None
@@ -951,9 +1044,11 @@ def main():
             "vs_baseline": None,
             "dtype": W_dtype,
             "data": "synthetic",
+            "full": args.full,
             "verified": verified,
-            "verification": "recount of 258 random rows copied back from HBM by the oracle's multi-threaded scan, bit-exact"
-                            if args.workload in ("freq", "fused") else "see bench.py:verify",
+            "verification": ("not run: the checks run under --full" if not args.full else
+                             "recount of 258 random rows copied back from HBM by the oracle's multi-threaded scan, bit-exact"
+                             if args.workload in ("freq", "fused") else "see bench.py:verify"),
             "config": {
                 "workload": f"{args.workload}: {args.variants} variants x {n} samples "
                             f"({'per GPU' if args.scaling == 'weak' else 'total'}), 2-bit hardcalls resident in HBM, "

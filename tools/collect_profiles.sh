@@ -8,7 +8,7 @@ OUT=gpurun_out/profiles
 rm -rf $OUT; mkdir -p $OUT
 run_bench() { # name args...
 	local name=$1; shift
-	python3 bench.py "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err
+	python3 bench.py --full "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err
 	echo "bench $name exit $?"
 }
 stats() { # name args...

@@ -28,7 +28,7 @@ else
   cd "$ROOT"
   for so in "$OUT"/*.so; do
     name=$(basename "$so" .so)
-    line=$(PGENHIP_LIB=$so python3 bench.py ${@:---workload score --score-cols 16} --steps ${STEPS:-10} --warmup 2 --cpu-seconds 0 --configs none --no-sql 2>/dev/null | tail -1)
+    line=$(PGENHIP_LIB=$so python3 bench.py ${@:---workload score --score-cols 16} --steps ${STEPS:-10} --warmup 2 --full --cpu-seconds 0 --configs none --no-sql 2>/dev/null | tail -1)
     printf "%-44s " "$name"; python3 - "$line" <<'PY'
 import json, sys
 try:
