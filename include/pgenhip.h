@@ -460,6 +460,42 @@ int pgh_reader_unpack_start(pgh_reader *rd, int slot, uint32_t v_begin, uint32_t
 int pgh_reader_unpack_wait(pgh_reader *rd, int slot);
 const char *pgh_reader_error(const pgh_reader *rd);
 
+/* ---- plink_glm: per-variant association regressions ---------------------------
+ * pgh_glm replaces plink_glm's per-variant loop (src/plink_glm.cpp:1250-1273: PgrGetD + Dosage16ToDoublesMinus9,
+ * then ComputeLinearRegression or ComputeLogisticRegression, :917-1215) for the variants [v_begin, v_end) of ds
+ * (a dataset or a shard group).  One output row per variant, in variant order.
+ *   phenotype   one double per output sample (subset order), NaN = missing
+ *   covariates  n_covar x n_out doubles, covariate-major, all finite (n_covar <= PGH_GLM_MAX_COVAR)
+ *   model       PGH_GLM_LINEAR or PGH_GLM_LOGISTIC (the bind-time 'auto' rule is the caller's)
+ *   firth       logistic only: a failed or unfinished Newton fit is refitted with Firth's penalty
+ * A variant's samples are those with a phenotype and a call (a dosage-track variant: a dosage or a call); its
+ * genotype value is the ALT dosage.  The fits run in FP64 on the device; a variant's row does not depend on the
+ * variants around it (tile, chunk or shard). */
+#define PGH_GLM_MAX_COVAR 20
+enum { PGH_GLM_LINEAR = 0, PGH_GLM_LOGISTIC = 1 };
+enum {
+	PGH_GLM_OK = 0,
+	PGH_GLM_TOO_FEW_SAMPLES = 1,
+	PGH_GLM_CONST_ALLELE = 2,
+	PGH_GLM_ZERO_VARIANCE = 3,
+	PGH_GLM_SINGULAR_MATRIX = 4,
+	PGH_GLM_NO_CONVERGENCE = 5,
+	PGH_GLM_SEPARATION = 6
+};
+typedef struct pgh_glm_row {
+	double beta, se, stat, p, a1_freq; /* NaN where the reference leaves NULL                 */
+	uint32_t obs_ct;
+	uint8_t errcode;                   /* PGH_GLM_*                                           */
+	uint8_t firth;                     /* 1: the row came from the Firth fallback (FIRTH_YN)  */
+	uint8_t pad[2];
+} pgh_glm_row;
+int pgh_glm(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end, const double *phenotype,
+            uint32_t n_covar, const double *covariates, int model, int firth, pgh_glm_row *out, char *errbuf);
+/* two-sided p of Student's t with df degrees of freedom (the reference's TstatToPvalue) */
+double pgh_glm_p_from_t(double t, double df);
+/* two-sided p of a standard normal z (ZstatToPvalue) */
+double pgh_glm_p_from_z(double z);
+
 /* ---- HWE exact tests (host) --------------------------------------------- */
 
 /* plink2::HweLnP (src/plink_hardy.cpp:78): ln of the two-sided exact-test p. */

@@ -1,0 +1,253 @@
+// api_glm.cpp -- pgh_glm: plink_glm's per-variant linear / logistic / Firth regressions (glm.hip) behind the C ABI.
+#include "api_internal.hpp"
+#include "glm.hpp"
+#include "glm_math.hpp"
+
+namespace {
+
+// Variants per chunk: bounds the per-variant state (logistic: ~9 KB a variant) and, on a file with dosage tracks,
+// the dense dosage rows of the chunk (512 MB at most).
+constexpr uint32_t kGlmChunk = 16384;
+constexpr uint64_t kGlmDosageBytes = 512ull << 20;
+
+int GlmOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end, const double *phenotype,
+           uint32_t k, const double *covariates, int model, int firth, pgh_glm_row *out, char *errbuf) {
+	PGH_ENTER(ds);
+	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct;
+	const uint32_t nv_all = v_end - v_begin;
+	const uint32_t kp = pgh::GlmPadCovar(k);
+	hipStream_t st = PghThreadStream();
+
+	// host staging: y (NaN = missing) and z sample-major, zero padded to kp columns
+	std::vector<double> hz(static_cast<size_t>(n_out) * kp, 0.0);
+	for (uint32_t j = 0; j < k; j++) {
+		for (uint32_t i = 0; i < n_out; i++) {
+			hz[static_cast<size_t>(i) * kp + j] = covariates[static_cast<size_t>(j) * n_out + i];
+		}
+	}
+	uint32_t n_y = 0;
+	for (uint32_t i = 0; i < n_out; i++) {
+		n_y += std::isnan(phenotype[i]) ? 0u : 1u;
+	}
+	// Linear: y and the covariates centred on their means over the samples with a phenotype.  The intercept absorbs
+	// the shift, so beta, SE and RSS are unchanged, and the whole-call Gram minus a variant's correction Gram then
+	// subtracts numbers of the data's spread rather than of its offset.
+	std::vector<double> hy(phenotype, phenotype + n_out);
+	if (model == PGH_GLM_LINEAR && n_y) {
+		double my = 0.0;
+		for (uint32_t i = 0; i < n_out; i++) {
+			my += std::isnan(hy[i]) ? 0.0 : hy[i];
+		}
+		my /= n_y;
+		for (uint32_t i = 0; i < n_out; i++) {
+			hy[i] -= my;
+		}
+		for (uint32_t j = 0; j < k; j++) {
+			double mz = 0.0;
+			for (uint32_t i = 0; i < n_out; i++) {
+				mz += std::isnan(hy[i]) ? 0.0 : hz[static_cast<size_t>(i) * kp + j];
+			}
+			mz /= n_y;
+			for (uint32_t i = 0; i < n_out; i++) {
+				hz[static_cast<size_t>(i) * kp + j] -= mz;
+			}
+		}
+	}
+	// which resident variants carry a dosage track
+	std::vector<int32_t> slot_all(nv_all, -1);
+	for (uint32_t v = v_begin; v < v_end && ds->dos_rows; v++) {
+		if (ds->dos_row_of[v - ds->v_begin] >= 0) {
+			slot_all[v - v_begin] = 0;
+		}
+	}
+	const bool any_dos = std::any_of(slot_all.begin(), slot_all.end(), [](int32_t s) { return s >= 0; });
+	uint32_t chunk = std::min(kGlmChunk, std::max(1u, nv_all));
+	if (any_dos) {
+		chunk = static_cast<uint32_t>(std::min<uint64_t>(chunk, std::max<uint64_t>(1, kGlmDosageBytes / (8ull * std::max(1u, n_out)))));
+	}
+
+	const bool logistic = model == PGH_GLM_LOGISTIC;
+	const uint32_t ns = kp + 4, q = k + 2, ne_gram = q * (q + 1) / 2;
+	const uint32_t ne_irls = pgh::GlmIrlsEntries(kp), pp = kp + 2;
+	const uint64_t hm = static_cast<uint64_t>(pgh::kGlmMaxP) * pgh::kGlmMaxP;
+	// one scratch block, carved in 256-byte pieces
+	auto up = [](uint64_t b) { return (b + 255) / 256 * 256; };
+	const uint64_t b_y = up(8ull * n_out), b_z = up(8ull * n_out * kp + 8), b_gram = up(8ull * ne_gram);
+	const uint64_t b_sums = up(8ull * chunk * ns), b_corr = up(8ull * chunk * ne_gram);
+	const uint64_t b_rows = up(sizeof(pgh_glm_row) * chunk), b_slot = up(4ull * chunk), b_list = up(4ull * chunk);
+	const uint64_t b_st = logistic ? up(sizeof(pgh::GlmState) * chunk) : 0, b_beta = logistic ? up(8ull * chunk * pp) : 0;
+	const uint64_t b_acc = logistic ? up(8ull * chunk * ne_irls) : 0, b_hm = logistic ? up(8ull * chunk * hm) : 0;
+	const uint64_t b_h0 = logistic && firth ? up(8ull * chunk * pp * pp) : 0;
+	const uint64_t b_dos = any_dos ? up(8ull * chunk * n_out) : 0;
+	const uint64_t total = b_y + b_z + b_gram + b_sums + b_corr + b_rows + b_slot + b_list + b_st + b_beta + b_acc + b_hm +
+	                       b_h0 + b_dos;
+	void *scratch = nullptr;
+	PGH_HIP(PghThreadScratch(total, st, &scratch), "glm scratch");
+	char *cur = static_cast<char *>(scratch);
+	auto take = [&](uint64_t b) {
+		char *p = cur;
+		cur += b;
+		return p;
+	};
+	double *d_y = reinterpret_cast<double *>(take(b_y));
+	double *d_z = reinterpret_cast<double *>(take(b_z));
+	double *d_gram = reinterpret_cast<double *>(take(b_gram));
+	double *d_sums = reinterpret_cast<double *>(take(b_sums));
+	double *d_corr = reinterpret_cast<double *>(take(b_corr));
+	pgh_glm_row *d_rows = reinterpret_cast<pgh_glm_row *>(take(b_rows));
+	int32_t *d_slot = reinterpret_cast<int32_t *>(take(b_slot));
+	uint32_t *d_list = reinterpret_cast<uint32_t *>(take(b_list));
+	pgh::GlmState *d_st = reinterpret_cast<pgh::GlmState *>(take(b_st));
+	double *d_beta = reinterpret_cast<double *>(take(b_beta));
+	double *d_acc = reinterpret_cast<double *>(take(b_acc));
+	double *d_hm = reinterpret_cast<double *>(take(b_hm));
+	double *d_h0 = reinterpret_cast<double *>(take(b_h0));
+	double *d_dos = reinterpret_cast<double *>(take(b_dos));
+
+	std::vector<int32_t> slot(chunk);
+	std::vector<uint32_t> vlist(chunk), flist;
+	std::vector<pgh::GlmState> hst;
+	HostSourceFence fence(st); // hy, hz, slot, vlist, flist feed asynchronous uploads
+	PGH_HIP(hipMemcpyAsync(d_y, hy.data(), 8ull * n_out, hipMemcpyHostToDevice, st), "glm phenotype upload");
+	if (kp) {
+		PGH_HIP(hipMemcpyAsync(d_z, hz.data(), 8ull * n_out * kp, hipMemcpyHostToDevice, st), "glm covariate upload");
+	}
+	if (!logistic) {
+		PGH_HIP(pgh::LaunchGlmGram(nullptr, 1, nullptr, 0, n_y, n_out, d_y, d_z, kp, k, d_gram, st), "glm gram kernel");
+	}
+	for (uint32_t c0 = 0; c0 < nv_all; c0 += chunk) {
+		const uint32_t nv = std::min(chunk, nv_all - c0);
+		pgh::GlmX g {};
+		g.view = ds->View();
+		g.v0 = v_begin + c0 - ds->v_begin;
+		g.n_out = n_out;
+		g.sel = subset ? subset->d_sel : nullptr;
+		uint32_t n_dos = 0;
+		if (any_dos) {
+			for (uint32_t i = 0; i < nv; i++) {
+				slot[i] = slot_all[c0 + i] >= 0 ? static_cast<int32_t>(n_dos) : -1;
+				if (slot[i] >= 0) {
+					vlist[n_dos++] = g.v0 + i;
+				}
+			}
+		}
+		if (n_dos) {
+			PGH_HIP(hipMemcpyAsync(d_slot, slot.data(), 4ull * nv, hipMemcpyHostToDevice, st), "glm slot upload");
+			PGH_HIP(hipMemcpyAsync(d_list, vlist.data(), 4ull * n_dos, hipMemcpyHostToDevice, st), "glm dosage list upload");
+			PGH_HIP(pgh::LaunchDosageUnpack(ds->View(), ds->Dosage(), 0, d_list, n_dos, g.sel, n_out, d_dos, n_out, st),
+			        "glm dosage unpack");
+			g.slot = d_slot;
+			g.dos = d_dos;
+		}
+		if (!logistic) {
+			PGH_HIP(pgh::LaunchGlmSums(g, nv, d_y, d_z, kp, d_sums, st), "glm sums kernel");
+			PGH_HIP(pgh::LaunchGlmGram(&g, nv, d_sums, ns, n_y, n_out, d_y, d_z, kp, k, d_corr, st), "glm correction kernel");
+			PGH_HIP(pgh::LaunchGlmLinearSolve(nv, d_sums, kp, k, d_gram, d_corr, d_rows, st), "glm solve kernel");
+		} else {
+			PGH_HIP(pgh::LaunchGlmSums(g, nv, d_y, d_z, 0, d_sums, st), "glm sums kernel");
+			PGH_HIP(pgh::LaunchGlmLogisticInit(nv, d_sums, kp, k, d_st, d_beta, d_rows, st), "glm logistic init");
+			// the Newton rules end every fit by its 15th iteration
+			for (int it = 0; it < 15; it++) {
+				PGH_HIP(pgh::LaunchGlmIrlsAcc(0, g, nullptr, nv, d_y, d_z, kp, d_st, d_beta, nullptr, d_acc, st),
+				        "glm newton pass");
+				PGH_HIP(pgh::LaunchGlmNewtonUpdate(nv, kp, k, d_acc, d_st, d_beta, d_hm, st), "glm newton update");
+			}
+			if (firth) {
+				hst.resize(nv);
+				PGH_HIP(hipMemcpyAsync(hst.data(), d_st, sizeof(pgh::GlmState) * nv, hipMemcpyDeviceToHost, st),
+				        "glm state copy");
+				PGH_HIP(hipStreamSynchronize(st), "glm state sync");
+				flist.clear();
+				for (uint32_t i = 0; i < nv; i++) {
+					if (hst[i].status == pgh::kGlmFailed || hst[i].status == pgh::kGlmUnfinished) {
+						flist.push_back(i);
+					}
+				}
+				const uint32_t nf = static_cast<uint32_t>(flist.size());
+				if (nf) {
+					PGH_HIP(hipMemcpyAsync(d_list, flist.data(), 4ull * nf, hipMemcpyHostToDevice, st), "glm firth list");
+					PGH_HIP(pgh::LaunchGlmFirthStart(d_list, nf, kp, d_st, d_beta, st), "glm firth start");
+					// 25 iterations and the test after the 26th: 27 evaluations at most
+					for (int it = 0; it < 27; it++) {
+						PGH_HIP(pgh::LaunchGlmIrlsAcc(1, g, d_list, nf, d_y, d_z, kp, d_st, d_beta, nullptr, d_acc, st),
+						        "glm firth pass 1");
+						PGH_HIP(pgh::LaunchGlmFirthUpdate(0, d_list, nf, kp, k, d_acc, d_st, d_beta, d_h0, d_hm, st),
+						        "glm firth update 1");
+						PGH_HIP(pgh::LaunchGlmIrlsAcc(2, g, d_list, nf, d_y, d_z, kp, d_st, d_beta, d_h0, d_acc, st),
+						        "glm firth pass 2");
+						PGH_HIP(pgh::LaunchGlmFirthUpdate(1, d_list, nf, kp, k, d_acc, d_st, d_beta, d_h0, d_hm, st),
+						        "glm firth update 2");
+					}
+				}
+			}
+			PGH_HIP(pgh::LaunchGlmLogisticFinish(nv, kp, k, d_st, d_beta, d_hm, d_rows, st), "glm logistic finish");
+		}
+		PGH_HIP(hipMemcpyAsync(out + c0, d_rows, sizeof(pgh_glm_row) * nv, hipMemcpyDeviceToHost, st), "glm rows copy");
+		PGH_HIP(hipStreamSynchronize(st), "glm sync");
+	}
+	return PGH_OK;
+}
+
+} // namespace
+
+extern "C" double pgh_glm_p_from_t(double t, double df) {
+	return pgh::GlmPFromT(t, df);
+}
+
+extern "C" double pgh_glm_p_from_z(double z) {
+	return pgh::GlmPFromZ(z);
+}
+
+extern "C" int pgh_glm(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                       const double *phenotype, uint32_t n_covar, const double *covariates, int model, int firth,
+                       pgh_glm_row *out, char *errbuf) {
+	int rc = CheckRange(ds, v_begin, v_end, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
+	}
+	if (model != PGH_GLM_LINEAR && model != PGH_GLM_LOGISTIC) {
+		SetErr(errbuf, "model must be PGH_GLM_LINEAR or PGH_GLM_LOGISTIC");
+		return PGH_ERR_ARG;
+	}
+	if (n_covar > PGH_GLM_MAX_COVAR) {
+		SetErr(errbuf, "at most " + std::to_string(PGH_GLM_MAX_COVAR) + " covariates are supported, got " +
+		                   std::to_string(n_covar));
+		return PGH_ERR_ARG;
+	}
+	if (subset && subset->ds != ds) {
+		SetErr(errbuf, "sample subset belongs to a different dataset");
+		return PGH_ERR_ARG;
+	}
+	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct;
+	if ((n_out && !phenotype) || (n_covar && n_out && !covariates) || (v_end > v_begin && !out)) {
+		SetErr(errbuf, "null argument");
+		return PGH_ERR_ARG;
+	}
+	for (uint64_t i = 0; i < static_cast<uint64_t>(n_covar) * n_out; i++) {
+		if (!std::isfinite(covariates[i])) {
+			SetErr(errbuf, "covariate " + std::to_string(i / n_out) + " is not finite at sample " +
+			                   std::to_string(i % n_out));
+			return PGH_ERR_ARG;
+		}
+	}
+	if (v_end == v_begin) {
+		return PGH_OK;
+	}
+	if (ds->IsGroup()) {
+		// every shard fills its own slice of out; nothing is exchanged
+		for (size_t k = 0; k < ds->shards.size(); k++) {
+			const pgh_dataset *s = ds->shards[k];
+			const uint32_t lo = std::max(v_begin, s->v_begin), hi = std::min(v_end, s->v_end);
+			if (lo >= hi) {
+				continue;
+			}
+			rc = GlmOne(s, subset ? subset->parts[k] : nullptr, lo, hi, phenotype, n_covar, covariates, model, firth,
+			            out + (lo - v_begin), errbuf);
+			if (rc != PGH_OK) {
+				return rc;
+			}
+		}
+		return PGH_OK;
+	}
+	return GlmOne(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, model, firth, out, errbuf);
+}

@@ -1,0 +1,814 @@
+// glm.hip -- plink_glm's per-variant regressions in FP64 (glm.hpp).
+//
+// Linear: one pass over the rows.  Only the genotype terms change between variants, so a workgroup accumulates
+// {n, sum x, sum x^2, sum x y, sum x z_j} for a tile of T variants (each sample's y and z are loaded once for the
+// tile); the covariate block [1, z, y]' [1, z, y] is one Gram per call, and a variant with missing calls subtracts
+// the Gram of those samples (a compacted list per sample chunk: sparse when calls are rarely missing, any count
+// works).  The solve is a Cholesky of the augmented [1, z, x, y] matrix per variant.
+// Logistic / Firth: rounds of an accumulation launch (one workgroup per variant still in play) and a per-variant
+// update launch (one thread per variant).
+//
+// Determinism: a thread always owns the same samples (stride 256) and reductions run in one fixed order, so a
+// variant's sums do not depend on its place in a tile, chunk or shard.
+#include "glm.hpp"
+#include "glm_math.hpp"
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+namespace pgh {
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kWaves = kBlock / 64;
+constexpr int kMaxP = 22; // intercept + genotype + PGH_GLM_MAX_COVAR
+
+__device__ inline double GlmValue(const GlmX &g, uint32_t v, uint32_t i) {
+	const int32_t s = g.slot ? g.slot[v] : -1;
+	if (s >= 0) {
+		return g.dos[static_cast<uint64_t>(s) * g.n_out + i];
+	}
+	const uint32_t raw = g.sel ? g.sel[i] : i;
+	const uint8_t *row = g.view.rows + static_cast<uint64_t>(g.v0 + v) * g.view.pitch;
+	const uint32_t c = (row[raw >> 2] >> (2 * (raw & 3))) & 3u;
+	return c == 3u ? -9.0 : static_cast<double>(c);
+}
+
+__device__ inline double WaveSum(double x) {
+	for (int d = 32; d >= 1; d >>= 1) {
+		x += __shfl_xor(x, d);
+	}
+	return x;
+}
+
+// Block sum of NE per-thread values in a fixed order: butterfly within each wave, then waves 0..3 in turn.
+template <int NE>
+__device__ inline void BlockSums(const double (&acc)[NE], double *lds, double *out) {
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+	for (int e = 0; e < NE; e++) {
+		const double s = WaveSum(acc[e]);
+		if (lane == 0) {
+			lds[wave * NE + e] = s;
+		}
+	}
+	__syncthreads();
+	for (int e = threadIdx.x; e < NE; e += kBlock) {
+		double s = lds[e];
+		for (int w = 1; w < kWaves; w++) {
+			s += lds[w * NE + e];
+		}
+		out[e] = s;
+	}
+}
+
+__device__ inline int PackIdx(int a, int b, int q) { // a <= b < q
+	return a * q - a * (a - 1) / 2 + (b - a);
+}
+
+// ---------------------------------------------------------------------------
+// linear sums
+// ---------------------------------------------------------------------------
+
+template <int KP, int T>
+__global__ void __launch_bounds__(kBlock) GlmSumsKernel(GlmX g, uint32_t nv, const double *__restrict__ y,
+                                                        const double *__restrict__ z, double *__restrict__ sums) {
+	constexpr int NS = KP + 4;
+	__shared__ double lds[kWaves * NS * T];
+	const uint32_t v0 = blockIdx.x * T;
+	double acc[NS * T];
+#pragma unroll
+	for (int e = 0; e < NS * T; e++) {
+		acc[e] = 0.0;
+	}
+	for (uint32_t i = threadIdx.x; i < g.n_out; i += kBlock) {
+		const double yi = y[i];
+		if (yi != yi) {
+			continue;
+		}
+		double zi[KP > 0 ? KP : 1];
+#pragma unroll
+		for (int j = 0; j < KP; j++) {
+			zi[j] = z[static_cast<uint64_t>(i) * KP + j];
+		}
+#pragma unroll
+		for (int t = 0; t < T; t++) {
+			if (v0 + t < nv) {
+				const double x = GlmValue(g, v0 + t, i);
+				if (x != -9.0) {
+					double *a = acc + t * NS;
+					a[0] += 1.0;
+					a[1] += x;
+					a[2] += x * x;
+					a[3] += x * yi;
+#pragma unroll
+					for (int j = 0; j < KP; j++) {
+						a[4 + j] += x * zi[j];
+					}
+				}
+			}
+		}
+	}
+	__shared__ double tile[NS * T];
+	BlockSums<NS * T>(acc, lds, tile);
+	__syncthreads();
+	for (int e = threadIdx.x; e < NS * T; e += kBlock) {
+		if (v0 + e / NS < nv) {
+			sums[static_cast<uint64_t>(v0) * NS + e] = tile[e];
+		}
+	}
+}
+
+// ---------------------------------------------------------------------------
+// Gram of [1, z, y] over a compacted sample list
+// ---------------------------------------------------------------------------
+
+__global__ void __launch_bounds__(kBlock) GlmGramKernel(GlmX g, int per_variant, const double *__restrict__ sums,
+                                                        uint32_t sums_stride, uint32_t n_y, uint32_t n_out,
+                                                        const double *__restrict__ y, const double *__restrict__ z,
+                                                        uint32_t kp, uint32_t k, double *__restrict__ out) {
+	const uint32_t q = k + 2, ne = q * (q + 1) / 2;
+	const uint32_t v = blockIdx.x;
+	double *dst = out + static_cast<uint64_t>(v) * ne;
+	if (per_variant && sums[static_cast<uint64_t>(v) * sums_stride] == static_cast<double>(n_y)) {
+		for (uint32_t e = threadIdx.x; e < ne; e += kBlock) {
+			dst[e] = 0.0;
+		}
+		return;
+	}
+	extern __shared__ double list[]; // kBlock rows of q doubles (sized at launch)
+	__shared__ uint32_t wave_ct[kWaves];
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	// entry owned by this thread
+	int ea = -1, eb = -1;
+	if (threadIdx.x < ne) {
+		int t = threadIdx.x, a = 0;
+		while (t >= static_cast<int>(q) - a) {
+			t -= q - a;
+			a++;
+		}
+		ea = a;
+		eb = a + t;
+	}
+	double acc = 0.0;
+	for (uint32_t c0 = 0; c0 < n_out; c0 += kBlock) {
+		const uint32_t i = c0 + threadIdx.x;
+		bool take = false;
+		double yi = 0.0;
+		if (i < n_out) {
+			yi = y[i];
+			take = yi == yi && (!per_variant || GlmValue(g, v, i) == -9.0);
+		}
+		const uint64_t bal = __ballot(take);
+		if (lane == 0) {
+			wave_ct[wave] = static_cast<uint32_t>(__popcll(bal));
+		}
+		__syncthreads();
+		uint32_t base = 0, total = 0;
+		for (int w = 0; w < kWaves; w++) {
+			base += w < wave ? wave_ct[w] : 0u;
+			total += wave_ct[w];
+		}
+		if (take) {
+			const uint32_t pos = base + static_cast<uint32_t>(__popcll(bal & ((1ull << lane) - 1ull)));
+			double *r = list + pos * q;
+			r[0] = 1.0;
+			for (uint32_t j = 0; j < k; j++) {
+				r[1 + j] = z[static_cast<uint64_t>(i) * kp + j];
+			}
+			r[q - 1] = yi;
+		}
+		__syncthreads();
+		if (ea >= 0) {
+			for (uint32_t s = 0; s < total; s++) {
+				acc += list[s * q + ea] * list[s * q + eb];
+			}
+		}
+		__syncthreads();
+	}
+	if (ea >= 0) {
+		dst[threadIdx.x] = acc;
+	}
+}
+
+// ---------------------------------------------------------------------------
+// linear solve: one thread per variant
+// ---------------------------------------------------------------------------
+
+__device__ inline void SetRowNull(pgh_glm_row &r) {
+	r.beta = r.se = r.stat = r.p = r.a1_freq = NAN;
+	r.obs_ct = 0;
+	r.errcode = PGH_GLM_OK;
+	r.firth = 0;
+	r.pad[0] = r.pad[1] = 0;
+}
+
+__global__ void GlmLinearSolveKernel(uint32_t nv, const double *__restrict__ sums, uint32_t kp, uint32_t k,
+                                     const double *__restrict__ gram, const double *__restrict__ corr,
+                                     pgh_glm_row *__restrict__ rows) {
+	const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+	if (v >= nv) {
+		return;
+	}
+	const uint32_t ns = kp + 4, q = k + 2, ne = q * (q + 1) / 2;
+	const double *s = sums + static_cast<uint64_t>(v) * ns;
+	const double *c = corr + static_cast<uint64_t>(v) * ne;
+	pgh_glm_row r;
+	SetRowNull(r);
+	const double n = s[0];
+	const int p = static_cast<int>(k) + 2;
+	r.obs_ct = static_cast<uint32_t>(n);
+	if (n < p + 1) {
+		r.errcode = PGH_GLM_TOO_FEW_SAMPLES;
+		rows[v] = r;
+		return;
+	}
+	r.a1_freq = s[1] / (2.0 * n);
+	if (s[2] - s[1] * s[1] / n < 1e-20) {
+		r.errcode = PGH_GLM_CONST_ALLELE;
+		rows[v] = r;
+		return;
+	}
+	// augmented matrix, order [1, z_1..z_k, x, y]; u = [1, z, y] is the Gram's order
+	constexpr int M = kMaxP + 1;
+	double a[M * M];
+	const int xi = p - 1, yi = p;
+	auto uidx = [&](int j) { return j <= static_cast<int>(k) ? j : yi; }; // u index -> matrix index
+	for (int ua = 0; ua < static_cast<int>(q); ua++) {
+		for (int ub = ua; ub < static_cast<int>(q); ub++) {
+			const int e = PackIdx(ua, ub, q);
+			const double val = gram[e] - c[e];
+			const int ia = uidx(ua), ib = uidx(ub);
+			a[ib * M + ia] = val; // lower triangle: ib >= ia
+		}
+	}
+	a[xi * M + 0] = s[1];
+	for (int j = 0; j < static_cast<int>(k); j++) {
+		a[xi * M + 1 + j] = s[4 + j];
+	}
+	a[xi * M + xi] = s[2];
+	a[yi * M + xi] = s[3];
+	if (!GlmCholesky(a, p, M, k ? 1e-10 : 0.0, nullptr)) {
+		r.errcode = PGH_GLM_SINGULAR_MATRIX;
+		rows[v] = r;
+		return;
+	}
+	double rss = a[yi * M + yi];
+	for (int j = 0; j < p; j++) {
+		double l = a[yi * M + j];
+		for (int t = 0; t < j; t++) {
+			l -= a[yi * M + t] * a[j * M + t];
+		}
+		l /= a[j * M + j];
+		a[yi * M + j] = l;
+		rss -= l * l;
+	}
+	rss = rss < 0.0 ? 0.0 : rss;
+	const double lxx = a[xi * M + xi];
+	const double df = n - p;
+	const double se2 = rss / df / (lxx * lxx);
+	const double beta = a[yi * M + xi] / lxx;
+	r.beta = beta;
+	if (se2 < 1e-30) {
+		r.errcode = PGH_GLM_ZERO_VARIANCE;
+		rows[v] = r;
+		return;
+	}
+	r.se = sqrt(se2);
+	r.stat = beta / r.se;
+	r.p = GlmPFromT(r.stat, df);
+	rows[v] = r;
+}
+
+// ---------------------------------------------------------------------------
+// logistic / Firth
+// ---------------------------------------------------------------------------
+
+__global__ void GlmLogisticInitKernel(uint32_t nv, const double *__restrict__ sums, uint32_t kp_sums, uint32_t kp,
+                                      uint32_t k, GlmState *__restrict__ st, double *__restrict__ beta,
+                                      pgh_glm_row *__restrict__ rows) {
+	const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+	if (v >= nv) {
+		return;
+	}
+	const double *s = sums + static_cast<uint64_t>(v) * (kp_sums + 4);
+	pgh_glm_row r;
+	SetRowNull(r);
+	GlmState g;
+	g.status = kGlmActive;
+	g.iter = 0;
+	g.firth = 0;
+	g.pad = 0;
+	g.min_delta = 1e9;
+	g.delta_max = 0.0;
+	g.loglik = g.loglik_old = 0.0;
+	const double n = s[0];
+	r.obs_ct = static_cast<uint32_t>(n);
+	if (n < static_cast<double>(k) + 3.0) {
+		r.errcode = PGH_GLM_TOO_FEW_SAMPLES;
+		g.status = kGlmDecided + PGH_GLM_TOO_FEW_SAMPLES;
+	} else {
+		r.a1_freq = s[1] / (2.0 * n);
+		if (s[2] - s[1] * s[1] / n < 1e-20) {
+			r.errcode = PGH_GLM_CONST_ALLELE;
+			g.status = kGlmDecided + PGH_GLM_CONST_ALLELE;
+		}
+	}
+	for (uint32_t j = 0; j < kp + 2; j++) {
+		beta[static_cast<uint64_t>(v) * (kp + 2) + j] = 0.0;
+	}
+	st[v] = g;
+	rows[v] = r;
+}
+
+template <int KP, int MODE>
+__global__ void __launch_bounds__(kBlock) GlmIrlsAccKernel(GlmX g, const uint32_t *__restrict__ list,
+                                                           const double *__restrict__ y, const double *__restrict__ z,
+                                                           const GlmState *__restrict__ st,
+                                                           const double *__restrict__ beta,
+                                                           const double *__restrict__ hinv0, double *__restrict__ acc_out) {
+	constexpr int PP = KP + 2;
+	constexpr int NH = PP * (PP + 1) / 2;
+	constexpr int NE = NH + PP + 2;
+	const uint32_t v = list ? list[blockIdx.x] : blockIdx.x;
+	if (st[v].status != kGlmActive) {
+		return;
+	}
+	__shared__ double lds[kWaves * NE];
+	__shared__ double hin[MODE == 2 ? PP * PP : 1];
+	double b[PP];
+#pragma unroll
+	for (int j = 0; j < PP; j++) {
+		b[j] = beta[static_cast<uint64_t>(v) * PP + j];
+	}
+	if (MODE == 2) {
+		for (int e = threadIdx.x; e < PP * PP; e += kBlock) {
+			hin[e] = hinv0[static_cast<uint64_t>(v) * PP * PP + e];
+		}
+		__syncthreads();
+	}
+	double acc[NE];
+#pragma unroll
+	for (int e = 0; e < NE; e++) {
+		acc[e] = 0.0;
+	}
+	for (uint32_t i = threadIdx.x; i < g.n_out; i += kBlock) {
+		const double yi = y[i];
+		if (yi != yi) {
+			continue;
+		}
+		const double x = GlmValue(g, v, i);
+		if (x == -9.0) {
+			continue;
+		}
+		double xr[PP];
+		xr[0] = 1.0;
+		xr[1] = x;
+#pragma unroll
+		for (int j = 0; j < KP; j++) {
+			xr[2 + j] = z[static_cast<uint64_t>(i) * KP + j];
+		}
+		double eta = 0.0;
+#pragma unroll
+		for (int j = 0; j < PP; j++) {
+			eta += b[j] * xr[j];
+		}
+		const double mu = 1.0 / (1.0 + exp(-eta));
+		const double var = mu * (1.0 - mu);
+		double w = var, r = mu - yi;
+		if (MODE == 1) {
+			if (mu == 0.0 || mu == 1.0) {
+				acc[NE - 1] += 1.0;
+			}
+			acc[NH + PP] += yi != 0.0 ? log(mu) : log1p(-mu);
+		} else if (MODE == 2) {
+			double h = 0.0;
+#pragma unroll
+			for (int a = 0; a < PP; a++) {
+				double t = 0.0;
+#pragma unroll
+				for (int c = 0; c < PP; c++) {
+					t += hin[a * PP + c] * xr[c];
+				}
+				h += xr[a] * t;
+			}
+			h *= var;
+			r = (yi - mu) + h * (0.5 - mu);
+			w = (1.0 + h) * var;
+		}
+		int e = 0;
+#pragma unroll
+		for (int a = 0; a < PP; a++) {
+			const double wa = w * xr[a];
+#pragma unroll
+			for (int c = a; c < PP; c++) {
+				acc[e++] += wa * xr[c];
+			}
+		}
+		if (MODE != 1) {
+#pragma unroll
+			for (int a = 0; a < PP; a++) {
+				acc[NH + a] += r * xr[a];
+			}
+		}
+	}
+	BlockSums<NE>(acc, lds, acc_out + static_cast<uint64_t>(v) * NE);
+}
+
+// unpack the real p x p block of a packed upper matrix of order pp into a full row-major matrix of stride kMaxP
+__device__ inline void UnpackSym(const double *packed, int pp, int p, double *m) {
+	for (int a = 0; a < p; a++) {
+		for (int c = a; c < p; c++) {
+			const double val = packed[PackIdx(a, c, pp)];
+			m[a * kMaxP + c] = val;
+			m[c * kMaxP + a] = val;
+		}
+	}
+}
+
+__global__ void GlmNewtonUpdateKernel(uint32_t nv, uint32_t kp, uint32_t k, const double *__restrict__ acc,
+                                      GlmState *__restrict__ st, double *__restrict__ beta, double *__restrict__ hmat) {
+	const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+	if (v >= nv || st[v].status != kGlmActive) {
+		return;
+	}
+	const int pp = kp + 2, p = k + 2;
+	const int nh = pp * (pp + 1) / 2, ne = nh + pp + 2;
+	const double *a = acc + static_cast<uint64_t>(v) * ne;
+	double h[kMaxP * kMaxP], l[kMaxP * kMaxP], d[kMaxP];
+	UnpackSym(a, pp, p, h);
+	double *hs = hmat + static_cast<uint64_t>(v) * kMaxP * kMaxP;
+	for (int e = 0; e < p * kMaxP; e++) {
+		hs[e] = h[e];
+	}
+	// the reference's Cholesky: a negative pivot is replaced by 1e-6 rather than failing the fit
+	for (int j = 0; j < p; j++) {
+		double dd = h[j * kMaxP + j];
+		for (int t = 0; t < j; t++) {
+			dd -= l[j * kMaxP + t] * l[j * kMaxP + t];
+		}
+		const double lj = dd >= 0.0 ? sqrt(dd) : 1e-6;
+		l[j * kMaxP + j] = lj;
+		const double inv = 1.0 / lj;
+		for (int i = j + 1; i < p; i++) {
+			double s = h[i * kMaxP + j];
+			for (int t = 0; t < j; t++) {
+				s -= l[i * kMaxP + t] * l[j * kMaxP + t];
+			}
+			l[i * kMaxP + j] = s * inv;
+		}
+	}
+	for (int j = 0; j < p; j++) {
+		d[j] = a[nh + j];
+	}
+	GlmCholSolve(l, p, kMaxP, d);
+	GlmState s = st[v];
+	double *b = beta + static_cast<uint64_t>(v) * pp;
+	double delta = 0.0;
+	for (int j = 0; j < p; j++) {
+		delta += fabs(d[j]);
+		b[j] -= d[j];
+	}
+	const int it = s.iter++;
+	s.min_delta = delta < s.min_delta ? delta : s.min_delta;
+	if (delta != delta) {
+		s.status = kGlmFailed;
+	} else {
+		bool done = false;
+		if (it > 3) {
+			if ((delta > 20.0 && delta > 2 * s.min_delta) || (it > 6 && fabs(1.0 - delta) < 1e-3)) {
+				s.status = kGlmFailed;
+				done = true;
+			} else if (it > 13) {
+				s.status = kGlmUnfinished;
+				for (int j = 0; j < p; j++) {
+					if (fabs(b[j]) > 8e3) {
+						s.status = kGlmFailed;
+					}
+				}
+				done = true;
+			}
+		}
+		if (!done && delta < 1e-4) {
+			s.status = kGlmConverged;
+			for (int j = 0; j < p; j++) {
+				if (fabs(b[j]) > 6e4) {
+					s.status = kGlmFailed;
+				}
+			}
+		}
+	}
+	st[v] = s;
+}
+
+__global__ void GlmFirthStartKernel(const uint32_t *__restrict__ list, uint32_t n, uint32_t kp,
+                                    GlmState *__restrict__ st, double *__restrict__ beta) {
+	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+	if (t >= n) {
+		return;
+	}
+	const uint32_t v = list[t];
+	GlmState s = st[v];
+	s.status = kGlmActive;
+	s.iter = 0;
+	s.firth = 1;
+	s.delta_max = 0.0;
+	s.loglik = s.loglik_old = 0.0;
+	st[v] = s;
+	for (uint32_t j = 0; j < kp + 2; j++) {
+		beta[static_cast<uint64_t>(v) * (kp + 2) + j] = 0.0;
+	}
+}
+
+// half 0: after the first pass (I(beta), log-likelihood): penalised log-likelihood and I(beta)^-1.
+// half 1: after the second pass (U*, second-weight Hessian): the convergence tests, then the capped step.
+__global__ void GlmFirthUpdateKernel(int half, const uint32_t *__restrict__ list, uint32_t n, uint32_t kp, uint32_t k,
+                                     const double *__restrict__ acc, GlmState *__restrict__ st,
+                                     double *__restrict__ beta, double *__restrict__ hinv0, double *__restrict__ hmat) {
+	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+	if (t >= n) {
+		return;
+	}
+	const uint32_t v = list[t];
+	GlmState s = st[v];
+	if (s.status != kGlmActive) {
+		return;
+	}
+	const int pp = kp + 2, p = k + 2;
+	const int nh = pp * (pp + 1) / 2, ne = nh + pp + 2;
+	const double *a = acc + static_cast<uint64_t>(v) * ne;
+	double h[kMaxP * kMaxP], col[kMaxP];
+	UnpackSym(a, pp, p, h);
+	if (half == 0) {
+		double logdet = 0.0;
+		if (a[ne - 1] != 0.0 || !GlmCholesky(h, p, kMaxP, 1e-13, &logdet)) {
+			s.status = kGlmFailed;
+			st[v] = s;
+			return;
+		}
+		s.loglik = a[nh + pp] + 0.5 * logdet;
+		double *dst = hinv0 + static_cast<uint64_t>(v) * pp * pp;
+		double inv[kMaxP * kMaxP];
+		GlmCholInverse(h, p, kMaxP, inv, col);
+		for (int i = 0; i < pp; i++) {
+			for (int c = 0; c < pp; c++) {
+				dst[i * pp + c] = (i < p && c < p) ? inv[i * kMaxP + c] : 0.0;
+			}
+		}
+		st[v] = s;
+		return;
+	}
+	double ustar_max = 0.0;
+	for (int j = 0; j < p; j++) {
+		ustar_max = fmax(ustar_max, fabs(a[nh + j]));
+	}
+	if (s.iter > 0) {
+		if (s.delta_max <= 1e-4 && ustar_max < 1e-4 && s.loglik - s.loglik_old < 1e-4) {
+			s.status = kGlmConverged;
+			st[v] = s;
+			return;
+		}
+		if (s.iter > 25) {
+			s.status = kGlmUnfinished;
+			st[v] = s;
+			return;
+		}
+	}
+	s.loglik_old = s.loglik;
+	if (!GlmCholesky(h, p, kMaxP, 1e-13, nullptr)) {
+		s.status = kGlmFailed;
+		st[v] = s;
+		return;
+	}
+	double inv[kMaxP * kMaxP];
+	GlmCholInverse(h, p, kMaxP, inv, col);
+	double *hs = hmat + static_cast<uint64_t>(v) * kMaxP * kMaxP;
+	for (int e = 0; e < p * kMaxP; e++) {
+		hs[e] = inv[e];
+	}
+	double dl[kMaxP];
+	double dmax = 0.0;
+	for (int i = 0; i < p; i++) {
+		double sdot = 0.0;
+		for (int c = 0; c < p; c++) {
+			sdot += inv[i * kMaxP + c] * a[nh + c];
+		}
+		dl[i] = sdot;
+		dmax = fmax(dmax, fabs(sdot));
+	}
+	if (dmax > 5.0) {
+		const double sc = 5.0 / dmax;
+		for (int i = 0; i < p; i++) {
+			dl[i] *= sc;
+		}
+		dmax = 5.0;
+	}
+	s.delta_max = dmax;
+	double *b = beta + static_cast<uint64_t>(v) * pp;
+	for (int i = 0; i < p; i++) {
+		b[i] += dl[i];
+	}
+	s.iter++;
+	st[v] = s;
+}
+
+__global__ void GlmLogisticFinishKernel(uint32_t nv, uint32_t kp, uint32_t k, const GlmState *__restrict__ st, const double *__restrict__ beta,
+                                        const double *__restrict__ hmat, pgh_glm_row *__restrict__ rows) {
+	const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+	if (v >= nv) {
+		return;
+	}
+	const GlmState s = st[v];
+	if (s.status >= kGlmDecided) {
+		return; // row written by the init kernel
+	}
+	pgh_glm_row r = rows[v];
+	const int pp = kp + 2, p = k + 2;
+	const double *hs = hmat + static_cast<uint64_t>(v) * kMaxP * kMaxP;
+	double se2;
+	if (s.firth) {
+		if (s.status == kGlmFailed) {
+			r.errcode = PGH_GLM_NO_CONVERGENCE;
+			rows[v] = r;
+			return;
+		}
+		r.firth = 1;
+		se2 = hs[1 * kMaxP + 1];
+	} else {
+		if (s.status != kGlmConverged) {
+			r.errcode = s.status == kGlmFailed ? PGH_GLM_SEPARATION : PGH_GLM_NO_CONVERGENCE;
+			rows[v] = r;
+			return;
+		}
+		double l[kMaxP * kMaxP], col[kMaxP];
+		for (int e = 0; e < p * kMaxP; e++) {
+			l[e] = hs[e];
+		}
+		if (!GlmCholesky(l, p, kMaxP, 1e-13, nullptr)) {
+			r.errcode = PGH_GLM_SINGULAR_MATRIX;
+			rows[v] = r;
+			return;
+		}
+		for (int i = 0; i < p; i++) {
+			col[i] = i == 1 ? 1.0 : 0.0;
+		}
+		GlmCholSolve(l, p, kMaxP, col);
+		se2 = col[1];
+	}
+	r.beta = beta[static_cast<uint64_t>(v) * pp + 1];
+	if (se2 < 1e-30) {
+		r.errcode = PGH_GLM_ZERO_VARIANCE;
+		rows[v] = r;
+		return;
+	}
+	r.se = sqrt(se2);
+	r.stat = r.beta / r.se;
+	r.p = GlmPFromZ(r.stat);
+	rows[v] = r;
+}
+
+uint32_t Blocks(uint32_t n, uint32_t per) {
+	return (n + per - 1) / per;
+}
+
+} // namespace
+
+uint32_t GlmPadCovar(uint32_t k) {
+	static const uint32_t widths[] = {0, 1, 2, 4, 8, 12, 16, 20};
+	for (uint32_t w : widths) {
+		if (k <= w) {
+			return w;
+		}
+	}
+	return 0xffffffffu;
+}
+
+hipError_t LaunchGlmSums(const GlmX &g, uint32_t nv, const double *y, const double *z, uint32_t kp, double *sums,
+                         hipStream_t stream) {
+	if (nv == 0) {
+		return hipSuccess;
+	}
+#define PGH_SUMS(KP_, T_)                                                                                              \
+	case KP_:                                                                                                          \
+		GlmSumsKernel<KP_, T_><<<Blocks(nv, T_), kBlock, 0, stream>>>(g, nv, y, z, sums);                              \
+		break;
+	switch (kp) {
+		PGH_SUMS(0, 8)
+		PGH_SUMS(1, 8)
+		PGH_SUMS(2, 8)
+		PGH_SUMS(4, 4)
+		PGH_SUMS(8, 4)
+		PGH_SUMS(12, 2)
+		PGH_SUMS(16, 2)
+		PGH_SUMS(20, 2)
+	default:
+		return hipErrorInvalidValue;
+	}
+#undef PGH_SUMS
+	return hipGetLastError();
+}
+
+hipError_t LaunchGlmGram(const GlmX *g, uint32_t nv, const double *sums, uint32_t sums_stride, uint32_t n_y,
+                         uint32_t n_out, const double *y, const double *z, uint32_t kp, uint32_t k, double *out,
+                         hipStream_t stream) {
+	if (k > 20) {
+		return hipErrorInvalidValue;
+	}
+	if (g && nv == 0) {
+		return hipSuccess;
+	}
+	GlmX none {};
+	GlmGramKernel<<<g ? nv : 1u, kBlock, sizeof(double) * kBlock * (k + 2), stream>>>(g ? *g : none, g ? 1 : 0, sums, sums_stride, n_y, n_out, y, z,
+	                                                  kp, k, out);
+	return hipGetLastError();
+}
+
+hipError_t LaunchGlmLinearSolve(uint32_t nv, const double *sums, uint32_t kp, uint32_t k, const double *gram,
+                                const double *corr, pgh_glm_row *rows, hipStream_t stream) {
+	if (nv == 0) {
+		return hipSuccess;
+	}
+	GlmLinearSolveKernel<<<Blocks(nv, 64), 64, 0, stream>>>(nv, sums, kp, k, gram, corr, rows);
+	return hipGetLastError();
+}
+
+hipError_t LaunchGlmLogisticInit(uint32_t nv, const double *sums, uint32_t kp, uint32_t k, GlmState *st, double *beta,
+                                 pgh_glm_row *rows, hipStream_t stream) {
+	if (nv == 0) {
+		return hipSuccess;
+	}
+	GlmLogisticInitKernel<<<Blocks(nv, 64), 64, 0, stream>>>(nv, sums, 0, kp, k, st, beta, rows);
+	return hipGetLastError();
+}
+
+hipError_t LaunchGlmIrlsAcc(int mode, const GlmX &g, const uint32_t *list, uint32_t n, const double *y, const double *z,
+                            uint32_t kp, const GlmState *st, const double *beta, const double *hinv0, double *acc,
+                            hipStream_t stream) {
+	if (n == 0) {
+		return hipSuccess;
+	}
+#define PGH_IRLS_MODE(KP_)                                                                                             \
+	case KP_:                                                                                                          \
+		if (mode == 0) {                                                                                               \
+			GlmIrlsAccKernel<KP_, 0><<<n, kBlock, 0, stream>>>(g, list, y, z, st, beta, hinv0, acc);                   \
+		} else if (mode == 1) {                                                                                        \
+			GlmIrlsAccKernel<KP_, 1><<<n, kBlock, 0, stream>>>(g, list, y, z, st, beta, hinv0, acc);                   \
+		} else {                                                                                                       \
+			GlmIrlsAccKernel<KP_, 2><<<n, kBlock, 0, stream>>>(g, list, y, z, st, beta, hinv0, acc);                   \
+		}                                                                                                              \
+		break;
+	switch (kp) {
+		PGH_IRLS_MODE(0)
+		PGH_IRLS_MODE(1)
+		PGH_IRLS_MODE(2)
+		PGH_IRLS_MODE(4)
+		PGH_IRLS_MODE(8)
+		PGH_IRLS_MODE(12)
+		PGH_IRLS_MODE(16)
+		PGH_IRLS_MODE(20)
+	default:
+		return hipErrorInvalidValue;
+	}
+#undef PGH_IRLS_MODE
+	return hipGetLastError();
+}
+
+hipError_t LaunchGlmNewtonUpdate(uint32_t nv, uint32_t kp, uint32_t k, const double *acc, GlmState *st, double *beta,
+                                 double *hmat, hipStream_t stream) {
+	if (nv == 0) {
+		return hipSuccess;
+	}
+	GlmNewtonUpdateKernel<<<Blocks(nv, 64), 64, 0, stream>>>(nv, kp, k, acc, st, beta, hmat);
+	return hipGetLastError();
+}
+
+hipError_t LaunchGlmFirthStart(const uint32_t *list, uint32_t n, uint32_t kp, GlmState *st, double *beta,
+                               hipStream_t stream) {
+	if (n == 0) {
+		return hipSuccess;
+	}
+	GlmFirthStartKernel<<<Blocks(n, 64), 64, 0, stream>>>(list, n, kp, st, beta);
+	return hipGetLastError();
+}
+
+hipError_t LaunchGlmFirthUpdate(int half, const uint32_t *list, uint32_t n, uint32_t kp, uint32_t k, const double *acc,
+                                GlmState *st, double *beta, double *hinv0, double *hmat, hipStream_t stream) {
+	if (n == 0) {
+		return hipSuccess;
+	}
+	GlmFirthUpdateKernel<<<Blocks(n, 64), 64, 0, stream>>>(half, list, n, kp, k, acc, st, beta, hinv0, hmat);
+	return hipGetLastError();
+}
+
+hipError_t LaunchGlmLogisticFinish(uint32_t nv, uint32_t kp, uint32_t k, const GlmState *st,
+                                   const double *beta, const double *hmat, pgh_glm_row *rows, hipStream_t stream) {
+	if (nv == 0) {
+		return hipSuccess;
+	}
+	GlmLogisticFinishKernel<<<Blocks(nv, 64), 64, 0, stream>>>(nv, kp, k, st, beta, hmat, rows);
+	return hipGetLastError();
+}
+
+} // namespace pgh

@@ -1,0 +1,78 @@
+// glm.hpp -- launch wrappers of plink_glm's kernels (glm.hip).  All pointers are device pointers; every wrapper only
+// enqueues work on `stream`.  Variants are addressed by their index i in the current chunk (local row g.v0 + i).
+#pragma once
+
+#include "../../include/pgenhip.h"
+#include "kernels.hpp"
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace pgh {
+
+// Where a chunk variant's genotype values come from: its dense dosage row when slot[i] >= 0 (n_out doubles, -9 =
+// missing, pgh_dosage_unpack's layout), otherwise its 2-bit row (code 3 = missing).  sel: output -> raw sample.
+struct GlmX {
+	RowView view;
+	uint32_t v0;
+	const int32_t *slot; // may be null: no dosage rows
+	const double *dos;
+	uint32_t n_out;
+	const uint32_t *sel; // null: all samples
+};
+
+// Per-variant fit state of the logistic / Firth rounds.
+struct GlmState {
+	int32_t status; // kGlmActive .. ; >= kGlmDecided + errcode: decided before any fit
+	int32_t iter;
+	int32_t firth;
+	int32_t pad;
+	double min_delta, delta_max, loglik, loglik_old;
+};
+enum : int32_t { kGlmActive = 0, kGlmConverged = 1, kGlmFailed = 2, kGlmUnfinished = 3, kGlmDecided = 16 };
+
+//! Padded covariate count of the kernels: the smallest instantiated width >= k (k <= 20).
+uint32_t GlmPadCovar(uint32_t k);
+//! Accumulators of one variant in the Newton / Firth rounds: packed upper Hessian, a vector, a scalar, a flag.
+inline uint32_t GlmIrlsEntries(uint32_t kp) {
+	const uint32_t pp = kp + 2;
+	return pp * (pp + 1) / 2 + pp + 2;
+}
+
+// sums[i][kp+4] = {n, sum x, sum x^2, sum x y, sum x z_j (j < kp)} over the samples with a phenotype and a value.
+// y: n_out doubles (NaN = missing); z: n_out x kp doubles, sample-major (zero padded).
+hipError_t LaunchGlmSums(const GlmX &g, uint32_t nv, const double *y, const double *z, uint32_t kp, double *sums,
+                         hipStream_t stream);
+// Packed upper Gram of u = [1, z_1..z_k, y] ((k+2)(k+3)/2 entries).  g == null: over every sample with a phenotype,
+// one row.  Otherwise per chunk variant over its samples with a phenotype and no value (zero rows for variants that
+// have none: sums[i][0] == n_y).
+hipError_t LaunchGlmGram(const GlmX *g, uint32_t nv, const double *sums, uint32_t sums_stride, uint32_t n_y,
+                         uint32_t n_out, const double *y, const double *z, uint32_t kp, uint32_t k, double *out,
+                         hipStream_t stream);
+// The OLS per variant from the sums, the whole-call Gram and the variant's correction Gram.
+hipError_t LaunchGlmLinearSolve(uint32_t nv, const double *sums, uint32_t kp, uint32_t k, const double *gram,
+                                const double *corr, pgh_glm_row *rows, hipStream_t stream);
+// Logistic: TOO_FEW_SAMPLES / CONST_ALLELE from the kp = 0 sums, beta = 0 for the others.
+hipError_t LaunchGlmLogisticInit(uint32_t nv, const double *sums, uint32_t kp, uint32_t k, GlmState *st, double *beta,
+                                 pgh_glm_row *rows, hipStream_t stream);
+// One accumulation pass over the active variants (list == null: chunk variants 0..n-1 with status kGlmActive).
+// mode 0: Newton (Hessian, gradient); 1: Firth, I(beta) + log-likelihood; 2: Firth, second-weight Hessian + U*
+// (reads hinv0: the inverse of mode 1's matrix).
+hipError_t LaunchGlmIrlsAcc(int mode, const GlmX &g, const uint32_t *list, uint32_t n, const double *y, const double *z,
+                            uint32_t kp, const GlmState *st, const double *beta, const double *hinv0, double *acc,
+                            hipStream_t stream);
+hipError_t LaunchGlmNewtonUpdate(uint32_t nv, uint32_t kp, uint32_t k, const double *acc, GlmState *st, double *beta,
+                                 double *hmat, hipStream_t stream);
+hipError_t LaunchGlmFirthStart(const uint32_t *list, uint32_t n, uint32_t kp, GlmState *st, double *beta,
+                               hipStream_t stream);
+hipError_t LaunchGlmFirthUpdate(int half, const uint32_t *list, uint32_t n, uint32_t kp, uint32_t k, const double *acc,
+                                GlmState *st, double *beta, double *hinv0, double *hmat, hipStream_t stream);
+// hmat: kMaxP x kMaxP doubles per variant (the last Newton Hessian; after a Firth fit, its last inverse).
+constexpr uint32_t kGlmMaxP = 22;
+// Rows of the logistic fits from the final state (a plain fit that failed or did not finish and was not refitted
+// with Firth's penalty gives SEPARATION / NO_CONVERGENCE).
+hipError_t LaunchGlmLogisticFinish(uint32_t nv, uint32_t kp, uint32_t k, const GlmState *st,
+                                   const double *beta, const double *hmat, pgh_glm_row *rows, hipStream_t stream);
+
+} // namespace pgh

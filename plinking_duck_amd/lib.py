@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = [
     "pgh_reader_unpack_start", "pgh_reader_unpack_wait", "pgh_get_2bit", "pgh_get_counts", "pgh_get_missingness", "pgh_get_int8", "pgh_get_dosage_f64", "pgh_get_phased",
     "pgh_tally_start", "pgh_tally_request", "pgh_tally_wait", "pgh_tally_counts", "pgh_tally_hwe_lnp",
     "pgh_tally_sample_missing", "pgh_tally_destroy", "pgh_tally_passes_started", "pgh_host_alloc", "pgh_host_free", "pgh_trim_device_cache",
-    "pgh_reader_error", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
+    "pgh_reader_error", "pgh_glm", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
 ]
 
 
@@ -49,6 +49,24 @@ class PghInfo(C.Structure):
 
 # pgh_allreduce_fn(ctx, d_buf, count, stream) -> 0 on success
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p)
+
+
+GLM_LINEAR, GLM_LOGISTIC = 0, 1
+# pgh_glm_row.errcode -> the reference's ERRCODE strings (None = NULL)
+GLM_ERRCODES = [None, "TOO_FEW_SAMPLES", "CONST_ALLELE", "ZERO_VARIANCE", "SINGULAR_MATRIX", "NO_CONVERGENCE",
+                "SEPARATION"]
+GLM_MAX_COVAR = 20
+
+
+class PghGlmRow(C.Structure):
+    _fields_ = [
+        ("beta", C.c_double), ("se", C.c_double), ("stat", C.c_double), ("p", C.c_double), ("a1_freq", C.c_double),
+        ("obs_ct", C.c_uint32), ("errcode", C.c_uint8), ("firth", C.c_uint8), ("pad", C.c_uint8 * 2),
+    ]
+
+
+GLM_ROW_DTYPE = np.dtype([("beta", "<f8"), ("se", "<f8"), ("stat", "<f8"), ("p", "<f8"), ("a1_freq", "<f8"),
+                          ("obs_ct", "<u4"), ("errcode", "u1"), ("firth", "u1"), ("pad", "u1", (2,))])
 
 
 class PghError(IOError):
@@ -161,6 +179,9 @@ def _load():
         "pgh_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(vp), cp]),
         "pgh_host_free": (None, [vp]),
         "pgh_trim_device_cache": (None, []),
+        "pgh_glm": (C.c_int, [vp, vp, u32, u32, vp, u32, vp, C.c_int, C.c_int, vp, cp]),
+        "pgh_glm_p_from_t": (C.c_double, [C.c_double, C.c_double]),
+        "pgh_glm_p_from_z": (C.c_double, [C.c_double]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -192,6 +213,35 @@ def _errbuf():
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def glm_p_from_t(t: float, df: float) -> float:
+    """Two-sided p of Student's t with df degrees of freedom (the reference's TstatToPvalue)."""
+    return _lib.pgh_glm_p_from_t(float(t), float(df))
+
+
+def glm_p_from_z(z: float) -> float:
+    """Two-sided p of a standard normal z (ZstatToPvalue)."""
+    return _lib.pgh_glm_p_from_z(float(z))
+
+
+def glm_model(phenotype, model: str = "auto"):
+    """plink_glm's bind-time model rule (src/plink_glm.cpp:720-760): returns (model, phenotype) with model
+    GLM_LINEAR or GLM_LOGISTIC.  'auto': all non-missing values 0/1 -> logistic; all 1/2 -> logistic, recoded to 0/1;
+    anything else -> linear.  NaN (or None) marks a missing value and is kept."""
+    y = np.array([np.nan if v is None else v for v in phenotype], dtype=np.float64)
+    if model == "linear":
+        return GLM_LINEAR, y
+    if model == "logistic":
+        return GLM_LOGISTIC, y
+    if model != "auto":
+        raise ValueError(f"plink_glm: model must be 'auto', 'linear', or 'logistic', got '{model}'")
+    obs = y[~np.isnan(y)]
+    if np.all((obs == 0.0) | (obs == 1.0)):
+        return GLM_LOGISTIC, y
+    if np.all((obs == 1.0) | (obs == 2.0)):
+        return GLM_LOGISTIC, y - 1.0
+    return GLM_LINEAR, y
 
 
 def version() -> str:
@@ -642,6 +692,36 @@ class Dataset:
         _check(_lib.pgh_dosage_unpack(self._h, subset._h if subset else None, v0, n, _ptr(v) if v is not None else None,
                                       _ptr(out), eb), eb)
         return out
+
+    def glm(self, phenotype, covariates=None, model="linear", firth: bool = True, v_begin: int | None = None,
+            v_end: int | None = None, subset: Subset | None = None) -> dict:
+        """pgh_glm over [v_begin, v_end): per-variant regression of phenotype (one value per output sample, NaN =
+        missing) on the ALT dosage plus covariates (n_covar x n_out, or None).  model: "linear" / "logistic" (or
+        GLM_LINEAR / GLM_LOGISTIC; apply glm_model() first for the reference's 'auto').  Returns numpy arrays beta, se,
+        stat, p, a1_freq (NaN where the reference emits NULL), obs_ct, errcode (strings or None) and firth (bool)."""
+        v0 = self.v_begin if v_begin is None else v_begin
+        v1 = self.v_end if v_end is None else v_end
+        n_out = subset.size if subset else self.n_samples
+        y = np.ascontiguousarray(phenotype, dtype=np.float64)
+        if y.shape != (n_out,):
+            raise ValueError(f"phenotype must hold one value per output sample ({n_out}), got shape {y.shape}")
+        if covariates is None:
+            z = np.zeros((0, n_out), dtype=np.float64)
+        else:
+            z = np.ascontiguousarray(np.atleast_2d(np.asarray(covariates, dtype=np.float64)))
+            if z.shape[1] != n_out:
+                raise ValueError(f"covariates must be n_covar x {n_out}, got shape {z.shape}")
+        m = {"linear": GLM_LINEAR, "logistic": GLM_LOGISTIC}.get(model, model)
+        rows = np.zeros(max(0, v1 - v0), dtype=GLM_ROW_DTYPE)
+        eb = _errbuf()
+        _check(_lib.pgh_glm(self._h, subset._h if subset else None, v0, v1, _ptr(y), z.shape[0],
+                            _ptr(z) if z.size else None, int(m), int(bool(firth)), _ptr(rows), eb), eb)
+        return {
+            "beta": rows["beta"].copy(), "se": rows["se"].copy(), "stat": rows["stat"].copy(), "p": rows["p"].copy(),
+            "a1_freq": rows["a1_freq"].copy(), "obs_ct": rows["obs_ct"].astype(np.int64),
+            "errcode": np.array([GLM_ERRCODES[c] for c in rows["errcode"]], dtype=object),
+            "firth": rows["firth"].astype(bool),
+        }
 
     def unpack_samples(self, vidx, subset: Subset | None = None, missing_code: int = -9) -> np.ndarray:
         """int8[n_out][len(vidx)]: the calls sample-major (read_pfile orient := 'sample')."""
