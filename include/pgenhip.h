@@ -134,6 +134,32 @@ const void *pgh_device_rows(const pgh_dataset *ds);
 /* CleanupPgr + CleanupPgfi (src/plink_freq.cpp:109-115). */
 void pgh_close(pgh_dataset *ds);
 
+/* ---- sparse-resident datasets ---------------------------------------------
+ * The reference's plinking_sample_counts_sparse route (PgrGetDifflistOrGenovec, src/pfile_reader.cpp:3364-3430)
+ * touches only a rare variant's carriers.  pgh_open_sparse keeps each variant of [variant_begin, variant_end) in ONE
+ * of two forms: sparse -- a base code (the row's majority class, any of 0..3) plus one uint32 entry
+ * sample << 2 | code per sample whose call differs from it, ascending -- or dense, the plain 2-bit row in a compact
+ * pool.  max_minor == 0: a row is sparse iff its entries take fewer bytes than its dense row (4 m < pitch), so the
+ * genotype payload never exceeds pgh_open's; max_minor > 0: sparse iff m <= max_minor.  Counts never depend on the
+ * choice.  Hardcalls only (dosage and phase tracks are stepped over; pgh_info still reports them), one device,
+ * fewer than 2^30 samples (PGH_ERR_ARG otherwise).  Served by pgh_get_info, pgh_close, pgh_counts_range(_dev),
+ * pgh_sample_counts(_dev), pgh_copy_rows_to_host and pgh_subset_*; every other entry point that reads rows returns
+ * PGH_ERR_ARG, and pgh_device_rows returns NULL. */
+typedef struct pgh_sparse_info {
+	uint32_t sparse_variant_ct; /* variants held as base + entries                                  */
+	uint32_t dense_variant_ct;  /* variants held as 2-bit rows in the pool                          */
+	uint64_t entry_ct;          /* entries of the sparse variants                                   */
+	uint64_t resident_bytes;    /* device bytes: entries + pool + 12 bytes of index per variant     */
+	uint64_t dense_bytes;       /* what pgh_open holds for the same rows (pitch x variants)          */
+	uint32_t base_hist[4];      /* sparse variants per base code (hom-ref, het, hom-alt, missing)    */
+} pgh_sparse_info;
+int pgh_open_sparse(const char *pgen_path, const char *pgi_path, uint32_t variant_begin, uint32_t variant_end,
+                    uint32_t max_minor, pgh_dataset **out, char *errbuf);
+/* PGH_ERR_ARG for a dataset that is not sparse-resident. */
+int pgh_get_sparse_info(const pgh_dataset *ds, pgh_sparse_info *out);
+/* pgh_open_sparse calls made by this process so far (a diagnostic, like pgh_tally_passes_started). */
+uint64_t pgh_sparse_opens_started(void);
+
 /* ---- shard groups: one process, several devices -------------------------------
  * The reference parallelises inside ONE process and merges per-thread partial sums under a mutex
  * (src/plink_score.cpp:657-664, src/plink_missing.cpp:614-619, src/plink_pca.cpp:940-954).  A shard group is

@@ -17,6 +17,9 @@ extern "C" int pgh_counts_range_dev(const pgh_dataset *ds, const pgh_subset *sub
 	}
 	PGH_ONE_DEVICE(ds);
 	PGH_ENTER(ds);
+	if (ds->sparse) {
+		return pgh_sparse::CountsRangeDev(ds, subset, v_begin, v_end, d_out, static_cast<hipStream_t>(stream), errbuf);
+	}
 	PGH_HIP(pgh::LaunchCounts(ds->View(), v_begin - ds->v_begin, nullptr, v_end - v_begin,
 	                          subset ? subset->d_mask2 : nullptr, subset ? subset->n_out : ds->sample_ct,
 	                          static_cast<uint32_t *>(d_out), static_cast<hipStream_t>(stream)),
@@ -63,6 +66,7 @@ extern "C" int pgh_freq_from_counts_dev(const void *d_counts, uint32_t n, void *
 
 extern "C" int pgh_missing_per_sample_dev(const pgh_dataset *ds, uint32_t v_begin, uint32_t v_end, void *d_out,
                                           void *stream, char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	int rc = CheckRange(ds, v_begin, v_end, errbuf);
 	if (rc != PGH_OK) {
 		return rc;
@@ -82,6 +86,7 @@ extern "C" int pgh_missing_per_sample_dev(const pgh_dataset *ds, uint32_t v_begi
 
 extern "C" int pgh_fused_tally_dev(const pgh_dataset *ds, uint32_t v_begin, uint32_t v_end, void *d_counts,
                                    void *d_missing, void *stream, char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	int rc = CheckRange(ds, v_begin, v_end, errbuf);
 	if (rc != PGH_OK) {
 		return rc;
@@ -105,6 +110,7 @@ extern "C" int pgh_fused_tally_dev(const pgh_dataset *ds, uint32_t v_begin, uint
 
 extern "C" int pgh_missing_per_sample(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin,
                                       uint32_t v_end, uint32_t *out, char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	int rc = CheckRange(ds, v_begin, v_end, errbuf);
 	if (rc == PGH_OK) {
 		rc = CheckSubset(ds, subset, errbuf);
@@ -146,6 +152,10 @@ extern "C" int pgh_sample_counts_dev(const pgh_dataset *ds, uint32_t v_begin, ui
 	PGH_ENTER(ds);
 	const uint32_t padded = (ds->sample_ct + 63) / 64 * 64;
 	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (ds->sparse) {
+		return pgh_sparse::SampleClasses(ds, v_begin - ds->v_begin, nullptr, nullptr, v_end - v_begin,
+		                                 static_cast<uint32_t *>(d_classes), padded, st, true, errbuf);
+	}
 	const size_t scratch_bytes = pgh::ClassCounts3ScratchBytes(ds->record_bytes);
 	void *scratch = nullptr;
 	PGH_HIP(PghThreadScratch(scratch_bytes, st, &scratch), "sample counts scratch");
@@ -192,17 +202,26 @@ extern "C" int pgh_sample_counts(const pgh_dataset *ds, const pgh_subset *subset
 	DevBuf d_cls, d_list, d_scratch;
 	HostSourceFence fence(st); // `local` feeds an asynchronous upload
 	PGH_HIP(d_cls.Alloc(sizeof(uint32_t) * 3ull * padded), "hipMalloc(sample counts)");
-	PGH_HIP(d_scratch.Alloc(pgh::ClassCounts3ScratchBytes(ds->record_bytes)), "hipMalloc(sample counts)");
 	if (vidx && n_var) {
 		PGH_HIP(d_list.Alloc(sizeof(uint32_t) * n_var), "hipMalloc(sample counts)");
 		PGH_HIP(hipMemcpyAsync(d_list.p, local.data(), sizeof(uint32_t) * n_var, hipMemcpyHostToDevice, st),
 		        "sample counts upload");
 	}
 	// het, hom-alt and missing column tallies in one pass; hom-ref is what is left
-	PGH_HIP(pgh::LaunchClassCounts3(ds->View(), vidx ? 0 : variant_begin - ds->v_begin,
-	                                vidx ? d_list.As<uint32_t>() : nullptr, n_var, d_scratch.As<uint8_t>(),
-	                                d_cls.As<uint32_t>(), padded, st),
-	        "sample counts kernel");
+	if (ds->sparse) {
+		rc = pgh_sparse::SampleClasses(ds, vidx ? 0 : variant_begin - ds->v_begin, vidx ? d_list.As<uint32_t>() : nullptr,
+		                               vidx ? local.data() : nullptr, n_var, d_cls.As<uint32_t>(), padded, st, false,
+		                               errbuf);
+		if (rc != PGH_OK) {
+			return rc;
+		}
+	} else {
+		PGH_HIP(d_scratch.Alloc(pgh::ClassCounts3ScratchBytes(ds->record_bytes)), "hipMalloc(sample counts)");
+		PGH_HIP(pgh::LaunchClassCounts3(ds->View(), vidx ? 0 : variant_begin - ds->v_begin,
+		                                vidx ? d_list.As<uint32_t>() : nullptr, n_var, d_scratch.As<uint8_t>(),
+		                                d_cls.As<uint32_t>(), padded, st),
+		        "sample counts kernel");
+	}
 	std::vector<uint32_t> raw(3ull * padded);
 	PGH_HIP(hipMemcpyAsync(raw.data(), d_cls.p, sizeof(uint32_t) * raw.size(), hipMemcpyDeviceToHost, st),
 	        "sample counts copy");
@@ -221,6 +240,7 @@ extern "C" int pgh_sample_counts(const pgh_dataset *ds, const pgh_subset *subset
 extern "C" int pgh_unpack_range_dev(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                                     void *d_out, size_t out_pitch, void *d_validity, int missing_code, void *stream,
                                     char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	int rc = CheckRange(ds, v_begin, v_end, errbuf);
 	if (rc == PGH_OK) {
 		rc = CheckSubset(ds, subset, errbuf);
@@ -262,6 +282,7 @@ extern "C" int pgh_probe_unpack_shape_dev(const void *d_src, size_t n_vec, void 
 
 extern "C" int pgh_unpack_range(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                                 int8_t *out, uint64_t *validity, int missing_code, char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	int rc = CheckRange(ds, v_begin, v_end, errbuf);
 	if (rc == PGH_OK) {
 		rc = CheckSubset(ds, subset, errbuf);
@@ -345,6 +366,7 @@ static int UploadVariantList(const pgh_dataset *ds, uint32_t v_begin, uint32_t n
 
 extern "C" int pgh_dosage_sums_dev(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                                    void *d_sums, void *stream, char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	int rc = CheckRange(ds, v_begin, v_end, errbuf);
 	if (rc == PGH_OK) {
 		rc = CheckSubset(ds, subset, errbuf);
@@ -367,6 +389,7 @@ extern "C" int pgh_dosage_sums_dev(const pgh_dataset *ds, const pgh_subset *subs
 
 extern "C" int pgh_dosage_sums(const pgh_dataset *ds, const pgh_subset *subset, uint32_t variant_begin,
                                uint32_t n_variants, const uint32_t *vidx, uint64_t (*sums)[3], char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	if (!ds || (n_variants && !sums)) {
 		SetErr(errbuf, "null argument");
 		return PGH_ERR_ARG;
@@ -398,6 +421,7 @@ extern "C" int pgh_dosage_sums(const pgh_dataset *ds, const pgh_subset *subset, 
 
 extern "C" int pgh_dosage_unpack_dev(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                                      void *d_out, size_t out_stride, void *stream, char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	int rc = CheckRange(ds, v_begin, v_end, errbuf);
 	if (rc == PGH_OK) {
 		rc = CheckSubset(ds, subset, errbuf);
@@ -421,6 +445,7 @@ extern "C" int pgh_dosage_unpack_dev(const pgh_dataset *ds, const pgh_subset *su
 
 extern "C" int pgh_dosage_unpack(const pgh_dataset *ds, const pgh_subset *subset, uint32_t variant_begin,
                                  uint32_t n_variants, const uint32_t *vidx, double *out, char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	if (!ds || (n_variants && !out)) {
 		SetErr(errbuf, "null argument");
 		return PGH_ERR_ARG;
@@ -497,6 +522,7 @@ static int UnpackSamples(const pgh_dataset *ds, const pgh_subset *subset, uint32
 
 extern "C" int pgh_unpack_samples(const pgh_dataset *ds, const pgh_subset *subset, uint32_t n_variants,
                                   const uint32_t *vidx, int8_t *out, int missing_code, char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	if (ds && ds->IsGroup()) {
 		return n_variants ? pgh_group::UnpackSamples(ds, subset, n_variants, vidx, out, missing_code, errbuf) : PGH_OK;
 	}
@@ -510,6 +536,7 @@ extern "C" int pgh_unpack_samples(const pgh_dataset *ds, const pgh_subset *subse
 
 extern "C" int pgh_dosage_unpack_samples(const pgh_dataset *ds, const pgh_subset *subset, uint32_t n_variants,
                                          const uint32_t *vidx, double *out, char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	if (ds && ds->IsGroup()) {
 		return n_variants ? pgh_group::DosageUnpackSamples(ds, subset, n_variants, vidx, out, errbuf) : PGH_OK;
 	}
@@ -901,6 +928,7 @@ static int ScorePlanCreate(const pgh_dataset *ds, const pgh_subset *subset, uint
 extern "C" int pgh_score_plan_create(const pgh_dataset *ds, const pgh_subset *subset, uint32_t n_scored,
                                      const uint32_t *vidx, const double *weights, const uint8_t *flip, uint32_t n_cols,
                                      int mode, pgh_score_plan **out, char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	return ScorePlanCreate(ds, subset, n_scored, vidx, weights, flip, n_cols, mode, nullptr, true, out, errbuf);
 }
 
@@ -1009,6 +1037,7 @@ extern "C" int pgh_score_run_dev(const pgh_score_plan *plan, void *d_score_sum, 
 int PghScoreDevCounts(const pgh_dataset *ds, const pgh_subset *subset, uint32_t n_scored, const uint32_t *vidx,
                       const double *weights, const uint8_t *flip, uint32_t n_cols, int mode, const uint32_t (*counts)[4],
                       void *d_score_sum, void *d_dosage_sum, void *d_allele_ct, void *stream, char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	PGH_ONE_DEVICE(ds);
 	PGH_ENTER(ds);
 	pgh_score_plan *plan = nullptr;
@@ -1030,6 +1059,7 @@ int PghScoreDevCounts(const pgh_dataset *ds, const pgh_subset *subset, uint32_t 
 extern "C" int pgh_score_dev(const pgh_dataset *ds, const pgh_subset *subset, uint32_t n_scored, const uint32_t *vidx,
                              const double *weights, const uint8_t *flip, uint32_t n_cols, int mode, void *d_score_sum,
                              void *d_dosage_sum, void *d_allele_ct, void *stream, char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	return PghScoreDevCounts(ds, subset, n_scored, vidx, weights, flip, n_cols, mode, nullptr, d_score_sum, d_dosage_sum,
 	                         d_allele_ct, stream, errbuf);
 }
@@ -1037,6 +1067,7 @@ extern "C" int pgh_score_dev(const pgh_dataset *ds, const pgh_subset *subset, ui
 extern "C" int pgh_score(const pgh_dataset *ds, const pgh_subset *subset, uint32_t n_scored, const uint32_t *vidx,
                          const double *weights, const uint8_t *flip, uint32_t n_cols, int mode, double *score_sum,
                          double *dosage_sum, uint32_t *allele_ct, char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	return pgh_score_counts(ds, subset, n_scored, vidx, weights, flip, n_cols, mode, nullptr, score_sum, dosage_sum,
 	                        allele_ct, errbuf);
 }
@@ -1045,6 +1076,7 @@ extern "C" int pgh_score_counts(const pgh_dataset *ds, const pgh_subset *subset,
                                 const double *weights, const uint8_t *flip, uint32_t n_cols, int mode,
                                 const uint32_t (*counts)[4], double *score_sum, double *dosage_sum, uint32_t *allele_ct,
                                 char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	if (!ds) {
 		SetErr(errbuf, "null dataset");
 		return PGH_ERR_ARG;
@@ -1118,6 +1150,7 @@ extern "C" int pgh_score_counts(const pgh_dataset *ds, const pgh_subset *subset,
 extern "C" int pgh_pca(const pgh_dataset *ds, const pgh_subset *subset, uint32_t n_var, const uint32_t *vidx,
                        const double *center, const double *inv_stdev, uint32_t n_pcs, const double *g1_init,
                        double *eigenvalues, double *eigenvectors, char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	if (ds && ds->IsGroup()) {
 		return pgh_group::Pca(ds, subset, n_var, vidx, center, inv_stdev, n_pcs, g1_init, eigenvalues, eigenvectors,
 		                      errbuf);
@@ -1659,6 +1692,7 @@ extern "C" int pgh_pca_sharded(const pgh_dataset *ds, const pgh_subset *subset, 
                                const double *center, const double *inv_stdev, uint64_t n_var_total, uint32_t n_pcs,
                                const double *g1_init, pgh_allreduce_fn allreduce, void *allreduce_ctx,
                                double *eigenvalues, double *eigenvectors, char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	if (!ds || !g1_init || !eigenvalues || !eigenvectors || n_pcs == 0 ||
 	    (n_var && (!vidx || !center || !inv_stdev))) {
 		SetErr(errbuf, "null or empty argument");
@@ -1805,6 +1839,7 @@ extern "C" int pgh_ld_pairs_status(char *errbuf) {
 extern "C" int pgh_ld_pairs_dev(const pgh_dataset *ds, const pgh_subset *subset, uint32_t n_pairs,
                                 const uint32_t *vidx_a, const uint32_t *vidx_b, void *d_sums, void *stream,
                                 char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	if (!ds || (n_pairs && (!vidx_a || !vidx_b || !d_sums))) {
 		SetErr(errbuf, "null argument");
 		return PGH_ERR_ARG;
@@ -1889,6 +1924,7 @@ extern "C" int pgh_ld_pairs_dev(const pgh_dataset *ds, const pgh_subset *subset,
 
 extern "C" int pgh_ld_pairs(const pgh_dataset *ds, const pgh_subset *subset, uint32_t n_pairs, const uint32_t *vidx_a,
                             const uint32_t *vidx_b, uint32_t (*sums)[6], char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	if (n_pairs && !sums) {
 		SetErr(errbuf, "null argument");
 		return PGH_ERR_ARG;

@@ -659,6 +659,11 @@ static int AppendPhaseTracksHost(pgh_dataset *ds, const pgh::RecordFile &file, c
 
 extern "C" int pgh_open(const char *pgen_path, const char *pgi_path, uint32_t variant_begin, uint32_t variant_end,
                         pgh_dataset **out, char *errbuf) {
+	return PghOpenRows(pgen_path, pgi_path, variant_begin, variant_end, false, out, errbuf);
+}
+
+int PghOpenRows(const char *pgen_path, const char *pgi_path, uint32_t variant_begin, uint32_t variant_end,
+                bool hardcalls_only, pgh_dataset **out, char *errbuf) {
 	if (!pgen_path || !out) {
 		SetErr(errbuf, "null argument");
 		return PGH_ERR_ARG;
@@ -700,10 +705,10 @@ extern "C" int pgh_open(const char *pgen_path, const char *pgi_path, uint32_t va
 	int rc = AllocRows(ds.get(), errbuf);
 	lap("rows allocated");
 	DosageStaging dosage;
-	if (rc == PGH_OK && ix.has_dosage) {
+	if (rc == PGH_OK && ix.has_dosage && !hardcalls_only) {
 		rc = PrepareDosage(ds.get(), dosage, errbuf);
 	}
-	if (rc == PGH_OK && ix.has_phase) {
+	if (rc == PGH_OK && ix.has_phase && !hardcalls_only) {
 		rc = PreparePhase(ds.get(), errbuf);
 	}
 	std::vector<uint32_t> host_phase; // phased variants whose track the host parses
@@ -1164,6 +1169,7 @@ extern "C" int pgh_synth_create(uint32_t variant_begin, uint32_t variant_end, ui
 }
 
 extern "C" int pgh_synth_add_dosage(pgh_dataset *ds, double rate, uint64_t seed, char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	if (!ds || ds->dos_rows || !(rate >= 0.0 && rate <= 1.0)) {
 		SetErr(errbuf, "bad argument (null dataset, tracks already present, or rate outside [0, 1])");
 		return PGH_ERR_ARG;
@@ -1440,6 +1446,9 @@ extern "C" int pgh_copy_rows_to_host(const pgh_dataset *ds, uint32_t v_begin, ui
 	if (ds->IsGroup()) {
 		return pgh_group::CopyRowsToHost(ds, v_begin, v_end, rows, row_stride, errbuf);
 	}
+	if (ds->sparse) {
+		return pgh_sparse::CopyRowsToHost(ds, v_begin, v_end, rows, row_stride, errbuf);
+	}
 	PGH_ENTER(ds);
 	PGH_HIP(hipMemcpy2D(rows, row_stride, ds->d_rows + static_cast<uint64_t>(v_begin - ds->v_begin) * ds->pitch,
 	                    ds->pitch, ds->record_bytes, v_end - v_begin, hipMemcpyDeviceToHost),
@@ -1486,6 +1495,7 @@ extern "C" void pgh_close(pgh_dataset *ds) {
 		return;
 	}
 	PGH_ENTER(ds);
+	pgh_sparse::Free(ds);
 	for (void *p : {static_cast<void *>(ds->d_rows), static_cast<void *>(ds->d_dos_row_of),
 	                static_cast<void *>(ds->d_dos_present), static_cast<void *>(ds->d_dos_rank),
 	                static_cast<void *>(ds->d_dos_val_off), static_cast<void *>(ds->d_dos_values),

@@ -201,6 +201,7 @@ extern "C" double pgh_glm_p_from_z(double z) {
 extern "C" int pgh_glm(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                        const double *phenotype, uint32_t n_covar, const double *covariates, int model, int firth,
                        pgh_glm_row *out, char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	int rc = CheckRange(ds, v_begin, v_end, errbuf);
 	if (rc != PGH_OK) {
 		return rc;

@@ -13,6 +13,7 @@
 #include "ld.hpp"
 #include "linalg.hpp"
 #include "pgen_file.hpp"
+#include "sparse.hpp"
 #include "synth.hpp"
 
 #include <hip/hip_runtime.h>
@@ -78,8 +79,26 @@ struct pgh_dataset {
 	// shards sit on distinct devices; an opaque pointer so that rccl.h stays out of this header)
 	mutable void *group_comms = nullptr;
 	mutable void *group_workers = nullptr; // the group's persistent per-shard worker threads (api_sharded.cpp)
+	// The sparse-resident form (pgh_open_sparse, api_sparse.cpp; layout in sparse.hpp): d_rows stays null, the rows
+	// live as per-row base codes + carrier entries, or in a compact pool of dense rows.  Hardcalls only.
+	bool sparse = false;
+	uint32_t sp_sparse_rows = 0;
+	uint32_t sp_dense_rows = 0;
+	uint64_t sp_entry_ct = 0;
+	uint32_t sp_base_hist[4] = {0, 0, 0, 0};
+	std::vector<uint32_t> sp_dense_before; // host: dense rows before resident row i (rows + 1 values)
+	int32_t *d_sp_row_of = nullptr;
+	uint64_t *d_sp_off = nullptr;
+	uint32_t *d_sp_entries = nullptr;
+	uint8_t *d_sp_pool = nullptr;
 	bool IsGroup() const {
 		return !shards.empty();
+	}
+	pgh::SparseView Sparse() const {
+		return pgh::SparseView {d_sp_row_of, d_sp_off, d_sp_entries, d_sp_pool, pitch, sample_ct, record_bytes};
+	}
+	RowView PoolView() const {
+		return RowView {d_sp_pool, pitch, sample_ct, record_bytes};
 	}
 
 	RowView View() const {
@@ -164,6 +183,33 @@ struct DeviceScope {
 			return PGH_ERR_ARG;                                                                                        \
 		}                                                                                                              \
 	} while (0)
+
+// entry points that read the 2-bit rows need them resident as rows: a sparse-resident dataset is refused
+#define PGH_DENSE_ROWS(ds_)                                                                                            \
+	do {                                                                                                               \
+		if ((ds_) && (ds_)->sparse) {                                                                                  \
+			SetErr(errbuf, "needs a dense-resident dataset (pgh_open)");                                               \
+			return PGH_ERR_ARG;                                                                                        \
+		}                                                                                                              \
+	} while (0)
+
+// the sparse-resident forms of the entry points that serve such a dataset (api_sparse.cpp)
+namespace pgh_sparse {
+int CountsRangeDev(const pgh_dataset *ds, const pgh_subset *ss, uint32_t v_begin, uint32_t v_end, void *d_out,
+                   hipStream_t st, char *errbuf);
+//! het / hom-alt / missing per raw sample into d_classes (uint32[3][out_stride]) over the local rows
+//! (vlist ? vlist[i] : v_first + i); vlist: device copy of the host list h_vlist (both local indices) or null.
+int SampleClasses(const pgh_dataset *ds, uint32_t v_first, const uint32_t *vlist, const uint32_t *h_vlist,
+                  uint32_t n_var, uint32_t *d_classes, uint32_t out_stride, hipStream_t st, bool scratch_from_thread,
+                  char *errbuf);
+int CopyRowsToHost(const pgh_dataset *ds, uint32_t v_begin, uint32_t v_end, uint8_t *rows, size_t row_stride,
+                   char *errbuf);
+void Free(pgh_dataset *ds);
+} // namespace pgh_sparse
+
+// pgh_open's body; hardcalls_only: dosage and phase tracks are stepped over (pgh_open_sparse's windows)
+int PghOpenRows(const char *pgen_path, const char *pgi_path, uint32_t variant_begin, uint32_t variant_end,
+                bool hardcalls_only, pgh_dataset **out, char *errbuf);
 
 // shard-group forms of the host-buffer entry points (api_sharded.cpp)
 namespace pgh_group {

@@ -7,6 +7,7 @@
 // ---------------------------------------------------------------------------
 
 extern "C" int pgh_reader_create(const pgh_dataset *ds, const pgh_subset *subset, pgh_reader **out, char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	if (!ds || !out) {
 		SetErr(errbuf, "null argument");
 		return PGH_ERR_ARG;

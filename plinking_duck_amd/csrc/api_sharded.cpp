@@ -436,6 +436,7 @@ extern "C" int pgh_group_create(pgh_dataset *const *shards, uint32_t n_shards, p
 			SetErr(errbuf, "a shard must be a plain dataset");
 			return PGH_ERR_ARG;
 		}
+		PGH_DENSE_ROWS(s);
 		if (s->sample_ct != shards[0]->sample_ct) {
 			SetErr(errbuf, "shards differ in sample count");
 			return PGH_ERR_ARG;

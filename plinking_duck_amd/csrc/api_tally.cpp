@@ -324,6 +324,7 @@ extern "C" uint64_t pgh_tally_passes_started(void) {
 
 extern "C" int pgh_tally_start(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                                uint32_t products, pgh_tally **out, char *errbuf) {
+	PGH_DENSE_ROWS(ds);
 	if (!out) {
 		SetErr(errbuf, "null argument");
 		return PGH_ERR_ARG;

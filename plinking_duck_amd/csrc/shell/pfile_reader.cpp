@@ -685,8 +685,17 @@ static unique_ptr<GlobalTableFunctionState> PfileInitGlobal(ClientContext &conte
 	}
 	// a row filter needs the tallies even when the struct itself is not projected
 	if (state->need_genotypes || bind_data.genotype_filter.active) {
+		// plinking_sample_counts_sparse: the per-sample tallies of orient := 'sample' with genotypes := 'counts' |
+		// 'stats' come from the file's sparse-resident form (only the carriers of a rare variant are read), or from
+		// the dense route when that form does not fit the HBM budget
+		const bool sparse_route = !bind_data.element_mode && !bind_data.genotype_orient &&
+		                          GetPlinkingSampleCountsSparse(context);
 		for (auto &src : bind_data.sources) {
-			state->datasets.push_back(DeviceDataset::Acquire(src.c.pgen_path, "read_pfile"));
+			shared_ptr<DeviceDataset> sparse;
+			if (sparse_route) {
+				sparse = DeviceDataset::AcquireSparse(src.c.pgen_path, "read_pfile");
+			}
+			state->datasets.push_back(sparse ? sparse : DeviceDataset::Acquire(src.c.pgen_path, "read_pfile"));
 			state->row_windows.push_back(make_uniq<RowWindows>());
 			state->subsets.push_back(nullptr);
 			if (bind_data.sources[0].c.has_sample_subset) {

@@ -1757,6 +1757,14 @@ bool GetPlinkingTallyCache(ClientContext &context) {
 	return true;
 }
 
+bool GetPlinkingSampleCountsSparse(ClientContext &context) {
+	Value val;
+	if (context.TryGetCurrentSetting("plinking_sample_counts_sparse", val) && !val.IsNull()) {
+		return val.GetValue<bool>();
+	}
+	return false;
+}
+
 namespace {
 //! One window of a streamed file, opened (pgh_open of the variant range, the sample subset staged next to it).
 struct OpenedWindow {
@@ -2201,8 +2209,9 @@ struct CacheKey {
 	int64_t mtime_ns;
 	int64_t size;
 	vector<int> devices;
+	bool sparse; // the sparse-resident form (AcquireSparse)
 	bool operator==(const CacheKey &o) const {
-		return path == o.path && mtime_ns == o.mtime_ns && size == o.size && devices == o.devices;
+		return path == o.path && mtime_ns == o.mtime_ns && size == o.size && devices == o.devices && sparse == o.sparse;
 	}
 };
 struct CacheEntry {
@@ -2271,6 +2280,19 @@ static int OpenSynth(const SynthSpec &spec, const vector<int> &devices, pgh_data
 }
 
 shared_ptr<DeviceDataset> DeviceDataset::Acquire(const string &pgen_path, const string &func_name) {
+	return AcquireForm(pgen_path, func_name, false);
+}
+
+shared_ptr<DeviceDataset> DeviceDataset::AcquireSparse(const string &pgen_path, const string &func_name) {
+	SynthSpec synth;
+	if (ParseSynthPath(pgen_path, synth)) {
+		return nullptr;
+	}
+	auto ds = AcquireForm(pgen_path, func_name, true);
+	return ds->handle ? ds : nullptr; // (an entry without a handle records that the sparse form did not fit)
+}
+
+shared_ptr<DeviceDataset> DeviceDataset::AcquireForm(const string &pgen_path, const string &func_name, bool sparse) {
 	struct stat st;
 	std::memset(&st, 0, sizeof st);
 	SynthSpec synth;
@@ -2280,7 +2302,7 @@ shared_ptr<DeviceDataset> DeviceDataset::Acquire(const string &pgen_path, const 
 	}
 	const vector<int> devices = GetPlinkingDevices();
 	CacheKey key {pgen_path, static_cast<int64_t>(st.st_mtim.tv_sec) * 1000000000LL + st.st_mtim.tv_nsec,
-	              static_cast<int64_t>(st.st_size), devices};
+	              static_cast<int64_t>(st.st_size), devices, sparse};
 	// The cache lock is NOT held while a file travels to HBM (seconds for a large one): the first caller leaves an
 	// entry without a dataset behind, binds of the same file wait for it, binds of other files go on.
 	std::unique_lock<std::mutex> lock(g_cache_mutex);
@@ -2330,7 +2352,24 @@ shared_ptr<DeviceDataset> DeviceDataset::Acquire(const string &pgen_path, const 
 	// one resident matrix on the current device, or one contiguous variant shard per listed device behind one
 	// handle: every pgh_* call the table functions make accepts either
 	int rc;
-	if (!is_synth) {
+	uint64_t sparse_bytes = 0;
+	if (sparse) {
+		// one device: the first plinking_devices entry
+		rc = devices.empty() ? PGH_OK : pgh_set_device(devices[0], errbuf);
+		if (rc == PGH_OK) {
+			rc = pgh_open_sparse(pgen_path.c_str(), nullptr, 0, UINT32_MAX, 0, &ds->handle, errbuf);
+		}
+		pgh_sparse_info si;
+		if (rc == PGH_OK && pgh_get_sparse_info(ds->handle, &si) == PGH_OK) {
+			sparse_bytes = si.resident_bytes;
+			if (sparse_bytes > CacheBudgetBytes()) {
+				pgh_close(ds->handle); // does not fit either: the entry remembers that, the caller goes dense
+				ds->handle = nullptr;
+				sparse_bytes = 0;
+			}
+		}
+		ds->sparse = true;
+	} else if (!is_synth) {
 		// a file whose rows exceed the HBM budget is not made resident: its tallies stream (DeviceTally)
 		pgh_info probe;
 		if (pgh_probe(pgen_path.c_str(), nullptr, &probe, errbuf) == PGH_OK) {
@@ -2342,7 +2381,9 @@ shared_ptr<DeviceDataset> DeviceDataset::Acquire(const string &pgen_path, const 
 			}
 		}
 	}
-	if (ds->streamed) {
+	if (sparse) {
+		// opened above
+	} else if (ds->streamed) {
 		rc = PGH_OK;
 	} else if (is_synth) {
 		rc = OpenSynth(synth, devices, &ds->handle, errbuf);
@@ -2367,14 +2408,15 @@ shared_ptr<DeviceDataset> DeviceDataset::Acquire(const string &pgen_path, const 
 		g_cache_opened.notify_all();
 		throw IOException("%s: failed to open '%s': %s", func_name, pgen_path, string(errbuf));
 	}
-	if (!ds->streamed) {
+	if (!ds->streamed && ds->handle) {
 		pgh_get_info(ds->handle, &ds->info);
 	}
 	// what the dataset holds in HBM: the 2-bit rows, and per dosage-bearing variant a presence bit and a 4-byte rank
 	// per 64 samples, 2 bytes per explicit value and up to 4 more once plink_score has built the entry records of
 	// the sparse tracks (phase tracks, two bit rows per phased variant, are not reported by pgh_get_info: not counted)
 	const uint64_t words = (static_cast<uint64_t>(ds->info.raw_sample_ct) + 63) / 64;
-	const uint64_t bytes = ds->streamed ? 0
+	const uint64_t bytes = ds->sparse     ? sparse_bytes
+	                       : ds->streamed ? 0
 	                                    : ds->info.pitch_bytes * (ds->info.variant_end - ds->info.variant_begin) +
 	                                          12ull * words * ds->info.dosage_variant_ct + 6ull * ds->info.dosage_value_ct;
 	if (mine < g_cache.size()) {

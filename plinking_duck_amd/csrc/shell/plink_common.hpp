@@ -288,6 +288,13 @@ public:
 	//! Variants per window of a streamed file: half the HBM budget.
 	uint64_t WindowVariants() const;
 	static shared_ptr<DeviceDataset> Acquire(const string &pgen_path, const string &func_name);
+	//! The sparse-resident form of the file (pgh_open_sparse: hardcall counts only), opened on the first
+	//! plinking_devices entry and cached next to the dense form under a key of its own; its resident bytes count
+	//! against PLINKING_HBM_CACHE_GB.  Null when it does not fit that budget (or for a `synth:` source): the caller
+	//! takes the dense route (Acquire), which gives the same counts.
+	static shared_ptr<DeviceDataset> AcquireSparse(const string &pgen_path, const string &func_name);
+	//! handle is a sparse-resident dataset (AcquireSparse)
+	bool sparse = false;
 
 	//! The tally pass over [begin, end) for this sample mask (nullptr = every sample), started if nobody has one:
 	//! plink_freq, plink_hardy, plink_missing and read_pgen's filters on the same file, subset and range share ONE
@@ -303,6 +310,7 @@ public:
 	shared_ptr<DeviceTally> FindTally(const vector<uint64_t> *sample_include, uint32_t begin, uint32_t end);
 
 private:
+	static shared_ptr<DeviceDataset> AcquireForm(const string &pgen_path, const string &func_name, bool sparse);
 	std::mutex tally_mutex_;
 	vector<shared_ptr<DeviceTally>> tallies_; // most recently used last
 };
@@ -357,6 +365,10 @@ vector<int> GetPlinkingDevices();
 //! The extension option `plinking_tally_cache` (default true; PLINKING_TALLY_CACHE=0 in the environment turns it
 //! off process-wide): whether tally passes are shared across table-function calls on the same file.
 bool GetPlinkingTallyCache(ClientContext &context);
+
+//! The reference's option `plinking_sample_counts_sparse` (default false; src/plinking_duck_extension.cpp:80-86):
+//! read_pfile(orient := 'sample', genotypes := 'counts' | 'stats') tallies a sparse-resident form of the file.
+bool GetPlinkingSampleCountsSparse(ClientContext &context);
 
 //! RAII pgh_subset
 class DeviceSubset {

@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = [
     "pgh_reader_unpack_start", "pgh_reader_unpack_wait", "pgh_get_2bit", "pgh_get_counts", "pgh_get_missingness", "pgh_get_int8", "pgh_get_dosage_f64", "pgh_get_phased",
     "pgh_tally_start", "pgh_tally_request", "pgh_tally_wait", "pgh_tally_counts", "pgh_tally_hwe_lnp",
     "pgh_tally_sample_missing", "pgh_tally_destroy", "pgh_tally_passes_started", "pgh_host_alloc", "pgh_host_free", "pgh_trim_device_cache",
-    "pgh_reader_error", "pgh_glm", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
+    "pgh_reader_error", "pgh_open_sparse", "pgh_get_sparse_info", "pgh_sparse_opens_started", "pgh_glm", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
 ]
 
 
@@ -44,6 +44,13 @@ class PghInfo(C.Structure):
         ("max_record_bytes", C.c_uint32), ("record_bytes", C.c_uint32), ("pitch_bytes", C.c_uint64),
         ("vrtype_hist", C.c_uint32 * 8), ("device", C.c_int32),
         ("dosage_variant_ct", C.c_uint32), ("dosage_value_ct", C.c_uint64),
+    ]
+
+
+class PghSparseInfo(C.Structure):
+    _fields_ = [
+        ("sparse_variant_ct", C.c_uint32), ("dense_variant_ct", C.c_uint32), ("entry_ct", C.c_uint64),
+        ("resident_bytes", C.c_uint64), ("dense_bytes", C.c_uint64), ("base_hist", C.c_uint32 * 4),
     ]
 
 
@@ -176,6 +183,9 @@ def _load():
         "pgh_tally_sample_missing": (C.c_int, [vp, vp, cp]),
         "pgh_tally_destroy": (None, [vp]),
         "pgh_tally_passes_started": (u64, []),
+        "pgh_open_sparse": (C.c_int, [cp, cp, u32, u32, u32, C.POINTER(vp), cp]),
+        "pgh_get_sparse_info": (C.c_int, [vp, C.POINTER(PghSparseInfo)]),
+        "pgh_sparse_opens_started": (u64, []),
         "pgh_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(vp), cp]),
         "pgh_host_free": (None, [vp]),
         "pgh_trim_device_cache": (None, []),
@@ -366,6 +376,11 @@ def tally_passes_started() -> int:
     return int(_lib.pgh_tally_passes_started())
 
 
+def sparse_opens_started() -> int:
+    """pgh_open_sparse calls made by this process so far."""
+    return int(_lib.pgh_sparse_opens_started())
+
+
 class TallyPass:
     """pgh_tally: one asynchronous walk of [v_begin, v_end) whose products land in pinned host memory."""
 
@@ -456,12 +471,27 @@ class Dataset:
         _lib.pgh_get_info(self._h, C.byref(self.info))
 
     @classmethod
-    def open(cls, path: str, pgi_path: str | None = None, variant_begin: int = 0, variant_end: int | None = None):
+    def open(cls, path: str, pgi_path: str | None = None, variant_begin: int = 0, variant_end: int | None = None,
+             sparse: bool = False, max_minor: int = 0):
+        """sparse=True: the sparse-resident form (pgh_open_sparse; hardcall counts only).  max_minor > 0 makes a
+        variant sparse iff at most that many samples differ from its majority call (0: whichever form is smaller)."""
         h = C.c_void_p()
         eb = _errbuf()
-        _check(_lib.pgh_open(path.encode(), pgi_path.encode() if pgi_path else None, variant_begin,
-                             0xFFFFFFFF if variant_end is None else variant_end, C.byref(h), eb), eb)
+        pgi = pgi_path.encode() if pgi_path else None
+        v_end = 0xFFFFFFFF if variant_end is None else variant_end
+        if sparse:
+            _check(_lib.pgh_open_sparse(path.encode(), pgi, variant_begin, v_end, max_minor, C.byref(h), eb), eb)
+        else:
+            _check(_lib.pgh_open(path.encode(), pgi, variant_begin, v_end, C.byref(h), eb), eb)
         return cls(h)
+
+    def sparse_info(self) -> PghSparseInfo:
+        """pgh_get_sparse_info (ValueError for a dataset that is not sparse-resident)."""
+        out = PghSparseInfo()
+        rc = _lib.pgh_get_sparse_info(self._h, C.byref(out))
+        if rc != PGH_OK:
+            raise PghArgError(rc, "not a sparse-resident dataset (Dataset.open(..., sparse=True))")
+        return out
 
     @classmethod
     def open_sharded(cls, path: str, devices, pgi_path: str | None = None, variant_begin: int = 0,
