@@ -205,6 +205,19 @@ __device__ inline void SetRowNull(pgh_glm_row &r) {
 	r.pad[0] = r.pad[1] = 0;
 }
 
+// CONST_ALLELE where the reference uses its two-pass variance sum (x - mean)^2 < 1e-20 (the multivariate linear and
+// the logistic fits).  Calls and dosages (value / 16384) lie on the 2^-14 grid in [0, 2], so n, sum x and sum x^2
+// are exact sums (sum x^2 while n < 2^23; for calls always), and a used set that is not constant has a variance sum
+// of at least 2^-28 (1 - 1/n) > 1e-20.  The rule is therefore "every used x is equal", which is n sum x^2 == (sum x)^2
+// (Cauchy-Schwarz: > otherwise).  Both products are compared exactly, each as an fma two-product (hi + lo).  The
+// one-pass sum x^2 - (sum x)^2 / n is not enough: for a constant dosage it can round to a positive number (2.3e-13 for
+// 20,001 samples at 4915 / 16384).
+__device__ inline bool GlmConstant(double n, double sx, double sxx) {
+	const double a = n * sxx, a_lo = fma(n, sxx, -a);
+	const double b = sx * sx, b_lo = fma(sx, sx, -b);
+	return a < b || (a == b && a_lo <= b_lo);
+}
+
 __global__ void GlmLinearSolveKernel(uint32_t nv, const double *__restrict__ sums, uint32_t kp, uint32_t k,
                                      const double *__restrict__ gram, const double *__restrict__ corr,
                                      pgh_glm_row *__restrict__ rows) {
@@ -226,7 +239,8 @@ __global__ void GlmLinearSolveKernel(uint32_t nv, const double *__restrict__ sum
 		return;
 	}
 	r.a1_freq = s[1] / (2.0 * n);
-	if (s[2] - s[1] * s[1] / n < 1e-20) {
+	// with no covariates the reference takes its one-pass closed form, and its test with it
+	if (k ? GlmConstant(n, s[1], s[2]) : s[2] - s[1] * s[1] / n < 1e-20) {
 		r.errcode = PGH_GLM_CONST_ALLELE;
 		rows[v] = r;
 		return;
@@ -311,7 +325,7 @@ __global__ void GlmLogisticInitKernel(uint32_t nv, const double *__restrict__ su
 		g.status = kGlmDecided + PGH_GLM_TOO_FEW_SAMPLES;
 	} else {
 		r.a1_freq = s[1] / (2.0 * n);
-		if (s[2] - s[1] * s[1] / n < 1e-20) {
+		if (GlmConstant(n, s[1], s[2])) {
 			r.errcode = PGH_GLM_CONST_ALLELE;
 			g.status = kGlmDecided + PGH_GLM_CONST_ALLELE;
 		}

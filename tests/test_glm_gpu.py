@@ -1,6 +1,6 @@
 """pgh_glm / Dataset.glm on the device: the reference's plink_glm expectations (test/sql/plink_glm.test and
 plink_glm_pthreshold.test, replayed with the bind steps done here), random fixtures against an FP64 numpy oracle of
-the same rules, dosage tracks, many sample chunks, shard groups and adjacent windows."""
+the same rules (tests/glm_oracle.py), dosage tracks, many sample chunks, shard groups and adjacent windows."""
 
 import math
 
@@ -8,192 +8,9 @@ import numpy as np
 import pytest
 
 from conftest import data_path
-
-scipy_stats = pytest.importorskip("scipy.stats")
+from glm_oracle import NAN, _pheno, _same_rows, check_rows
 
 pytestmark = pytest.mark.gpu
-
-NAN = float("nan")
-
-
-# ---------------------------------------------------------------------------
-# FP64 oracle: ComputeLinearRegression / ComputeLogisticRegression's rules, written with numpy
-# ---------------------------------------------------------------------------
-
-def _chol_ok(a, rel):
-    """Cholesky pivots of a (in order); False when one is not positive or below rel x its diagonal."""
-    a = np.array(a, dtype=np.float64)
-    n = a.shape[0]
-    low = np.zeros_like(a)
-    for j in range(n):
-        d = a[j, j] - low[j, :j] @ low[j, :j]
-        if not d > 0 or d <= rel * abs(a[j, j]):
-            return False
-        low[j, j] = math.sqrt(d)
-        for i in range(j + 1, n):
-            low[i, j] = (a[i, j] - low[i, :j] @ low[j, :j]) / low[j, j]
-    return True
-
-
-def _ref_chol_solve(h, g):
-    """The reference's Newton Cholesky: a negative pivot becomes 1e-6 instead of failing."""
-    p = h.shape[0]
-    low = np.zeros_like(h)
-    for j in range(p):
-        d = h[j, j] - low[j, :j] @ low[j, :j]
-        low[j, j] = math.sqrt(d) if d >= 0 else 1e-6
-        for i in range(j + 1, p):
-            low[i, j] = (h[i, j] - low[i, :j] @ low[j, :j]) / low[j, j]
-    with np.errstate(all="ignore"):
-        w = np.linalg.solve(low, g) if np.all(np.diag(low) != 0) else np.full(p, np.nan)
-        return np.linalg.solve(low.T, w) if np.all(np.isfinite(w)) else np.full(p, np.nan)
-
-
-def _sigmoid(eta):
-    with np.errstate(over="ignore"):
-        return 1.0 / (1.0 + np.exp(-eta))
-
-
-def _newton(X, y):
-    p = X.shape[1]
-    b = np.zeros(p)
-    min_delta = 1e9
-    h = None
-    for it in range(1000):
-        mu = _sigmoid(X @ b)
-        h = (X * (mu * (1 - mu))[:, None]).T @ X
-        d = _ref_chol_solve(h, X.T @ (mu - y))
-        delta = float(np.sum(np.abs(d)))
-        b = b - d
-        min_delta = min(min_delta, delta)
-        if delta != delta:
-            return "failed", b, h
-        if it > 3:
-            if (delta > 20 and delta > 2 * min_delta) or (it > 6 and abs(1 - delta) < 1e-3):
-                return "failed", b, h
-            if it > 13:
-                return ("failed" if np.any(np.abs(b) > 8e3) else "unfinished"), b, h
-        if delta < 1e-4:
-            return ("failed" if np.any(np.abs(b) > 6e4) else "converged"), b, h
-    raise AssertionError("unreachable")
-
-
-def _firth(X, y):
-    p = X.shape[1]
-    b = np.zeros(p)
-    delta_max, ll_old, hinv = 0.0, 0.0, None
-    for it in range(1000):
-        mu = _sigmoid(X @ b)
-        if np.any((mu == 0) | (mu == 1)):
-            return "failed", b, hinv
-        ll = float(np.sum(np.where(y != 0, np.log(mu), np.log1p(-mu))))
-        v = mu * (1 - mu)
-        h0 = (X * v[:, None]).T @ X
-        if not _chol_ok(h0, 1e-13):
-            return "failed", b, hinv
-        ll += 0.5 * np.linalg.slogdet(h0)[1]
-        h0i = np.linalg.inv(h0)
-        hd = v * np.einsum("ij,jk,ik->i", X, h0i, X)
-        ustar = X.T @ ((y - mu) + hd * (0.5 - mu))
-        if it > 0:
-            if delta_max <= 1e-4 and np.max(np.abs(ustar)) < 1e-4 and ll - ll_old < 1e-4:
-                return "converged", b, hinv
-            if it > 25:
-                return "unfinished", b, hinv
-        ll_old = ll
-        hh = (X * ((1 + hd) * v)[:, None]).T @ X
-        if not _chol_ok(hh, 1e-13):
-            return "failed", b, hinv
-        hinv = np.linalg.inv(hh)
-        d = hinv @ ustar
-        delta_max = float(np.max(np.abs(d)))
-        if delta_max > 5:
-            d *= 5 / delta_max
-            delta_max = 5.0
-        b = b + d
-    raise AssertionError("unreachable")
-
-
-def oracle_row(x, y, Z, model, firth=True):
-    """x: values with -9 = missing; y: NaN = missing; Z: k x n covariates."""
-    k = Z.shape[0]
-    p = k + 2
-    use = (x != -9.0) & ~np.isnan(y)
-    n = int(use.sum())
-    row = dict(beta=NAN, se=NAN, stat=NAN, p=NAN, a1_freq=NAN, obs_ct=n, errcode=None, firth=False)
-    if n < p + 1:
-        row["errcode"] = "TOO_FEW_SAMPLES"
-        return row
-    xs, ys = x[use], y[use]
-    row["a1_freq"] = xs.sum() / (2.0 * n)
-    if np.sum(xs * xs) - xs.sum() ** 2 / n < 1e-20:
-        row["errcode"] = "CONST_ALLELE"
-        return row
-    if model == "linear":
-        X = np.column_stack([np.ones(n), Z[:, use].T, xs])  # the genotype last
-        xtx = X.T @ X
-        if not _chol_ok(xtx, 1e-10 if k else 0.0):
-            row["errcode"] = "SINGULAR_MATRIX"
-            return row
-        coef = np.linalg.solve(xtx, X.T @ ys)
-        rss = max(0.0, float(np.sum((ys - X @ coef) ** 2)))
-        df = n - p
-        se2 = rss / df * np.linalg.inv(xtx)[-1, -1]
-        row["beta"] = coef[-1]
-        if se2 < 1e-30:
-            row["errcode"] = "ZERO_VARIANCE"
-            return row
-        row["se"] = math.sqrt(se2)
-        row["stat"] = row["beta"] / row["se"]
-        row["p"] = 2 * scipy_stats.t.sf(abs(row["stat"]), df)
-        return row
-    X = np.column_stack([np.ones(n), xs, Z[:, use].T])
-    status, b, h = _newton(X, ys)
-    if status == "converged":
-        if not _chol_ok(h, 1e-13):
-            row["errcode"] = "SINGULAR_MATRIX"
-            return row
-        se2 = np.linalg.inv(h)[1, 1]
-    elif firth:
-        status, b, hinv = _firth(X, ys)
-        if status == "failed":
-            row["errcode"] = "NO_CONVERGENCE"
-            return row
-        row["firth"] = True
-        se2 = hinv[1, 1]
-    else:
-        row["errcode"] = "SEPARATION" if status == "failed" else "NO_CONVERGENCE"
-        return row
-    row["beta"] = b[1]
-    if se2 < 1e-30:
-        row["errcode"] = "ZERO_VARIANCE"
-        return row
-    row["se"] = math.sqrt(se2)
-    row["stat"] = row["beta"] / row["se"]
-    row["p"] = 2 * scipy_stats.norm.sf(abs(row["stat"]))
-    return row
-
-
-def check_rows(got, xs, y, Z, model, firth=True, rel=1e-9, idx=None):
-    """got: Dataset.glm output; xs: one value row per variant."""
-    fitted = 0
-    for i in (range(len(xs)) if idx is None else idx):
-        exp = oracle_row(xs[i], y, Z, model, firth)
-        ctx = (i, exp, {k: got[k][i] for k in got})
-        assert got["errcode"][i] == exp["errcode"], ctx
-        assert got["obs_ct"][i] == exp["obs_ct"], ctx
-        assert bool(got["firth"][i]) == exp["firth"], ctx
-        for key in ("beta", "se", "stat", "p", "a1_freq"):
-            g, e = got[key][i], exp[key]
-            if math.isnan(e):
-                assert math.isnan(g), (key, ctx)
-            else:
-                # relative to the value, or for an estimate close to zero to its standard error (the scale of beta)
-                scale = abs(e) + (exp["se"] if key == "beta" else 1.0 if key == "stat" else 0.0)
-                assert abs(g - e) <= rel * scale + 1e-300, (key, ctx)
-        fitted += exp["errcode"] is None
-    return fitted
-
 
 # ---------------------------------------------------------------------------
 # the reference's expectations
@@ -359,14 +176,6 @@ def rand_fixture(gpu_lib, tmp_path_factory):
     return ds, x, rows, rng
 
 
-def _pheno(rng, n, kind, Z):
-    y = 0.3 * (Z.sum(axis=0) if Z.shape[0] else 0) + rng.normal(size=n)
-    if kind == "logistic":
-        y = (rng.random(n) < 1 / (1 + np.exp(-0.2 * y))).astype(np.float64)
-    y[rng.random(n) < 0.03] = NAN
-    return y
-
-
 @pytest.mark.parametrize("k", [0, 3, 20])
 def test_random_linear(gpu_lib, rand_fixture, k):
     ds, x, _, rng = rand_fixture
@@ -454,13 +263,6 @@ def test_many_sample_chunks(gpu_lib):
     check_rows(ds.glm(y, Z, model="linear"), x, y, Z, "linear", rel=1e-9)
     yb = _pheno(rng, n, "logistic", Z)
     check_rows(ds.glm(yb, Z, model="logistic"), x, yb, Z, "logistic", rel=1e-6)
-
-
-def _same_rows(a, b):
-    for key in ("beta", "se", "stat", "p", "a1_freq"):
-        assert np.array_equal(a[key], b[key], equal_nan=True), key
-    for key in ("obs_ct", "errcode", "firth"):
-        assert list(a[key]) == list(b[key]), key
 
 
 @pytest.mark.parametrize("model", ["linear", "logistic"])
