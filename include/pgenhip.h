@@ -517,6 +517,16 @@ typedef struct pgh_glm_row {
 } pgh_glm_row;
 int pgh_glm(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end, const double *phenotype,
             uint32_t n_covar, const double *covariates, int model, int firth, pgh_glm_row *out, char *errbuf);
+/* pgh_glm for n_pheno phenotypes at once.  phenotypes: n_pheno x n_out doubles, phenotype-major, NaN = missing.
+ * out: (v_end - v_begin) x n_pheno rows, variant-major: out[(v - v_begin) * n_pheno + p] is phenotype p's row
+ * for variant v.  Every other argument means what it means for pgh_glm; n_pheno == 0 is PGH_ERR_ARG.
+ * Each row is what pgh_glm returns for that phenotype alone: logistic and Firth rows bit for bit; linear rows with
+ * the same errcode, obs_ct and a1_freq, and estimates that agree to rounding (the phenotypes of one missing-value
+ * pattern share one walk of the rows, and their sums are accumulated in another order).  A row does not depend on
+ * the other phenotypes of the call or on its place among them. */
+int pgh_glm_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                  uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
+                  int model, int firth, pgh_glm_row *out, char *errbuf);
 /* two-sided p of Student's t with df degrees of freedom (the reference's TstatToPvalue) */
 double pgh_glm_p_from_t(double t, double df);
 /* two-sided p of a standard normal z (ZstatToPvalue) */

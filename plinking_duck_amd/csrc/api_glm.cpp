@@ -1,7 +1,10 @@
-// api_glm.cpp -- pgh_glm: plink_glm's per-variant linear / logistic / Firth regressions (glm.hip) behind the C ABI.
+// api_glm.cpp -- pgh_glm: plink_glm's per-variant linear / logistic / Firth regressions (glm.hip) behind the C ABI;
+// pgh_glm_multi: the same for many phenotypes in one call.
 #include "api_internal.hpp"
 #include "glm.hpp"
 #include "glm_math.hpp"
+
+#include <unordered_map>
 
 namespace {
 
@@ -188,6 +191,269 @@ int GlmOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, ui
 	return PGH_OK;
 }
 
+// pgh_glm_multi, linear: variants per chunk, and the bound of a chunk's scratch (sums, corrections and rows of a
+// phenotype block grow with both; dense dosage rows keep kGlmDosageBytes).
+constexpr uint32_t kGlmMultiChunk = 65536;
+constexpr uint64_t kGlmMultiChunkBytes = 1ull << 30;
+
+// The phenotypes of `phenotypes` (n_pheno x n_out) grouped by missing-value pattern, each group in phenotype order and
+// the groups in the order of their first phenotype.
+std::vector<std::vector<uint32_t>> GlmPatternGroups(uint32_t n_pheno, const double *phenotypes, uint32_t n_out) {
+	const size_t words = (static_cast<size_t>(n_out) + 63) / 64;
+	std::vector<uint64_t> masks(words * n_pheno, 0);
+	std::unordered_map<uint64_t, std::vector<uint32_t>> by_hash; // hash -> group ids
+	std::vector<std::vector<uint32_t>> groups;
+	for (uint32_t p = 0; p < n_pheno; p++) {
+		uint64_t *m = masks.data() + words * p;
+		const double *y = phenotypes + static_cast<size_t>(p) * n_out;
+		for (uint32_t i = 0; i < n_out; i++) {
+			m[i >> 6] |= static_cast<uint64_t>(std::isnan(y[i])) << (i & 63);
+		}
+		uint64_t h = 1469598103934665603ull; // FNV-1a over the words
+		for (size_t w = 0; w < words; w++) {
+			h = (h ^ m[w]) * 1099511628211ull;
+		}
+		std::vector<uint32_t> &cands = by_hash[h];
+		bool placed = false;
+		for (uint32_t gi : cands) {
+			if (std::equal(m, m + words, masks.data() + words * groups[gi][0])) {
+				groups[gi].push_back(p);
+				placed = true;
+				break;
+			}
+		}
+		if (!placed) {
+			cands.push_back(static_cast<uint32_t>(groups.size()));
+			groups.push_back({p});
+		}
+	}
+	return groups;
+}
+
+// Linear fits of the phenotypes `idx` (one missing-value pattern) over the variants [v_begin, v_end) of one dataset:
+// out[(v - v_begin) * n_pheno + idx[j]].  The covariates are centred on the pattern's samples and each phenotype on
+// its own mean, as GlmOne does.
+int GlmMultiLinear(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end, uint32_t n_pheno,
+                   const double *phenotypes, const std::vector<uint32_t> &idx, uint32_t k, const double *covariates,
+                   pgh_glm_row *out, char *errbuf) {
+	PGH_ENTER(ds);
+	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct;
+	const uint32_t nv_all = v_end - v_begin;
+	const uint32_t kp = pgh::GlmPadCovar(k);
+	const uint32_t np = static_cast<uint32_t>(idx.size());
+	hipStream_t st = PghThreadStream();
+
+	const double *ypat = phenotypes + static_cast<size_t>(idx[0]) * n_out; // NaN exactly at the pattern
+	std::vector<double> hz(static_cast<size_t>(n_out) * kp, 0.0);
+	for (uint32_t j = 0; j < k; j++) {
+		for (uint32_t i = 0; i < n_out; i++) {
+			hz[static_cast<size_t>(i) * kp + j] = covariates[static_cast<size_t>(j) * n_out + i];
+		}
+	}
+	uint32_t n_y = 0;
+	for (uint32_t i = 0; i < n_out; i++) {
+		n_y += std::isnan(ypat[i]) ? 0u : 1u;
+	}
+	if (n_y) {
+		for (uint32_t j = 0; j < k; j++) {
+			double mz = 0.0;
+			for (uint32_t i = 0; i < n_out; i++) {
+				mz += std::isnan(ypat[i]) ? 0.0 : hz[static_cast<size_t>(i) * kp + j];
+			}
+			mz /= n_y;
+			for (uint32_t i = 0; i < n_out; i++) {
+				hz[static_cast<size_t>(i) * kp + j] -= mz;
+			}
+		}
+	}
+	std::vector<int32_t> slot_all(nv_all, -1);
+	for (uint32_t v = v_begin; v < v_end && ds->dos_rows; v++) {
+		if (ds->dos_row_of[v - ds->v_begin] >= 0) {
+			slot_all[v - v_begin] = 0;
+		}
+	}
+	const bool any_dos = std::any_of(slot_all.begin(), slot_all.end(), [](int32_t s) { return s >= 0; });
+
+	const uint32_t pb_max = std::min(pgh::kGlmMultiPb, np);
+	const uint32_t ns = kp + 4, q = k + 2, ne_gram = q * (q + 1) / 2, nes = (k + 1) * (k + 2) / 2;
+	const uint64_t per_variant = 8ull * (ns + nes) + static_cast<uint64_t>(pb_max) * (8 + 8 * q + sizeof(pgh_glm_row)) + 8;
+	uint32_t chunk = std::min(kGlmMultiChunk, std::max(1u, nv_all));
+	chunk = static_cast<uint32_t>(std::min<uint64_t>(chunk, std::max<uint64_t>(1, kGlmMultiChunkBytes / per_variant)));
+	if (any_dos) {
+		chunk = static_cast<uint32_t>(std::min<uint64_t>(chunk, std::max<uint64_t>(1, kGlmDosageBytes / (8ull * std::max(1u, n_out)))));
+	}
+	auto up = [](uint64_t b) { return (b + 255) / 256 * 256; };
+	const uint64_t b_pat = up(8ull * n_out), b_z = up(8ull * n_out * kp + 8), b_yb = up(8ull * n_out * pb_max);
+	const uint64_t b_gram = up(8ull * ne_gram), b_whole = up(8ull * pb_max * q), b_sums = up(8ull * chunk * ns);
+	const uint64_t b_sxy = up(8ull * chunk * pb_max), b_cs = up(8ull * chunk * nes), b_cp = up(8ull * chunk * pb_max * q);
+	const uint64_t b_rows = up(sizeof(pgh_glm_row) * chunk * pb_max), b_slot = up(4ull * chunk), b_list = up(4ull * chunk);
+	const uint64_t b_dos = any_dos ? up(8ull * chunk * n_out) : 0;
+	const uint64_t total = b_pat + b_z + b_yb + b_gram + b_whole + b_sums + b_sxy + b_cs + b_cp + b_rows + b_slot + b_list +
+	                       b_dos;
+	void *scratch = nullptr;
+	PGH_HIP(PghThreadScratch(total, st, &scratch), "glm_multi scratch");
+	char *cur = static_cast<char *>(scratch);
+	auto take = [&](uint64_t b) {
+		char *p = cur;
+		cur += b;
+		return p;
+	};
+	double *d_pat = reinterpret_cast<double *>(take(b_pat));
+	double *d_z = reinterpret_cast<double *>(take(b_z));
+	double *d_yb = reinterpret_cast<double *>(take(b_yb));
+	double *d_gram = reinterpret_cast<double *>(take(b_gram));
+	double *d_whole = reinterpret_cast<double *>(take(b_whole));
+	double *d_sums = reinterpret_cast<double *>(take(b_sums));
+	double *d_sxy = reinterpret_cast<double *>(take(b_sxy));
+	double *d_cs = reinterpret_cast<double *>(take(b_cs));
+	double *d_cp = reinterpret_cast<double *>(take(b_cp));
+	pgh_glm_row *d_rows = reinterpret_cast<pgh_glm_row *>(take(b_rows));
+	int32_t *d_slot = reinterpret_cast<int32_t *>(take(b_slot));
+	uint32_t *d_list = reinterpret_cast<uint32_t *>(take(b_list));
+	double *d_dos = reinterpret_cast<double *>(take(b_dos));
+
+	std::vector<double> hyb(static_cast<size_t>(n_out) * pb_max);
+	std::vector<pgh_glm_row> hrows(static_cast<size_t>(chunk) * pb_max);
+	std::vector<int32_t> slot(chunk);
+	std::vector<uint32_t> vlist(chunk);
+	HostSourceFence fence(st); // hz, hyb, slot, vlist feed asynchronous uploads
+	PGH_HIP(hipMemcpyAsync(d_pat, ypat, 8ull * n_out, hipMemcpyHostToDevice, st), "glm_multi pattern upload");
+	if (kp) {
+		PGH_HIP(hipMemcpyAsync(d_z, hz.data(), 8ull * n_out * kp, hipMemcpyHostToDevice, st), "glm_multi covariate upload");
+	}
+	PGH_HIP(pgh::LaunchGlmGram(nullptr, 1, nullptr, 0, n_y, n_out, d_pat, d_z, kp, k, d_gram, st), "glm_multi gram kernel");
+	for (uint32_t b0 = 0; b0 < np; b0 += pb_max) {
+		const uint32_t pb = std::min(pb_max, np - b0);
+		// every upload of the previous block has completed: each chunk below ends with a stream synchronisation
+		for (uint32_t j = 0; j < pb; j++) {
+			const double *y = phenotypes + static_cast<size_t>(idx[b0 + j]) * n_out;
+			double my = 0.0;
+			for (uint32_t i = 0; i < n_out; i++) {
+				my += std::isnan(y[i]) ? 0.0 : y[i];
+			}
+			my /= n_y ? n_y : 1u;
+			double *dst = hyb.data() + static_cast<size_t>(j) * n_out;
+			for (uint32_t i = 0; i < n_out; i++) {
+				dst[i] = std::isnan(y[i]) ? 0.0 : y[i] - my;
+			}
+		}
+		PGH_HIP(hipMemcpyAsync(d_yb, hyb.data(), 8ull * n_out * pb, hipMemcpyHostToDevice, st), "glm_multi phenotype upload");
+		PGH_HIP(pgh::LaunchGlmMultiWhole(n_out, d_yb, pb, d_z, kp, k, d_whole, st), "glm_multi whole-call kernel");
+		for (uint32_t c0 = 0; c0 < nv_all; c0 += chunk) {
+			const uint32_t nv = std::min(chunk, nv_all - c0);
+			pgh::GlmX g {};
+			g.view = ds->View();
+			g.v0 = v_begin + c0 - ds->v_begin;
+			g.n_out = n_out;
+			g.sel = subset ? subset->d_sel : nullptr;
+			uint32_t n_dos = 0;
+			if (any_dos) {
+				for (uint32_t i = 0; i < nv; i++) {
+					slot[i] = slot_all[c0 + i] >= 0 ? static_cast<int32_t>(n_dos) : -1;
+					if (slot[i] >= 0) {
+						vlist[n_dos++] = g.v0 + i;
+					}
+				}
+			}
+			if (n_dos) {
+				PGH_HIP(hipMemcpyAsync(d_slot, slot.data(), 4ull * nv, hipMemcpyHostToDevice, st), "glm_multi slot upload");
+				PGH_HIP(hipMemcpyAsync(d_list, vlist.data(), 4ull * n_dos, hipMemcpyHostToDevice, st),
+				        "glm_multi dosage list upload");
+				PGH_HIP(pgh::LaunchDosageUnpack(ds->View(), ds->Dosage(), 0, d_list, n_dos, g.sel, n_out, d_dos, n_out, st),
+				        "glm_multi dosage unpack");
+				g.slot = d_slot;
+				g.dos = d_dos;
+			}
+			PGH_HIP(pgh::LaunchGlmSums(g, nv, d_pat, d_z, kp, d_sums, st), "glm_multi sums kernel");
+			PGH_HIP(pgh::LaunchGlmMultiXy(g, nv, d_yb, pb, d_sxy, st), "glm_multi genotype x phenotype kernel");
+			PGH_HIP(pgh::LaunchGlmMultiCorr(g, nv, d_sums, n_y, d_pat, d_yb, pb, d_z, kp, k, d_cs, d_cp, st),
+			        "glm_multi correction kernel");
+			PGH_HIP(pgh::LaunchGlmMultiSolve(nv, pb, d_sums, kp, k, d_sxy, d_gram, d_whole, d_cs, d_cp, d_rows, st),
+			        "glm_multi solve kernel");
+			PGH_HIP(hipMemcpyAsync(hrows.data(), d_rows, sizeof(pgh_glm_row) * nv * pb, hipMemcpyDeviceToHost, st),
+			        "glm_multi rows copy");
+			PGH_HIP(hipStreamSynchronize(st), "glm_multi sync");
+			for (uint32_t i = 0; i < nv; i++) {
+				for (uint32_t j = 0; j < pb; j++) {
+					out[static_cast<size_t>(c0 + i) * n_pheno + idx[b0 + j]] = hrows[static_cast<size_t>(i) * pb + j];
+				}
+			}
+		}
+	}
+	return PGH_OK;
+}
+
+// pgh_glm_multi on one dataset (not a group): linear fits by missing-value pattern, logistic fits phenotype by
+// phenotype through GlmOne (so their rows are pgh_glm's bit for bit).
+int GlmMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end, uint32_t n_pheno,
+                const double *phenotypes, uint32_t k, const double *covariates, int model, int firth, pgh_glm_row *out,
+                char *errbuf) {
+	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct;
+	const uint32_t nv = v_end - v_begin;
+	if (model == PGH_GLM_LOGISTIC) {
+		std::vector<pgh_glm_row> rows(nv);
+		for (uint32_t p = 0; p < n_pheno; p++) {
+			const int rc = GlmOne(ds, subset, v_begin, v_end, phenotypes + static_cast<size_t>(p) * n_out, k, covariates,
+			                      model, firth, rows.data(), errbuf);
+			if (rc != PGH_OK) {
+				return rc;
+			}
+			for (uint32_t v = 0; v < nv; v++) {
+				out[static_cast<size_t>(v) * n_pheno + p] = rows[v];
+			}
+		}
+		return PGH_OK;
+	}
+	for (const std::vector<uint32_t> &idx : GlmPatternGroups(n_pheno, phenotypes, n_out)) {
+		const int rc = GlmMultiLinear(ds, subset, v_begin, v_end, n_pheno, phenotypes, idx, k, covariates, out, errbuf);
+		if (rc != PGH_OK) {
+			return rc;
+		}
+	}
+	return PGH_OK;
+}
+
+// The argument checks of pgh_glm (n_pheno = 1) and pgh_glm_multi.
+int GlmCheckArgs(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end, uint32_t n_pheno,
+                 const double *phenotypes, uint32_t n_covar, const double *covariates, int model, const pgh_glm_row *out,
+                 char *errbuf) {
+	PGH_DENSE_ROWS(ds);
+	int rc = CheckRange(ds, v_begin, v_end, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
+	}
+	if (model != PGH_GLM_LINEAR && model != PGH_GLM_LOGISTIC) {
+		SetErr(errbuf, "model must be PGH_GLM_LINEAR or PGH_GLM_LOGISTIC");
+		return PGH_ERR_ARG;
+	}
+	if (n_pheno == 0) {
+		SetErr(errbuf, "at least one phenotype is needed");
+		return PGH_ERR_ARG;
+	}
+	if (n_covar > PGH_GLM_MAX_COVAR) {
+		SetErr(errbuf, "at most " + std::to_string(PGH_GLM_MAX_COVAR) + " covariates are supported, got " +
+		                   std::to_string(n_covar));
+		return PGH_ERR_ARG;
+	}
+	if (subset && subset->ds != ds) {
+		SetErr(errbuf, "sample subset belongs to a different dataset");
+		return PGH_ERR_ARG;
+	}
+	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct;
+	if ((n_out && !phenotypes) || (n_covar && n_out && !covariates) || (v_end > v_begin && !out)) {
+		SetErr(errbuf, "null argument");
+		return PGH_ERR_ARG;
+	}
+	for (uint64_t i = 0; i < static_cast<uint64_t>(n_covar) * n_out; i++) {
+		if (!std::isfinite(covariates[i])) {
+			SetErr(errbuf, "covariate " + std::to_string(i / n_out) + " is not finite at sample " +
+			                   std::to_string(i % n_out));
+			return PGH_ERR_ARG;
+		}
+	}
+	return PGH_OK;
+}
+
 } // namespace
 
 extern "C" double pgh_glm_p_from_t(double t, double df) {
@@ -201,35 +467,9 @@ extern "C" double pgh_glm_p_from_z(double z) {
 extern "C" int pgh_glm(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                        const double *phenotype, uint32_t n_covar, const double *covariates, int model, int firth,
                        pgh_glm_row *out, char *errbuf) {
-	PGH_DENSE_ROWS(ds);
-	int rc = CheckRange(ds, v_begin, v_end, errbuf);
+	int rc = GlmCheckArgs(ds, subset, v_begin, v_end, 1, phenotype, n_covar, covariates, model, out, errbuf);
 	if (rc != PGH_OK) {
 		return rc;
-	}
-	if (model != PGH_GLM_LINEAR && model != PGH_GLM_LOGISTIC) {
-		SetErr(errbuf, "model must be PGH_GLM_LINEAR or PGH_GLM_LOGISTIC");
-		return PGH_ERR_ARG;
-	}
-	if (n_covar > PGH_GLM_MAX_COVAR) {
-		SetErr(errbuf, "at most " + std::to_string(PGH_GLM_MAX_COVAR) + " covariates are supported, got " +
-		                   std::to_string(n_covar));
-		return PGH_ERR_ARG;
-	}
-	if (subset && subset->ds != ds) {
-		SetErr(errbuf, "sample subset belongs to a different dataset");
-		return PGH_ERR_ARG;
-	}
-	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct;
-	if ((n_out && !phenotype) || (n_covar && n_out && !covariates) || (v_end > v_begin && !out)) {
-		SetErr(errbuf, "null argument");
-		return PGH_ERR_ARG;
-	}
-	for (uint64_t i = 0; i < static_cast<uint64_t>(n_covar) * n_out; i++) {
-		if (!std::isfinite(covariates[i])) {
-			SetErr(errbuf, "covariate " + std::to_string(i / n_out) + " is not finite at sample " +
-			                   std::to_string(i % n_out));
-			return PGH_ERR_ARG;
-		}
 	}
 	if (v_end == v_begin) {
 		return PGH_OK;
@@ -251,4 +491,30 @@ extern "C" int pgh_glm(const pgh_dataset *ds, const pgh_subset *subset, uint32_t
 		return PGH_OK;
 	}
 	return GlmOne(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, model, firth, out, errbuf);
+}
+
+extern "C" int pgh_glm_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                             uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
+                             int model, int firth, pgh_glm_row *out, char *errbuf) {
+	int rc = GlmCheckArgs(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, model, out, errbuf);
+	if (rc != PGH_OK || v_end == v_begin) {
+		return rc;
+	}
+	if (ds->IsGroup()) {
+		// every shard fills its own slice of out, as in pgh_glm
+		for (size_t k = 0; k < ds->shards.size(); k++) {
+			const pgh_dataset *s = ds->shards[k];
+			const uint32_t lo = std::max(v_begin, s->v_begin), hi = std::min(v_end, s->v_end);
+			if (lo >= hi) {
+				continue;
+			}
+			rc = GlmMultiOne(s, subset ? subset->parts[k] : nullptr, lo, hi, n_pheno, phenotypes, n_covar, covariates,
+			                 model, firth, out + static_cast<size_t>(lo - v_begin) * n_pheno, errbuf);
+			if (rc != PGH_OK) {
+				return rc;
+			}
+		}
+		return PGH_OK;
+	}
+	return GlmMultiOne(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, model, firth, out, errbuf);
 }

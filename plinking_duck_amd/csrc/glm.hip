@@ -683,6 +683,316 @@ __global__ void GlmLogisticFinishKernel(uint32_t nv, uint32_t kp, uint32_t k, co
 	rows[v] = r;
 }
 
+// ---------------------------------------------------------------------------
+// many phenotypes (pgh_glm_multi, linear): the phenotypes of one missing-value pattern share n, sum x, sum x^2,
+// sum x z_j, the (1, z) Gram and its corrections; each adds sum x y_p and the (1, y_p), (z_j, y_p), (y_p, y_p) entries.
+// Every per-phenotype number of a variant is one thread's sequential FMA chain over the samples in order, so it does
+// not depend on the phenotype tile, the other phenotypes or the variant chunk.
+// ---------------------------------------------------------------------------
+
+// sxy[v][p] = sum_i x_v(i) y_p(i): a GEMM of the chunk's genotype rows (nv x n_out) and the phenotype block
+// (pb x n_out, phenotype-major, 0 where missing).  A workgroup owns TV variants x TP phenotypes and each thread an
+// MV x MP register tile; both operands pass through LDS kXyS samples at a time (missing calls staged as 0).
+constexpr int kXyS = 32;
+
+template <int MV, int MP, int NTP>
+__global__ void __launch_bounds__(kBlock) GlmMultiXyKernel(GlmX g, uint32_t nv, const double *__restrict__ yb,
+                                                           uint32_t pb, double *__restrict__ sxy) {
+	constexpr int NTV = kBlock / NTP;
+	constexpr int TV = NTV * MV, TP = NTP * MP, S = kXyS;
+	__shared__ double xs[S][TV];
+	__shared__ double ys[S][TP];
+	const uint32_t v0 = blockIdx.x * TV, p0 = blockIdx.y * TP;
+	const int tv = threadIdx.x % NTV, tp = threadIdx.x / NTV;
+	double acc[MV][MP];
+#pragma unroll
+	for (int a = 0; a < MV; a++) {
+#pragma unroll
+		for (int b = 0; b < MP; b++) {
+			acc[a][b] = 0.0;
+		}
+	}
+	for (uint32_t i0 = 0; i0 < g.n_out; i0 += S) {
+		for (int e = threadIdx.x; e < TV * S; e += kBlock) {
+			const int s = e % S, t = e / S;
+			const uint32_t v = v0 + t, i = i0 + s;
+			double x = 0.0;
+			if (v < nv && i < g.n_out) {
+				x = GlmValue(g, v, i);
+				x = x == -9.0 ? 0.0 : x;
+			}
+			xs[s][t] = x;
+		}
+		for (int e = threadIdx.x; e < TP * S; e += kBlock) {
+			const int s = e % S, t = e / S;
+			const uint32_t p = p0 + t, i = i0 + s;
+			ys[s][t] = p < pb && i < g.n_out ? yb[static_cast<uint64_t>(p) * g.n_out + i] : 0.0;
+		}
+		__syncthreads();
+#pragma unroll 4
+		for (int s = 0; s < S; s++) {
+			double xr[MV], yr[MP];
+#pragma unroll
+			for (int a = 0; a < MV; a++) {
+				xr[a] = xs[s][tv * MV + a];
+			}
+#pragma unroll
+			for (int b = 0; b < MP; b++) {
+				yr[b] = ys[s][tp * MP + b];
+			}
+#pragma unroll
+			for (int a = 0; a < MV; a++) {
+#pragma unroll
+				for (int b = 0; b < MP; b++) {
+					acc[a][b] = fma(xr[a], yr[b], acc[a][b]);
+				}
+			}
+		}
+		__syncthreads();
+	}
+#pragma unroll
+	for (int a = 0; a < MV; a++) {
+#pragma unroll
+		for (int b = 0; b < MP; b++) {
+			const uint32_t v = v0 + tv * MV + a, p = p0 + tp * MP + b;
+			if (v < nv && p < pb) {
+				sxy[static_cast<uint64_t>(v) * pb + p] = acc[a][b];
+			}
+		}
+	}
+}
+
+// whole[p][0..k+1] = {sum y_p, sum z_j y_p (j < k), sum y_p^2} over every sample (y_p = 0 where missing); one
+// workgroup per phenotype, BlockSums' fixed order.
+template <int KP>
+__global__ void __launch_bounds__(kBlock) GlmMultiWholeKernel(uint32_t n_out, const double *__restrict__ yb,
+                                                              const double *__restrict__ z, uint32_t k,
+                                                              double *__restrict__ whole) {
+	constexpr int NE = KP + 2;
+	__shared__ double lds[kWaves * NE];
+	__shared__ double tile[NE];
+	const uint32_t p = blockIdx.x;
+	const double *y = yb + static_cast<uint64_t>(p) * n_out;
+	double acc[NE];
+#pragma unroll
+	for (int e = 0; e < NE; e++) {
+		acc[e] = 0.0;
+	}
+	for (uint32_t i = threadIdx.x; i < n_out; i += kBlock) {
+		const double yi = y[i];
+		acc[0] += yi;
+#pragma unroll
+		for (int j = 0; j < KP; j++) {
+			acc[1 + j] += z[static_cast<uint64_t>(i) * KP + j] * yi;
+		}
+		acc[KP + 1] += yi * yi;
+	}
+	BlockSums<NE>(acc, lds, tile);
+	__syncthreads();
+	double *dst = whole + static_cast<uint64_t>(p) * (k + 2);
+	for (uint32_t e = threadIdx.x; e < k + 2; e += kBlock) {
+		dst[e] = tile[e <= k ? e : KP + 1];
+	}
+}
+
+// The missing-call corrections of one variant per workgroup, over its samples with a phenotype (the group's
+// pattern: ypat is NaN where it is missing) and no value: corr_s[v] = the packed Gram of [1, z] ((k+1)(k+2)/2
+// entries), corr_p[v][p][0..k+1] = {sum y_p, sum z_j y_p, sum y_p^2}.  The compacted list of those samples
+// (GlmGramKernel's, per 256-sample chunk, in sample order) is contracted against the phenotype block kYSub list
+// entries at a time; a thread owns up to kCorrRegs (phenotype, entry) pairs in registers.  Variants with no such
+// sample (sums[v][0] == n_y) write zeros.
+constexpr int kYSub = 16;
+constexpr int kCorrRegs = (kGlmMultiPb * kMaxP + kBlock - 1) / kBlock;
+
+__global__ void __launch_bounds__(kBlock) GlmMultiCorrKernel(GlmX g, const double *__restrict__ sums, uint32_t ns,
+                                                             uint32_t n_y, const double *__restrict__ ypat,
+                                                             const double *__restrict__ yb, uint32_t pb,
+                                                             const double *__restrict__ z, uint32_t kp, uint32_t k,
+                                                             double *__restrict__ corr_s, double *__restrict__ corr_p) {
+	const uint32_t qs = k + 1, nes = qs * (qs + 1) / 2, qp = k + 2, nep = pb * qp;
+	const uint32_t v = blockIdx.x;
+	double *ds = corr_s + static_cast<uint64_t>(v) * nes;
+	double *dp = corr_p + static_cast<uint64_t>(v) * nep;
+	if (sums[static_cast<uint64_t>(v) * ns] == static_cast<double>(n_y)) {
+		for (uint32_t e = threadIdx.x; e < nes; e += kBlock) {
+			ds[e] = 0.0;
+		}
+		for (uint32_t e = threadIdx.x; e < nep; e += kBlock) {
+			dp[e] = 0.0;
+		}
+		return;
+	}
+	extern __shared__ double lz[]; // kBlock list rows [1, z_1..z_k] (sized at launch)
+	__shared__ uint32_t lidx[kBlock];
+	__shared__ double ysub[kYSub * kGlmMultiPb];
+	__shared__ uint32_t wave_ct[kWaves];
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	int ea = -1, eb = -1;
+	if (threadIdx.x < nes) {
+		int t = threadIdx.x, a = 0;
+		while (t >= static_cast<int>(qs) - a) {
+			t -= qs - a;
+			a++;
+		}
+		ea = a;
+		eb = a + t;
+	}
+	double acc_s = 0.0;
+	double acc_p[kCorrRegs];
+#pragma unroll
+	for (int r = 0; r < kCorrRegs; r++) {
+		acc_p[r] = 0.0;
+	}
+	for (uint32_t c0 = 0; c0 < g.n_out; c0 += kBlock) {
+		const uint32_t i = c0 + threadIdx.x;
+		bool take = false;
+		if (i < g.n_out) {
+			const double yi = ypat[i];
+			take = yi == yi && GlmValue(g, v, i) == -9.0;
+		}
+		const uint64_t bal = __ballot(take);
+		if (lane == 0) {
+			wave_ct[wave] = static_cast<uint32_t>(__popcll(bal));
+		}
+		__syncthreads();
+		uint32_t base = 0, total = 0;
+		for (int w = 0; w < kWaves; w++) {
+			base += w < wave ? wave_ct[w] : 0u;
+			total += wave_ct[w];
+		}
+		if (take) {
+			const uint32_t pos = base + static_cast<uint32_t>(__popcll(bal & ((1ull << lane) - 1ull)));
+			double *r = lz + pos * qs;
+			r[0] = 1.0;
+			for (uint32_t j = 0; j < k; j++) {
+				r[1 + j] = z[static_cast<uint64_t>(i) * kp + j];
+			}
+			lidx[pos] = i;
+		}
+		__syncthreads();
+		// total is the same in every thread: the loop below and its barriers are uniform
+		if (ea >= 0) {
+			for (uint32_t s = 0; s < total; s++) {
+				acc_s += lz[s * qs + ea] * lz[s * qs + eb];
+			}
+		}
+		for (uint32_t b0 = 0; b0 < total; b0 += kYSub) {
+			const uint32_t nb = min(total - b0, static_cast<uint32_t>(kYSub));
+			for (uint32_t e = threadIdx.x; e < nb * pb; e += kBlock) {
+				const uint32_t s = e / pb, p = e % pb;
+				ysub[s * kGlmMultiPb + p] = yb[static_cast<uint64_t>(p) * g.n_out + lidx[b0 + s]];
+			}
+			__syncthreads();
+#pragma unroll
+			for (int r = 0; r < kCorrRegs; r++) {
+				const uint32_t e = threadIdx.x + r * kBlock;
+				if (e < nep) {
+					const uint32_t p = e / qp, j = e % qp;
+					double a = acc_p[r];
+					for (uint32_t s = 0; s < nb; s++) {
+						const double yv = ysub[s * kGlmMultiPb + p];
+						const double u = j == 0 ? 1.0 : j <= k ? lz[(b0 + s) * qs + j] : yv;
+						a = fma(u, yv, a);
+					}
+					acc_p[r] = a;
+				}
+			}
+			__syncthreads();
+		}
+	}
+	if (ea >= 0) {
+		ds[threadIdx.x] = acc_s;
+	}
+#pragma unroll
+	for (int r = 0; r < kCorrRegs; r++) {
+		const uint32_t e = threadIdx.x + r * kBlock;
+		if (e < nep) {
+			dp[e] = acc_p[r];
+		}
+	}
+}
+
+// The OLS of (variant, phenotype) pairs, one thread each: GlmLinearSolveKernel's augmented Cholesky in the order [1,
+// z, x, y_p], with the (1, z) block from the group's Gram and correction and the y_p entries from whole and corr_p.
+__global__ void GlmMultiSolveKernel(uint32_t nv, uint32_t pb, const double *__restrict__ sums, uint32_t kp, uint32_t k,
+                                    const double *__restrict__ sxy, const double *__restrict__ gram,
+                                    const double *__restrict__ whole, const double *__restrict__ corr_s,
+                                    const double *__restrict__ corr_p, pgh_glm_row *__restrict__ rows) {
+	const uint64_t t = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+	if (t >= static_cast<uint64_t>(nv) * pb) {
+		return;
+	}
+	const uint32_t v = static_cast<uint32_t>(t / pb), ph = static_cast<uint32_t>(t % pb);
+	const uint32_t ns = kp + 4, q = k + 2, qs = k + 1, nes = qs * (qs + 1) / 2;
+	const double *s = sums + static_cast<uint64_t>(v) * ns;
+	const double *cs = corr_s + static_cast<uint64_t>(v) * nes;
+	const double *cp = corr_p + t * q;
+	const double *wp = whole + static_cast<uint64_t>(ph) * q;
+	pgh_glm_row r;
+	SetRowNull(r);
+	const double n = s[0];
+	const int p = static_cast<int>(k) + 2;
+	r.obs_ct = static_cast<uint32_t>(n);
+	if (n < p + 1) {
+		r.errcode = PGH_GLM_TOO_FEW_SAMPLES;
+		rows[t] = r;
+		return;
+	}
+	r.a1_freq = s[1] / (2.0 * n);
+	if (k ? GlmConstant(n, s[1], s[2]) : s[2] - s[1] * s[1] / n < 1e-20) {
+		r.errcode = PGH_GLM_CONST_ALLELE;
+		rows[t] = r;
+		return;
+	}
+	// augmented matrix, order [1, z_1..z_k, x, y], lower triangle
+	constexpr int M = kMaxP + 1;
+	double a[M * M];
+	const int xi = p - 1, yi = p;
+	for (int ua = 0; ua < static_cast<int>(qs); ua++) {
+		for (int ub = ua; ub < static_cast<int>(qs); ub++) {
+			a[ub * M + ua] = gram[PackIdx(ua, ub, q)] - cs[PackIdx(ua, ub, qs)];
+		}
+		a[yi * M + ua] = wp[ua] - cp[ua];
+	}
+	a[yi * M + yi] = wp[k + 1] - cp[k + 1];
+	a[xi * M + 0] = s[1];
+	for (int j = 0; j < static_cast<int>(k); j++) {
+		a[xi * M + 1 + j] = s[4 + j];
+	}
+	a[xi * M + xi] = s[2];
+	a[yi * M + xi] = sxy[t];
+	if (!GlmCholesky(a, p, M, k ? 1e-10 : 0.0, nullptr)) {
+		r.errcode = PGH_GLM_SINGULAR_MATRIX;
+		rows[t] = r;
+		return;
+	}
+	double rss = a[yi * M + yi];
+	for (int j = 0; j < p; j++) {
+		double l = a[yi * M + j];
+		for (int c = 0; c < j; c++) {
+			l -= a[yi * M + c] * a[j * M + c];
+		}
+		l /= a[j * M + j];
+		a[yi * M + j] = l;
+		rss -= l * l;
+	}
+	rss = rss < 0.0 ? 0.0 : rss;
+	const double lxx = a[xi * M + xi];
+	const double df = n - p;
+	const double se2 = rss / df / (lxx * lxx);
+	const double beta = a[yi * M + xi] / lxx;
+	r.beta = beta;
+	if (se2 < 1e-30) {
+		r.errcode = PGH_GLM_ZERO_VARIANCE;
+		rows[t] = r;
+		return;
+	}
+	r.se = sqrt(se2);
+	r.stat = beta / r.se;
+	r.p = GlmPFromT(r.stat, df);
+	rows[t] = r;
+}
+
 uint32_t Blocks(uint32_t n, uint32_t per) {
 	return (n + per - 1) / per;
 }
@@ -822,6 +1132,80 @@ hipError_t LaunchGlmLogisticFinish(uint32_t nv, uint32_t kp, uint32_t k, const G
 		return hipSuccess;
 	}
 	GlmLogisticFinishKernel<<<Blocks(nv, 64), 64, 0, stream>>>(nv, kp, k, st, beta, hmat, rows);
+	return hipGetLastError();
+}
+
+hipError_t LaunchGlmMultiXy(const GlmX &g, uint32_t nv, const double *yb, uint32_t pb, double *sxy,
+                            hipStream_t stream) {
+	if (nv == 0 || pb == 0) {
+		return hipSuccess;
+	}
+	if (pb > kGlmMultiPb) {
+		return hipErrorInvalidValue;
+	}
+	// 64 variants x 8 phenotypes (2 x 1 per thread) for small blocks, 64 x 64 (4 x 4) otherwise
+	if (pb <= 8) {
+		GlmMultiXyKernel<2, 1, 8><<<dim3(Blocks(nv, 64), 1), kBlock, 0, stream>>>(g, nv, yb, pb, sxy);
+	} else {
+		GlmMultiXyKernel<4, 4, 16><<<dim3(Blocks(nv, 64), 1), kBlock, 0, stream>>>(g, nv, yb, pb, sxy);
+	}
+	return hipGetLastError();
+}
+
+hipError_t LaunchGlmMultiWhole(uint32_t n_out, const double *yb, uint32_t pb, const double *z, uint32_t kp,
+                               uint32_t k, double *whole, hipStream_t stream) {
+	if (pb == 0) {
+		return hipSuccess;
+	}
+	if (k > kp) {
+		return hipErrorInvalidValue;
+	}
+#define PGH_WHOLE(KP_)                                                                                                 \
+	case KP_:                                                                                                          \
+		GlmMultiWholeKernel<KP_><<<pb, kBlock, 0, stream>>>(n_out, yb, z, k, whole);                                   \
+		break;
+	switch (kp) {
+		PGH_WHOLE(0)
+		PGH_WHOLE(1)
+		PGH_WHOLE(2)
+		PGH_WHOLE(4)
+		PGH_WHOLE(8)
+		PGH_WHOLE(12)
+		PGH_WHOLE(16)
+		PGH_WHOLE(20)
+	default:
+		return hipErrorInvalidValue;
+	}
+#undef PGH_WHOLE
+	return hipGetLastError();
+}
+
+hipError_t LaunchGlmMultiCorr(const GlmX &g, uint32_t nv, const double *sums, uint32_t n_y, const double *ypat,
+                              const double *yb, uint32_t pb, const double *z, uint32_t kp, uint32_t k, double *corr_s,
+                              double *corr_p, hipStream_t stream) {
+	if (nv == 0) {
+		return hipSuccess;
+	}
+	if (pb > kGlmMultiPb || k > 20 || k > kp) {
+		return hipErrorInvalidValue;
+	}
+	GlmMultiCorrKernel<<<nv, kBlock, sizeof(double) * kBlock * (k + 1), stream>>>(g, sums, kp + 4, n_y, ypat, yb, pb, z,
+	                                                                              kp, k, corr_s, corr_p);
+	return hipGetLastError();
+}
+
+hipError_t LaunchGlmMultiSolve(uint32_t nv, uint32_t pb, const double *sums, uint32_t kp, uint32_t k,
+                               const double *sxy, const double *gram, const double *whole, const double *corr_s,
+                               const double *corr_p, pgh_glm_row *rows, hipStream_t stream) {
+	const uint64_t n = static_cast<uint64_t>(nv) * pb;
+	if (n == 0) {
+		return hipSuccess;
+	}
+	if (k > 20 || n > 0xffffffffull - 64) {
+		return hipErrorInvalidValue;
+	}
+	GlmMultiSolveKernel<<<Blocks(static_cast<uint32_t>(n), 64), 64, 0, stream>>>(nv, pb, sums, kp, k, sxy, gram, whole,
+	                                                                            corr_s, corr_p, rows);
 	return hipGetLastError();
 }
 

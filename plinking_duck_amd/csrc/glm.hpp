@@ -75,4 +75,27 @@ constexpr uint32_t kGlmMaxP = 22;
 hipError_t LaunchGlmLogisticFinish(uint32_t nv, uint32_t kp, uint32_t k, const GlmState *st,
                                    const double *beta, const double *hmat, pgh_glm_row *rows, hipStream_t stream);
 
+// ---- pgh_glm_multi, linear: the phenotypes of one missing-value pattern, at most kGlmMultiPb per launch ----
+// yb: pb x n_out doubles, phenotype-major, centred, 0 where missing.  ypat: n_out doubles, NaN exactly where the
+// pattern's phenotypes are missing.  Every (variant, phenotype) number is one thread's sequential sum over the
+// samples, so none depends on pb, the phenotype's place in the block or the chunk.
+constexpr uint32_t kGlmMultiPb = 64;
+// sxy[i][p] = sum x y_p over the chunk variant's samples with a value (pb <= kGlmMultiPb)
+hipError_t LaunchGlmMultiXy(const GlmX &g, uint32_t nv, const double *yb, uint32_t pb, double *sxy,
+                            hipStream_t stream);
+// whole[p][0..k+1] = {sum y_p, sum z_j y_p (j < k), sum y_p^2} over every sample with a phenotype
+hipError_t LaunchGlmMultiWhole(uint32_t n_out, const double *yb, uint32_t pb, const double *z, uint32_t kp,
+                               uint32_t k, double *whole, hipStream_t stream);
+// Per chunk variant, over its samples with a phenotype and no value: corr_s[i] = packed Gram of [1, z]
+// ((k+1)(k+2)/2 entries), corr_p[i][p][0..k+1] = whole's entries (zeros for variants that have none: sums[i][0] ==
+// n_y).  sums: LaunchGlmSums' rows (stride kp + 4).
+hipError_t LaunchGlmMultiCorr(const GlmX &g, uint32_t nv, const double *sums, uint32_t n_y, const double *ypat,
+                              const double *yb, uint32_t pb, const double *z, uint32_t kp, uint32_t k, double *corr_s,
+                              double *corr_p, hipStream_t stream);
+// rows[i][p]: the OLS of chunk variant i and phenotype p.  gram: LaunchGlmGram's whole-call Gram of [1, z, ypat]
+// (only its (1, z) block is read).
+hipError_t LaunchGlmMultiSolve(uint32_t nv, uint32_t pb, const double *sums, uint32_t kp, uint32_t k,
+                               const double *sxy, const double *gram, const double *whole, const double *corr_s,
+                               const double *corr_p, pgh_glm_row *rows, hipStream_t stream);
+
 } // namespace pgh
