@@ -532,6 +532,52 @@ double pgh_glm_p_from_t(double t, double df);
 /* two-sided p of a standard normal z (ZstatToPvalue) */
 double pgh_glm_p_from_z(double z);
 
+/* ---- KING-robust kinship -------------------------------- */
+
+/* For two samples i and j, over the variants of the call at which BOTH have a hardcall (dosage and phase tracks are
+ * not read), five uint32 counts:
+ *   NSNP      both called                         HETHET    i het and j het
+ *   IBS0      one hom-ref, the other hom-alt      HET1HOM2  i het and j homozygous     HET2HOM1  i homozygous, j het
+ * and from them, in FP64,
+ *   min_het = HETHET + min(HET1HOM2, HET2HOM1)
+ *   KINSHIP = 0.5 - (4 IBS0 + HET1HOM2 + HET2HOM1) / (4 min_het)          (NaN when min_het == 0)
+ * the KING-robust between-family estimator (Manichaikul et al. 2010) with the smaller of the two het counts.  This
+ * formula is the definition; it has not been compared with plink2 --make-king-table's output.
+ * The counts are exact: products of 0 / +-1 indicator planes accumulated in int32 on the int8 matrix cores.
+ * Both entry points take one dense-resident dataset (not a shard group, not a sparse-resident dataset). */
+enum { PGH_KING_NSNP = 0, PGH_KING_HETHET = 1, PGH_KING_IBS0 = 2, PGH_KING_HET1HOM2 = 3,
+       PGH_KING_HET2HOM1 = 4, PGH_KING_PLANES = 5 };
+
+/* Counts for the rectangle of sample pairs [i_begin, i_end) x [j_begin, j_end) (indices into the output
+ * samples: subset order, or raw order without a subset).  counts: PGH_KING_PLANES planes of
+ * (i_end - i_begin) x (j_end - j_begin) uint32, plane-major, i-major inside a plane, host memory.
+ * Variants: [variant_begin, variant_begin + n_var), or the n_var entries of vidx when it is not NULL
+ * (pgh_sample_counts' convention); 1 <= n_var <= 2^31 - 1.  "1" is the row sample, "2" the column sample.  The
+ * rectangle may lie anywhere, the diagonal included (there a sample is paired with itself); an empty or reversed
+ * one, or one beyond the output samples, is PGH_ERR_ARG. */
+int pgh_king_counts(const pgh_dataset *ds, const pgh_subset *subset, uint32_t variant_begin, uint32_t n_var,
+                    const uint32_t *vidx, uint32_t i_begin, uint32_t i_end, uint32_t j_begin, uint32_t j_end,
+                    uint32_t *counts, char *errbuf);
+
+typedef struct pgh_king_pair {
+	uint32_t i, j;                                   /* output-sample indices, i < j */
+	uint32_t nsnp, hethet, ibs0, het1hom2, het2hom1; /* "1" is i, "2" is j          */
+	uint32_t pad;
+	double kinship;
+} pgh_king_pair;
+
+/* Every pair i < j of the output samples whose KINSHIP >= min_kinship, ascending by (i, j).  A NaN kinship
+ * never passes; min_kinship = -INFINITY or NaN means no filter (every pair, NaN ones included).
+ * *n_pairs receives the number of qualifying pairs whether or not they fit; at most `capacity` of them
+ * (the first in (i, j) order) are written to out.  out may be NULL when capacity is 0: a counting call.
+ * The same call returns the same bytes every time. */
+int pgh_king_table(const pgh_dataset *ds, const pgh_subset *subset, uint32_t variant_begin, uint32_t n_var,
+                   const uint32_t *vidx, double min_kinship, pgh_king_pair *out, uint64_t capacity,
+                   uint64_t *n_pairs, char *errbuf);
+
+/* The formula above, on the host (the table's KINSHIP is this function of its own counts, bit for bit). */
+double pgh_king_kinship(uint32_t hethet, uint32_t ibs0, uint32_t het1hom2, uint32_t het2hom1);
+
 /* ---- HWE exact tests (host) --------------------------------------------- */
 
 /* plink2::HweLnP (src/plink_hardy.cpp:78): ln of the two-sided exact-test p. */

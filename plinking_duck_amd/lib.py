@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "pgh_tally_start", "pgh_tally_request", "pgh_tally_wait", "pgh_tally_counts", "pgh_tally_hwe_lnp",
     "pgh_tally_sample_missing", "pgh_tally_destroy", "pgh_tally_passes_started", "pgh_host_alloc", "pgh_host_free", "pgh_trim_device_cache",
     "pgh_reader_error", "pgh_open_sparse", "pgh_get_sparse_info", "pgh_sparse_opens_started", "pgh_glm", "pgh_glm_multi", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
+    "pgh_king_counts", "pgh_king_table", "pgh_king_kinship",
 ]
 
 
@@ -72,6 +73,11 @@ class PghGlmRow(C.Structure):
     ]
 
 
+# pgh_king_counts' planes, pgh_king_pair, and the kernel's tile of sample pairs (a test of tile edges names it)
+KING_NSNP, KING_HETHET, KING_IBS0, KING_HET1HOM2, KING_HET2HOM1, KING_PLANES = 0, 1, 2, 3, 4, 5
+KING_TILE = 128
+KING_PAIR_DTYPE = np.dtype([("i", "<u4"), ("j", "<u4"), ("nsnp", "<u4"), ("hethet", "<u4"), ("ibs0", "<u4"),
+                            ("het1hom2", "<u4"), ("het2hom1", "<u4"), ("pad", "<u4"), ("kinship", "<f8")])
 GLM_ROW_DTYPE = np.dtype([("beta", "<f8"), ("se", "<f8"), ("stat", "<f8"), ("p", "<f8"), ("a1_freq", "<f8"),
                           ("obs_ct", "<u4"), ("errcode", "u1"), ("firth", "u1"), ("pad", "u1", (2,))])
 
@@ -193,6 +199,9 @@ def _load():
         "pgh_glm_multi": (C.c_int, [vp, vp, u32, u32, u32, vp, u32, vp, C.c_int, C.c_int, vp, cp]),
         "pgh_glm_p_from_t": (C.c_double, [C.c_double, C.c_double]),
         "pgh_glm_p_from_z": (C.c_double, [C.c_double]),
+        "pgh_king_counts": (C.c_int, [vp, vp, u32, u32, vp, u32, u32, u32, u32, vp, cp]),
+        "pgh_king_table": (C.c_int, [vp, vp, u32, u32, vp, C.c_double, vp, u64, C.POINTER(u64), cp]),
+        "pgh_king_kinship": (C.c_double, [u32, u32, u32, u32]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -234,6 +243,12 @@ def glm_p_from_t(t: float, df: float) -> float:
 def glm_p_from_z(z: float) -> float:
     """Two-sided p of a standard normal z (ZstatToPvalue)."""
     return _lib.pgh_glm_p_from_z(float(z))
+
+
+def king_kinship(hethet: int, ibs0: int, het1hom2: int, het2hom1: int) -> float:
+    """pgh_king_kinship: 0.5 - (4 IBS0 + HET1HOM2 + HET2HOM1) / (4 (HETHET + min(HET1HOM2, HET2HOM1))), NaN when the
+    denominator is zero -- the function king_table's kinship column is of its own counts."""
+    return _lib.pgh_king_kinship(int(hethet), int(ibs0), int(het1hom2), int(het2hom1))
 
 
 def glm_model(phenotype, model: str = "auto"):
@@ -782,6 +797,51 @@ class Dataset:
             "errcode": np.array(GLM_ERRCODES, dtype=object)[rows["errcode"]],
             "firth": rows["firth"].astype(bool),
         }
+
+    def king_counts(self, v_begin: int | None = None, v_end: int | None = None, vidx=None,
+                    subset: Subset | None = None, i_range=None, j_range=None) -> np.ndarray:
+        """pgh_king_counts: uint32[KING_PLANES][ni][nj], the KING pair counts (NSNP, HETHET, IBS0, HET1HOM2, HET2HOM1;
+        "1" is the row sample) of output samples i_range x j_range (default: all of them) over a variant range or
+        list."""
+        n_out = subset.size if subset else self.n_samples
+        i0, i1 = (0, n_out) if i_range is None else (int(i_range[0]), int(i_range[1]))
+        j0, j1 = (0, n_out) if j_range is None else (int(j_range[0]), int(j_range[1]))
+        v0, n, v = self._range_or_list(v_begin, v_end, vidx)
+        for x in (i0, i1, j0, j1, v0, n):
+            if not 0 <= x <= 0xFFFFFFFF:
+                raise ValueError(f"king_counts: {x} is not an unsigned 32-bit index")
+        out = np.zeros((KING_PLANES, max(0, i1 - i0), max(0, j1 - j0)), dtype=np.uint32)
+        eb = _errbuf()
+        _check(_lib.pgh_king_counts(self._h, subset._h if subset else None, v0, n, _ptr(v) if v is not None else None,
+                                    i0, i1, j0, j1, _ptr(out), eb), eb)
+        return out
+
+    def king_table_capped(self, min_kinship: float, capacity: int, v_begin: int | None = None,
+                          v_end: int | None = None, vidx=None, subset: Subset | None = None):
+        """pgh_king_table as it is: (rows, n_pairs) -- the first `capacity` rows at most of the table in (i, j) order
+        (a KING_PAIR_DTYPE array) and the number of qualifying pairs.  capacity 0 is a counting call."""
+        v0, n, v = self._range_or_list(v_begin, v_end, vidx)
+        for x in (v0, n):
+            if not 0 <= x <= 0xFFFFFFFF:
+                raise ValueError(f"king_table: {x} is not an unsigned 32-bit index")
+        capacity = int(capacity)
+        rows = np.zeros(capacity, dtype=KING_PAIR_DTYPE)
+        found = C.c_uint64(0)
+        eb = _errbuf()
+        _check(_lib.pgh_king_table(self._h, subset._h if subset else None, v0, n, _ptr(v) if v is not None else None,
+                                   float(min_kinship), _ptr(rows) if capacity else None, capacity, C.byref(found), eb),
+               eb)
+        return rows[: min(found.value, capacity)], int(found.value)
+
+    def king_table(self, min_kinship: float = float("-inf"), v_begin: int | None = None, v_end: int | None = None,
+                   vidx=None, subset: Subset | None = None) -> np.ndarray:
+        """The pairs i < j of the output samples with kinship >= min_kinship (-inf or NaN: every pair, NaN ones
+        included), ascending by (i, j), as a KING_PAIR_DTYPE array (i, j, nsnp, hethet, ibs0, het1hom2, het2hom1,
+        kinship).  A second call with a buffer of the reported size follows when the first was too small."""
+        rows, found = self.king_table_capped(min_kinship, 65536, v_begin, v_end, vidx, subset)
+        if found > len(rows):
+            rows, found = self.king_table_capped(min_kinship, found, v_begin, v_end, vidx, subset)
+        return rows
 
     def unpack_samples(self, vidx, subset: Subset | None = None, missing_code: int = -9) -> np.ndarray:
         """int8[n_out][len(vidx)]: the calls sample-major (read_pfile orient := 'sample')."""
