@@ -578,6 +578,57 @@ int pgh_king_table(const pgh_dataset *ds, const pgh_subset *subset, uint32_t var
 /* The formula above, on the host (the table's KINSHIP is this function of its own counts, bit for bit). */
 double pgh_king_kinship(uint32_t hethet, uint32_t ibs0, uint32_t het1hom2, uint32_t het2hom1);
 
+/* ---- windowed r2 and LD pruning -------------------------- */
+
+/* For two variants a and b of the call, over the output samples at which BOTH have a hardcall (dosage and phase
+ * tracks are not read; a sample outside the subset counts as missing everywhere), pgh_ld_pairs' six uint32 sums
+ *   n, sum_a, sum_b, sum_ab, sum_a2, sum_b2            (genotype = ALT copies 0 / 1 / 2)
+ * as products of three small-integer planes per variant on the int8 matrix cores, exact in int32 for up to 2^29 - 1
+ * samples (more: PGH_ERR_ARG).  From them, in int64 and then FP64,
+ *   num = n sum_ab - sum_a sum_b     va = n sum_a2 - sum_a^2     vb = n sum_b2 - sum_b^2
+ *   the pair EXCEEDS r2_threshold iff n >= 2, va > 0, vb > 0 and ((double)num * (double)num) / ((double)va *
+ *   (double)vb) > r2_threshold
+ * so a variant that is monomorphic over the pair's samples never exceeds.  This is not plink_ld's mean-based
+ * arithmetic; plink_ld's output is unchanged.  Minor-allele order, per variant over the output samples:
+ *   alt = het + 2 hom_alt, obs = 2 called, mc = min(alt, obs - alt); k has the LOWER MAF than u iff
+ *   mc_k obs_u < mc_u obs_k in uint64 (obs = 0 compares as equal to everything).
+ * Pruning rule over the call's variants k = 0 .. n_var - 1 in call order, win_end[k] the exclusive end of k's window:
+ *   keep[:] = 1
+ *   for k in 0 .. n_var-1:   if keep[k]:
+ *     for u in k+1 .. win_end[k]-1:   if keep[u] and exceeds(k, u):
+ *       if lower_maf(k, u): keep[k] = 0; break      else: keep[u] = 0        (ties remove the later variant)
+ * These formulas are the definition; they have not been compared with plink2 --indep-pairwise's output
+ * (DESIGN.md 3.13).  Both device entry points take one dense-resident dataset (not a shard group, not a
+ * sparse-resident dataset). */
+enum { PGH_LD_N = 0, PGH_LD_SUM_A = 1, PGH_LD_SUM_B = 2, PGH_LD_SUM_AB = 3, PGH_LD_SUM_A2 = 4, PGH_LD_SUM_B2 = 5,
+       PGH_LD_PLANES = 6 };
+
+/* Sums for the rectangle of variant pairs [a_begin, a_end) x [b_begin, b_end) (indices into the call's variants:
+ * [variant_begin, variant_begin + n_var), or the n_var entries of vidx when it is not NULL, in any order).
+ * sums: PGH_LD_PLANES planes of (a_end - a_begin) x (b_end - b_begin) uint32, plane-major, a-major inside a plane,
+ * host memory.  The rectangle may lie anywhere, the diagonal included; an empty or reversed one, or one beyond
+ * n_var, is PGH_ERR_ARG.  1 <= n_var <= 2^31 - 1. */
+int pgh_ld_window_sums(const pgh_dataset *ds, const pgh_subset *subset, uint32_t variant_begin, uint32_t n_var,
+                       const uint32_t *vidx, uint32_t a_begin, uint32_t a_end, uint32_t b_begin, uint32_t b_end,
+                       uint32_t *sums, char *errbuf);
+
+/* The pruning rule above: keep[k] = 1 or 0 for each of the call's n_var variants, *n_kept (may be NULL) their sum.
+ * win_end: n_var entries with k < win_end[k] <= n_var, not decreasing in k (variant-count windows, kb windows and
+ * chromosome boundaries are all this one array).  A vidx list must be strictly increasing; r2_threshold must be
+ * finite and in [0, 1].  Any violation is PGH_ERR_ARG.  Only the tiles of pairs that meet the band
+ * k < u < win_end[k] are computed; a pair's sums never leave the registers, one bit per band pair comes back.
+ * The band is walked in launches of at most PGH_LD_PRUNE_CHUNK_TILES tiles of 96 x 128 pairs (environment
+ * variable, read at every call; default and maximum 32768 = 48 MiB of device scratch for the bits); the result
+ * does not depend on it.  The same call returns the same bytes every time, from any thread. */
+int pgh_ld_prune(const pgh_dataset *ds, const pgh_subset *subset, uint32_t variant_begin, uint32_t n_var,
+                 const uint32_t *vidx, const uint32_t *win_end, double r2_threshold, uint8_t *keep,
+                 uint64_t *n_kept, char *errbuf);
+
+/* "Exceeds" above on the host, of sums = {n, sum_a, sum_b, sum_ab, sum_a2, sum_b2}: 1 or 0.  The device evaluates
+ * the same function of the same sums, bit for bit.  The int64 terms are exact for sums the library can return
+ * (n <= 2^29 - 1); larger hand-made values may wrap. */
+int pgh_ld_exceeds(const uint32_t sums[6], double r2_threshold);
+
 /* ---- HWE exact tests (host) --------------------------------------------- */
 
 /* plink2::HweLnP (src/plink_hardy.cpp:78): ln of the two-sided exact-test p. */

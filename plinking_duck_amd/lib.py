@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = [
     "pgh_tally_sample_missing", "pgh_tally_destroy", "pgh_tally_passes_started", "pgh_host_alloc", "pgh_host_free", "pgh_trim_device_cache",
     "pgh_reader_error", "pgh_open_sparse", "pgh_get_sparse_info", "pgh_sparse_opens_started", "pgh_glm", "pgh_glm_multi", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
     "pgh_king_counts", "pgh_king_table", "pgh_king_kinship",
+    "pgh_ld_window_sums", "pgh_ld_prune", "pgh_ld_exceeds",
 ]
 
 
@@ -78,6 +79,11 @@ KING_NSNP, KING_HETHET, KING_IBS0, KING_HET1HOM2, KING_HET2HOM1, KING_PLANES = 0
 KING_TILE = 128
 KING_PAIR_DTYPE = np.dtype([("i", "<u4"), ("j", "<u4"), ("nsnp", "<u4"), ("hethet", "<u4"), ("ibs0", "<u4"),
                             ("het1hom2", "<u4"), ("het2hom1", "<u4"), ("pad", "<u4"), ("kinship", "<f8")])
+# pgh_ld_window_sums' planes (pgh_ld_pairs' order), the kernel's tile of variant pairs (anchors x partners; a test of
+# tile edges names it) and the environment variable that sets pgh_ld_prune's launch size in tiles
+LD_N, LD_SUM_A, LD_SUM_B, LD_SUM_AB, LD_SUM_A2, LD_SUM_B2, LD_PLANES = 0, 1, 2, 3, 4, 5, 6
+LD_TILE_A, LD_TILE_B = 96, 128
+LD_PRUNE_CHUNK_ENV = "PGH_LD_PRUNE_CHUNK_TILES"
 GLM_ROW_DTYPE = np.dtype([("beta", "<f8"), ("se", "<f8"), ("stat", "<f8"), ("p", "<f8"), ("a1_freq", "<f8"),
                           ("obs_ct", "<u4"), ("errcode", "u1"), ("firth", "u1"), ("pad", "u1", (2,))])
 
@@ -202,6 +208,9 @@ def _load():
         "pgh_king_counts": (C.c_int, [vp, vp, u32, u32, vp, u32, u32, u32, u32, vp, cp]),
         "pgh_king_table": (C.c_int, [vp, vp, u32, u32, vp, C.c_double, vp, u64, C.POINTER(u64), cp]),
         "pgh_king_kinship": (C.c_double, [u32, u32, u32, u32]),
+        "pgh_ld_window_sums": (C.c_int, [vp, vp, u32, u32, vp, u32, u32, u32, u32, vp, cp]),
+        "pgh_ld_prune": (C.c_int, [vp, vp, u32, u32, vp, vp, C.c_double, vp, C.POINTER(u64), cp]),
+        "pgh_ld_exceeds": (C.c_int, [vp, C.c_double]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -249,6 +258,44 @@ def king_kinship(hethet: int, ibs0: int, het1hom2: int, het2hom1: int) -> float:
     """pgh_king_kinship: 0.5 - (4 IBS0 + HET1HOM2 + HET2HOM1) / (4 (HETHET + min(HET1HOM2, HET2HOM1))), NaN when the
     denominator is zero -- the function king_table's kinship column is of its own counts."""
     return _lib.pgh_king_kinship(int(hethet), int(ibs0), int(het1hom2), int(het2hom1))
+
+
+def ld_exceeds(sums, r2: float) -> bool:
+    """pgh_ld_exceeds: whether sums = (n, sum_a, sum_b, sum_ab, sum_a2, sum_b2) has r2 > `r2` -- in int64
+    num = n sum_ab - sum_a sum_b, va = n sum_a2 - sum_a^2, vb = n sum_b2 - sum_b^2; never when n < 2, va <= 0 or
+    vb <= 0; else (float(num) * float(num)) / (float(va) * float(vb)) > r2.  The function ld_prune applies to every
+    pair of its band."""
+    s = np.ascontiguousarray(sums, dtype=np.uint32)
+    if s.shape != (6,):
+        raise ValueError(f"ld_exceeds: six sums expected, got shape {s.shape}")
+    return bool(_lib.pgh_ld_exceeds(_ptr(s), float(r2)))
+
+
+def ld_windows(chrom, pos, kb: float) -> np.ndarray:
+    """win_end for ld_prune from a map: win_end[k] = one past the last u >= k with chrom[u] == chrom[k] and
+    pos[u] - pos[k] <= 1000 kb.  Every chromosome must be one run of variants and pos must not decrease inside it
+    (ValueError otherwise).  Host only."""
+    chrom = np.asarray(chrom)
+    pos = np.asarray(pos, dtype=np.int64)
+    if chrom.ndim != 1 or chrom.shape != pos.shape:
+        raise ValueError("ld_windows: chrom and pos must be one-dimensional and of one length")
+    if not kb >= 0:
+        raise ValueError("ld_windows: kb must be a number >= 0")
+    n = len(pos)
+    out = np.zeros(n, dtype=np.uint32)
+    if n == 0:
+        return out
+    starts = np.concatenate([[0], np.flatnonzero(chrom[1:] != chrom[:-1]) + 1, [n]])
+    names = [chrom[s].item() if hasattr(chrom[s], "item") else chrom[s] for s in starts[:-1]]
+    if len(set(names)) != len(names):
+        raise ValueError("ld_windows: the variants of a chromosome must be contiguous")
+    span = int(1000 * kb)
+    for s, e in zip(starts[:-1], starts[1:]):
+        p = pos[s:e]
+        if (np.diff(p) < 0).any():
+            raise ValueError(f"ld_windows: positions decrease inside chromosome {chrom[s]}")
+        out[s:e] = s + np.searchsorted(p, p + span, side="right")
+    return out
 
 
 def glm_model(phenotype, model: str = "auto"):
@@ -842,6 +889,51 @@ class Dataset:
         if found > len(rows):
             rows, found = self.king_table_capped(min_kinship, found, v_begin, v_end, vidx, subset)
         return rows
+
+    def ld_window_sums(self, v_begin: int | None = None, v_end: int | None = None, vidx=None,
+                       subset: Subset | None = None, a_range=None, b_range=None) -> np.ndarray:
+        """pgh_ld_window_sums: uint32[LD_PLANES][na][nb], ld_pairs' six sums (n, sum_a, sum_b, sum_ab, sum_a2, sum_b2)
+        of the variant pairs a_range x b_range (indices into the call's variants; default: all of them) over a
+        variant range or list."""
+        v0, n, v = self._range_or_list(v_begin, v_end, vidx)
+        a0, a1 = (0, n) if a_range is None else (int(a_range[0]), int(a_range[1]))
+        b0, b1 = (0, n) if b_range is None else (int(b_range[0]), int(b_range[1]))
+        for x in (a0, a1, b0, b1, v0, n):
+            if not 0 <= x <= 0xFFFFFFFF:
+                raise ValueError(f"ld_window_sums: {x} is not an unsigned 32-bit index")
+        out = np.zeros((LD_PLANES, max(0, a1 - a0), max(0, b1 - b0)), dtype=np.uint32)
+        eb = _errbuf()
+        _check(_lib.pgh_ld_window_sums(self._h, subset._h if subset else None, v0, n,
+                                       _ptr(v) if v is not None else None, a0, a1, b0, b1, _ptr(out), eb), eb)
+        return out
+
+    def ld_prune(self, r2: float, win_end=None, window: int | None = None, v_begin: int | None = None,
+                 v_end: int | None = None, vidx=None, subset: Subset | None = None) -> np.ndarray:
+        """pgh_ld_prune: the boolean keep array of greedy pruning at r2 over a variant range or (strictly increasing)
+        list.  Exactly one of win_end (the exclusive end of each variant's window, see ld_windows) and window (W:
+        win_end[k] = min(k + W, n_var)) must be given."""
+        if (win_end is None) == (window is None):
+            raise ValueError("ld_prune: pass exactly one of win_end and window")
+        v0, n, v = self._range_or_list(v_begin, v_end, vidx)
+        for x in (v0, n):
+            if not 0 <= x <= 0xFFFFFFFF:
+                raise ValueError(f"ld_prune: {x} is not an unsigned 32-bit index")
+        if window is not None:
+            if not 1 <= int(window) <= 0xFFFFFFFF:
+                raise ValueError("ld_prune: window must be at least 1")
+            w = np.minimum(np.arange(n, dtype=np.int64) + int(window), n).astype(np.uint32)
+        else:
+            w = np.asarray(win_end)
+            if w.shape != (n,) or (n and (w.min() < 0 or w.max() > 0xFFFFFFFF)):
+                raise ValueError(f"ld_prune: win_end must hold one unsigned 32-bit value per variant ({n})")
+            w = np.ascontiguousarray(w, dtype=np.uint32)
+        keep = np.zeros(n, dtype=np.uint8)
+        kept = C.c_uint64(0)
+        eb = _errbuf()
+        _check(_lib.pgh_ld_prune(self._h, subset._h if subset else None, v0, n, _ptr(v) if v is not None else None,
+                                 _ptr(w), float(r2), _ptr(keep), C.byref(kept), eb), eb)
+        assert int(keep.sum()) == kept.value
+        return keep.astype(bool)
 
     def unpack_samples(self, vidx, subset: Subset | None = None, missing_code: int = -9) -> np.ndarray:
         """int8[n_out][len(vidx)]: the calls sample-major (read_pfile orient := 'sample')."""
