@@ -629,6 +629,43 @@ int pgh_ld_prune(const pgh_dataset *ds, const pgh_subset *subset, uint32_t varia
  * (n <= 2^29 - 1); larger hand-made values may wrap. */
 int pgh_ld_exceeds(const uint32_t sums[6], double r2_threshold);
 
+/* ---- variance-standardised relationship matrix, GRM ------- */
+
+/* Over the output samples (subset order, or raw order without a subset) and the variants of the call, hardcalls only
+ * (dosage and phase tracks are not read).  Per variant v, with het, alt and called counted over the output samples,
+ *   p = double(het + 2 alt) / double(2 called)        or p = freq[v] when the caller supplies freq
+ * and v is SKIPPED when called == 0, or when p is not finite, p <= 0 or p >= 1: it contributes nothing.  For the
+ * other ("used") variants, in this exact sequence of FP64 operations on the host,
+ *   q = 1 - p      s = sqrt((2 p) q)      z[c] = (c - 2 p) / s  for the codes c = 0, 1, 2      z = 0 for a missing call
+ *   nobs_ij = number of used variants at which both i and j are called                          (uint32, exact)
+ *   rel_ij  = (sum over used v of z_iv z_jv) / nobs_ij                                           (NaN when nobs_ij == 0)
+ * With PGH_GRM_MEANIMPUTE the divisor is the number of used variants for every pair (NaN when it is 0).
+ * This is the matrix of plink2 --make-rel / GCTA's GRM; the formulas above are the definition, they have not been
+ * compared with either program's output.  The sum runs on the FP64 matrix cores in the order of the
+ * call's variants: a pair's value does not depend on the rectangle asked for or on which of the two is the row
+ * sample, and the same call returns the same bytes every time.
+ * Takes one dense-resident dataset (not a shard group, not a sparse-resident dataset). */
+enum { PGH_GRM_MEANIMPUTE = 1 };
+#define PGH_GRM_TILE 128 /* sample pairs per workgroup: PGH_GRM_TILE x PGH_GRM_TILE */
+
+/* rel (and nobs, unless NULL): (i_end - i_begin) x (j_end - j_begin), i-major, host memory, for the rectangle of
+ * output-sample pairs [i_begin, i_end) x [j_begin, j_end).  Variants, rectangle and errors as pgh_king_counts:
+ * [variant_begin, variant_begin + n_var), or the n_var entries of vidx when it is not NULL; 1 <= n_var <= 2^31 - 1;
+ * the rectangle may lie anywhere, the diagonal included; an empty or reversed one, or one beyond the output samples,
+ * is PGH_ERR_ARG, and so are unknown flag bits.  freq: NULL, or one frequency per variant of the call.
+ * *n_used (unless NULL) receives the number of variants not skipped.
+ * The rows are walked in bands through device blocks of at most PGH_GRM_BAND_BYTES bytes (environment variable, read at
+ * every call; default and maximum 268435456; a band is never less than PGH_GRM_TILE rows); the result does not depend
+ * on it. */
+int pgh_grm(const pgh_dataset *ds, const pgh_subset *subset, uint32_t variant_begin, uint32_t n_var,
+            const uint32_t *vidx, const double *freq /* NULL or n_var */, uint32_t i_begin, uint32_t i_end,
+            uint32_t j_begin, uint32_t j_end, uint32_t flags, double *rel, uint32_t *nobs /* may be NULL */,
+            uint32_t *n_used /* may be NULL */, char *errbuf);
+
+/* The standardisation above on the host: returns p, or NaN when the variant is skipped; z[0..2] is written only when
+ * it is not (z may be NULL).  pgh_grm's tables are this function of the counts, bit for bit. */
+double pgh_grm_standardize(uint32_t het, uint32_t alt, uint32_t called, double z[3]);
+
 /* ---- HWE exact tests (host) --------------------------------------------- */
 
 /* plink2::HweLnP (src/plink_hardy.cpp:78): ln of the two-sided exact-test p. */

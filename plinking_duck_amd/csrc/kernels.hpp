@@ -131,6 +131,10 @@ hipError_t LaunchCopyCols(const double *src, uint32_t ld_src, double *dst, uint3
 uint64_t TransposedPitch(uint32_t n_var);
 hipError_t LaunchTranspose2bit(const RowView &view, const uint32_t *vlist, uint32_t n_var, uint8_t *out,
                                hipStream_t stream);
+// The same for the raw samples [sample_begin, sample_end) only (sample_begin a multiple of 256): sample s is row
+// s - sample_begin of out, which holds sample_end - sample_begin rows.
+hipError_t LaunchTranspose2bitRange(const RowView &view, const uint32_t *vlist, uint32_t n_var, uint32_t sample_begin,
+                                    uint32_t sample_end, uint8_t *out, hipStream_t stream);
 hipError_t LaunchIota(uint32_t *p, uint32_t n, hipStream_t stream);
 // out[c] = sum_r m[r * stride + c]
 hipError_t LaunchColumnSums(const double *m, uint64_t n_rows, uint32_t stride, uint32_t n_cols, double *out,

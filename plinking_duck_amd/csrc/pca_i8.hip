@@ -18,10 +18,11 @@ namespace {
 
 // 256 variants x 256 samples per workgroup: 256 rows x 64 B in, 256 sample rows x 64 B out, through LDS.
 __global__ __launch_bounds__(256) void k_transpose_2bit(const uint8_t *__restrict__ rows, uint64_t pitch,
-                                                        uint32_t sample_ct, const uint32_t *__restrict__ vlist,
-                                                        uint32_t n_var, uint8_t *__restrict__ out, uint64_t out_pitch) {
+                                                        uint32_t sample_begin, uint32_t sample_ct,
+                                                        const uint32_t *__restrict__ vlist, uint32_t n_var,
+                                                        uint8_t *__restrict__ out, uint64_t out_pitch) {
 	__shared__ __attribute__((aligned(16))) uint8_t s_in[256][64 + 16]; // +16: rows of one byte column spread over banks
-	const uint32_t v0 = blockIdx.y * 256u, s0 = blockIdx.x * 256u;
+	const uint32_t v0 = blockIdx.y * 256u, s0 = sample_begin + blockIdx.x * 256u; // sample_begin: a multiple of 256
 	const uint32_t t = threadIdx.x;
 	const uint64_t in_col = static_cast<uint64_t>(s0 / 4u) + 16u * (t & 3u);
 #pragma unroll
@@ -49,7 +50,7 @@ __global__ __launch_bounds__(256) void k_transpose_2bit(const uint8_t *__restric
 		}
 		w[k] = acc;
 	}
-	uint4 *dst = reinterpret_cast<uint4 *>(out + static_cast<uint64_t>(s) * out_pitch + (v0 / 4u));
+	uint4 *dst = reinterpret_cast<uint4 *>(out + static_cast<uint64_t>(s - sample_begin) * out_pitch + (v0 / 4u));
 #pragma unroll
 	for (uint32_t q = 0; q < 4; q++) {
 		if (v0 / 4u + 16u * q < out_pitch) {
@@ -108,16 +109,25 @@ uint64_t TransposedPitch(uint32_t n_var) {
 
 hipError_t LaunchTranspose2bit(const RowView &view, const uint32_t *vlist, uint32_t n_var, uint8_t *out,
                                hipStream_t stream) {
-	if (n_var == 0 || view.sample_ct == 0) {
+	return LaunchTranspose2bitRange(view, vlist, n_var, 0, view.sample_ct, out, stream);
+}
+
+hipError_t LaunchTranspose2bitRange(const RowView &view, const uint32_t *vlist, uint32_t n_var, uint32_t sample_begin,
+                                    uint32_t sample_end, uint8_t *out, hipStream_t stream) {
+	if (sample_begin % 256u != 0 || sample_end > view.sample_ct) {
+		return hipErrorInvalidValue;
+	}
+	if (n_var == 0 || sample_begin >= sample_end) {
 		return hipSuccess;
 	}
+	const uint32_t count = sample_end - sample_begin;
 	const uint64_t out_pitch = TransposedPitch(n_var);
-	hipError_t e = hipMemsetAsync(out, 0, out_pitch * view.sample_ct, stream);
+	hipError_t e = hipMemsetAsync(out, 0, out_pitch * count, stream);
 	if (e != hipSuccess) {
 		return e;
 	}
-	hipLaunchKernelGGL(k_transpose_2bit, dim3((view.sample_ct + 255) / 256, (n_var + 255) / 256), dim3(256), 0, stream,
-	                   view.rows, view.pitch, view.sample_ct, vlist, n_var, out, out_pitch);
+	hipLaunchKernelGGL(k_transpose_2bit, dim3((count + 255) / 256, (n_var + 255) / 256), dim3(256), 0, stream, view.rows,
+	                   view.pitch, sample_begin, sample_end, vlist, n_var, out, out_pitch);
 	return hipGetLastError();
 }
 

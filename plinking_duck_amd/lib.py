@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "pgh_reader_error", "pgh_open_sparse", "pgh_get_sparse_info", "pgh_sparse_opens_started", "pgh_glm", "pgh_glm_multi", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
     "pgh_king_counts", "pgh_king_table", "pgh_king_kinship",
     "pgh_ld_window_sums", "pgh_ld_prune", "pgh_ld_exceeds",
+    "pgh_grm", "pgh_grm_standardize",
 ]
 
 
@@ -84,6 +85,11 @@ KING_PAIR_DTYPE = np.dtype([("i", "<u4"), ("j", "<u4"), ("nsnp", "<u4"), ("hethe
 LD_N, LD_SUM_A, LD_SUM_B, LD_SUM_AB, LD_SUM_A2, LD_SUM_B2, LD_PLANES = 0, 1, 2, 3, 4, 5, 6
 LD_TILE_A, LD_TILE_B = 96, 128
 LD_PRUNE_CHUNK_ENV = "PGH_LD_PRUNE_CHUNK_TILES"
+# pgh_grm's flag, the kernel's tile of sample pairs (a test of tile edges names it) and the environment variable that
+# lowers the byte budget of a band of rows (results do not depend on it)
+GRM_MEANIMPUTE = 1
+GRM_TILE = 128
+GRM_BAND_ENV = "PGH_GRM_BAND_BYTES"
 GLM_ROW_DTYPE = np.dtype([("beta", "<f8"), ("se", "<f8"), ("stat", "<f8"), ("p", "<f8"), ("a1_freq", "<f8"),
                           ("obs_ct", "<u4"), ("errcode", "u1"), ("firth", "u1"), ("pad", "u1", (2,))])
 
@@ -211,6 +217,8 @@ def _load():
         "pgh_ld_window_sums": (C.c_int, [vp, vp, u32, u32, vp, u32, u32, u32, u32, vp, cp]),
         "pgh_ld_prune": (C.c_int, [vp, vp, u32, u32, vp, vp, C.c_double, vp, C.POINTER(u64), cp]),
         "pgh_ld_exceeds": (C.c_int, [vp, C.c_double]),
+        "pgh_grm": (C.c_int, [vp, vp, u32, u32, vp, vp, u32, u32, u32, u32, u32, vp, vp, C.POINTER(u32), cp]),
+        "pgh_grm_standardize": (C.c_double, [u32, u32, u32, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -258,6 +266,15 @@ def king_kinship(hethet: int, ibs0: int, het1hom2: int, het2hom1: int) -> float:
     """pgh_king_kinship: 0.5 - (4 IBS0 + HET1HOM2 + HET2HOM1) / (4 (HETHET + min(HET1HOM2, HET2HOM1))), NaN when the
     denominator is zero -- the function king_table's kinship column is of its own counts."""
     return _lib.pgh_king_kinship(int(hethet), int(ibs0), int(het1hom2), int(het2hom1))
+
+
+def grm_standardize(het: int, alt: int, called: int):
+    """pgh_grm_standardize: (p, z) with p = (het + 2 alt) / (2 called) and z[c] = (c - 2 p) / sqrt((2 p) (1 - p)) for
+    the codes 0, 1, 2 -- the table pgh_grm builds per variant.  (NaN, None) when the variant is skipped: nothing
+    called, p <= 0 or p >= 1."""
+    z = np.zeros(3, dtype=np.float64)
+    p = _lib.pgh_grm_standardize(int(het), int(alt), int(called), _ptr(z))
+    return (p, None) if p != p else (p, z)
 
 
 def ld_exceeds(sums, r2: float) -> bool:
@@ -889,6 +906,35 @@ class Dataset:
         if found > len(rows):
             rows, found = self.king_table_capped(min_kinship, found, v_begin, v_end, vidx, subset)
         return rows
+
+    def grm(self, v_begin: int | None = None, v_end: int | None = None, vidx=None, subset: Subset | None = None,
+            freq=None, i_range=None, j_range=None, meanimpute: bool = False, want_nobs: bool = True):
+        """pgh_grm: (rel float64[ni][nj], nobs uint32[ni][nj], n_used) -- the variance-standardised relationship
+        matrix of output samples i_range x j_range (default: all of them) over a variant range or list.  rel is the
+        sum over the used variants of z_i z_j divided by nobs (the variants at which both are called), or by n_used
+        with meanimpute; freq: one allele frequency per variant of the call instead of the counted one.  want_nobs=False
+        passes NULL for nobs (a smaller device block and a third less to copy back) and returns None in its place."""
+        n_out = subset.size if subset else self.n_samples
+        i0, i1 = (0, n_out) if i_range is None else (int(i_range[0]), int(i_range[1]))
+        j0, j1 = (0, n_out) if j_range is None else (int(j_range[0]), int(j_range[1]))
+        v0, n, v = self._range_or_list(v_begin, v_end, vidx)
+        for x in (i0, i1, j0, j1, v0, n):
+            if not 0 <= x <= 0xFFFFFFFF:
+                raise ValueError(f"grm: {x} is not an unsigned 32-bit index")
+        f = None
+        if freq is not None:
+            f = np.ascontiguousarray(freq, dtype=np.float64)
+            if f.shape != (n,):
+                raise ValueError(f"grm: freq must hold one frequency per variant of the call ({n})")
+        rel = np.zeros((max(0, i1 - i0), max(0, j1 - j0)), dtype=np.float64)
+        nobs = np.zeros(rel.shape, dtype=np.uint32) if want_nobs else None
+        used = C.c_uint32(0)
+        eb = _errbuf()
+        _check(_lib.pgh_grm(self._h, subset._h if subset else None, v0, n, _ptr(v) if v is not None else None,
+                            _ptr(f) if f is not None else None, i0, i1, j0, j1,
+                            GRM_MEANIMPUTE if meanimpute else 0, _ptr(rel), _ptr(nobs) if want_nobs else None,
+                            C.byref(used), eb), eb)
+        return rel, nobs, int(used.value)
 
     def ld_window_sums(self, v_begin: int | None = None, v_end: int | None = None, vidx=None,
                        subset: Subset | None = None, a_range=None, b_range=None) -> np.ndarray:
