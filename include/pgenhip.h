@@ -629,6 +629,41 @@ int pgh_ld_prune(const pgh_dataset *ds, const pgh_subset *subset, uint32_t varia
  * (n <= 2^29 - 1); larger hand-made values may wrap. */
 int pgh_ld_exceeds(const uint32_t sums[6], double r2_threshold);
 
+/* Windowed LD scores.  With the six sums, num, va and vb of a pair as above,
+ *   defined(a, b)  iff  n >= 2 (n >= 3 with PGH_LDSCORE_UNBIASED) and va > 0 and vb > 0
+ *   r2   = ((double)num * (double)num) / ((double)va * (double)vb)
+ *   term = r2                                           (flags == 0)
+ *   term = r2 - (1.0 - r2) / (double)(n - 2)            (PGH_LDSCORE_UNBIASED: ldsc's adjustment, with the pair's own n)
+ * each statement one IEEE operation.  The pairs of the band are k < u < win_end[k] (win_end as for pgh_ld_prune), and
+ *   self[k]       = 1.0 if defined(k, k) from k's own class counts over the output samples (n = called,
+ *                   sum_a = sum_b = het + 2 hom_alt, sum_ab = sum_a2 = sum_b2 = het + 4 hom_alt), else 0.0
+ *   score[k]      = self[k] + sum of term(k, u) over the defined band pairs (k, u)
+ *                           + sum of term(j, k) over the defined band pairs (j, k)
+ *   n_partners[k] = the number of those defined pairs (self not counted)
+ * so a band pair contributes to both of its variants (for kb windows: the symmetric window |pos_u - pos_k| <= kb),
+ * and a variant that is monomorphic or uncalled over a pair's samples contributes nothing and receives nothing.
+ * Missing calls are handled by pairwise-complete samples, not by mean imputation.  These formulas are the
+ * definition; they have NOT been compared with `ldsc --l2` output (ldsc mean-imputes).
+ *
+ * Order of the sum (no atomics): score[k] starts at self[k]; then the band's tiles of 96 anchors x 128 partners
+ * (origins at multiples of 96 and 128) are taken by anchor tile row ascending, partner tile ascending, and each adds
+ * its 96 row sums to its anchors and then its 128 column sums to its partners; inside a tile the terms are added in a
+ * fixed order that depends only on the position in the tile.  The result is therefore a function of
+ * the variant list, the subset, win_end and flags alone: the same bytes on every run, from any thread, and whatever
+ * PGH_LD_SCORE_CHUNK_TILES (environment variable, read at every call: tiles per launch, default and maximum 32768 =
+ * 84 MiB of device scratch for the partial sums) is.
+ * score: n_var doubles; n_partners: n_var uint32, may be NULL.  Validation is pgh_ld_prune's (win_end, strictly
+ * increasing vidx); flag bits other than PGH_LDSCORE_UNBIASED are PGH_ERR_ARG.  One dense-resident dataset. */
+enum { PGH_LDSCORE_UNBIASED = 1 };
+int pgh_ld_scores(const pgh_dataset *ds, const pgh_subset *subset, uint32_t variant_begin, uint32_t n_var,
+                  const uint32_t *vidx, const uint32_t *win_end, uint32_t flags, double *score, uint32_t *n_partners,
+                  char *errbuf);
+
+/* "term" above on the host, of sums = {n, sum_a, sum_b, sum_ab, sum_a2, sum_b2}: returns 1 and stores *term when the
+ * pair is defined, else 0 (also for unknown flag bits).  The device evaluates the same function of the same sums, bit
+ * for bit. */
+int pgh_ld_r2(const uint32_t sums[6], uint32_t flags, double *term);
+
 /* ---- variance-standardised relationship matrix, GRM ------- */
 
 /* Over the output samples (subset order, or raw order without a subset) and the variants of the call, hardcalls only

@@ -1,5 +1,6 @@
-// api_ldband.cpp -- pgh_ld_window_sums / pgh_ld_prune / pgh_ld_exceeds: the six r2 sums of a rectangle of variant
-// pairs, and greedy LD pruning over a band of them (kernel in ldband.hip, formula in ld_math.hpp).
+// api_ldband.cpp -- pgh_ld_window_sums / pgh_ld_prune / pgh_ld_exceeds / pgh_ld_scores / pgh_ld_r2: the six r2 sums
+// of a rectangle of variant pairs, greedy LD pruning over a band of them, and the LD score of every variant of a band
+// (kernel in ldband.hip, formulas in ld_math.hpp).
 #include "api_internal.hpp"
 #include "ld_math.hpp"
 #include "ldband.hpp"
@@ -7,6 +8,7 @@
 #include <cstdlib>
 
 static_assert(PGH_LD_PLANES == pgh::kLdPlanes, "plane count");
+static_assert(PGH_LDSCORE_UNBIASED == pgh::kLdScoreUnbiased, "flag value");
 
 namespace {
 
@@ -14,6 +16,8 @@ constexpr uint32_t kLdMaxVariants = 0x7fffffffu;        // tile origins + tile s
 constexpr size_t kSumsBandBytes = 256ull << 20;          // device block of one band of pgh_ld_window_sums' rows
 constexpr uint32_t kPruneChunkTiles = 32768;             // tiles per launch of pgh_ld_prune: 48 MiB of band bits
 constexpr const char *kPruneChunkEnv = "PGH_LD_PRUNE_CHUNK_TILES";
+constexpr uint32_t kScoreChunkTiles = 32768;             // tiles per launch of pgh_ld_scores: 84 MiB of partial sums
+constexpr const char *kScoreChunkEnv = "PGH_LD_SCORE_CHUNK_TILES";
 
 // The call's operand: the local row of each of its variants, on `st`.
 struct LdCall {
@@ -74,16 +78,30 @@ int Prepare(const pgh_dataset *ds, const pgh_subset *subset, uint32_t variant_be
 	return PGH_OK;
 }
 
-uint32_t PruneChunkTiles() {
-	const char *s = std::getenv(kPruneChunkEnv);
+// tiles per launch: the environment variable when it holds a number of at least 1, capped at `most`
+uint32_t ChunkTiles(const char *env, uint32_t most) {
+	const char *s = std::getenv(env);
 	if (s && *s) {
 		char *end = nullptr;
 		const unsigned long long v = std::strtoull(s, &end, 10);
 		if (end && *end == '\0' && v >= 1) {
-			return static_cast<uint32_t>(std::min<unsigned long long>(v, kPruneChunkTiles));
+			return static_cast<uint32_t>(std::min<unsigned long long>(v, most));
 		}
 	}
-	return kPruneChunkTiles;
+	return most;
+}
+
+int CheckWindows(const uint32_t *win_end, uint32_t n_var, char *errbuf) {
+	for (uint32_t k = 0; k < n_var; k++) {
+		if (win_end[k] <= k || win_end[k] > n_var || (k && win_end[k] < win_end[k - 1])) {
+			char msg[200];
+			std::snprintf(msg, sizeof msg, "win_end[%u] = %u: need k < win_end[k] <= n_var (%u), not decreasing in k", k,
+			              win_end[k], n_var);
+			SetErr(errbuf, msg);
+			return PGH_ERR_ARG;
+		}
+	}
+	return PGH_OK;
 }
 
 // The tiles of anchor tile row ta that meet the band: partner tiles [first, first + count)
@@ -192,14 +210,9 @@ extern "C" int pgh_ld_prune(const pgh_dataset *ds, const pgh_subset *subset, uin
 		SetErr(errbuf, "r2_threshold must be a finite number in [0, 1]");
 		return PGH_ERR_ARG;
 	}
-	for (uint32_t k = 0; k < n_var; k++) {
-		if (win_end[k] <= k || win_end[k] > n_var || (k && win_end[k] < win_end[k - 1])) {
-			char msg[200];
-			std::snprintf(msg, sizeof msg, "win_end[%u] = %u: need k < win_end[k] <= n_var (%u), not decreasing in k", k,
-			              win_end[k], n_var);
-			SetErr(errbuf, msg);
-			return PGH_ERR_ARG;
-		}
+	rc = CheckWindows(win_end, n_var, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
 	}
 	hipStream_t st = PghThreadStream();
 	LdCall call;
@@ -234,7 +247,7 @@ extern "C" int pgh_ld_prune(const pgh_dataset *ds, const pgh_subset *subset, uin
 
 	// Launches of at most `chunk` band tiles in (anchor tile row, partner tile) order; a tile row's bits are pruned
 	// over once all of its tiles are back.  keep[] depends only on the bits, never on where the launches were cut.
-	const uint32_t chunk = PruneChunkTiles();
+	const uint32_t chunk = ChunkTiles(kPruneChunkEnv, kPruneChunkTiles);
 	const uint32_t tile_rows = (n_var + pgh::kLdTileA - 1) / pgh::kLdTileA;
 	std::memset(keep, 1, n_var);
 	std::vector<pgh::LdTile> tiles;
@@ -309,6 +322,136 @@ extern "C" int pgh_ld_prune(const pgh_dataset *ds, const pgh_subset *subset, uin
 			kept += keep[k];
 		}
 		*n_kept = kept;
+	}
+	return PGH_OK;
+}
+
+extern "C" int pgh_ld_r2(const uint32_t sums[6], uint32_t flags, double *term) {
+	double v = 0.0;
+	if (!sums || (flags & ~static_cast<uint32_t>(PGH_LDSCORE_UNBIASED)) ||
+	    !pgh::LdR2Term(sums[0], sums[1], sums[2], sums[3], sums[4], sums[5], flags, &v)) {
+		return 0;
+	}
+	if (term) {
+		*term = v;
+	}
+	return 1;
+}
+
+extern "C" int pgh_ld_scores(const pgh_dataset *ds, const pgh_subset *subset, uint32_t variant_begin, uint32_t n_var,
+                             const uint32_t *vidx, const uint32_t *win_end, uint32_t flags, double *score,
+                             uint32_t *n_partners, char *errbuf) {
+	if (!ds || !win_end || !score) {
+		SetErr(errbuf, "null argument");
+		return PGH_ERR_ARG;
+	}
+	PGH_ONE_DEVICE(ds);
+	PGH_DENSE_ROWS(ds);
+	PGH_ENTER(ds);
+	int rc = CheckSubset(ds, subset, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
+	}
+	if (flags & ~static_cast<uint32_t>(PGH_LDSCORE_UNBIASED)) {
+		SetErr(errbuf, "unknown flag bits (PGH_LDSCORE_UNBIASED is the only flag)");
+		return PGH_ERR_ARG;
+	}
+	rc = CheckWindows(win_end, n_var, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
+	}
+	hipStream_t st = PghThreadStream();
+	LdCall call;
+	rc = Prepare(ds, subset, variant_begin, n_var, vidx, true, st, call, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
+	}
+	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct;
+
+	// self terms from the class tallies: a variant against itself has r2 = 1 wherever it has an r2 at all
+	std::vector<uint32_t> partners(n_var, 0u);
+	DevBuf d_win;
+	{
+		DevBuf d_counts;
+		std::vector<uint32_t> counts(static_cast<size_t>(n_var) * 4);
+		PGH_HIP(d_counts.Alloc(counts.size() * sizeof(uint32_t)), "hipMalloc(ld scores counts)");
+		PGH_HIP(pgh::LaunchCounts(call.op.view, 0, call.op.list, n_var, call.op.mask2, n_out, d_counts.As<uint32_t>(), st),
+		        "counts kernel");
+		PGH_HIP(hipMemcpyAsync(counts.data(), d_counts.p, counts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st),
+		        "ld scores counts copy");
+		PGH_HIP(d_win.Alloc(sizeof(uint32_t) * static_cast<size_t>(n_var)), "hipMalloc(ld scores windows)");
+		PGH_HIP(hipMemcpyAsync(d_win.p, win_end, sizeof(uint32_t) * static_cast<size_t>(n_var), hipMemcpyHostToDevice, st),
+		        "ld scores windows upload");
+		PGH_HIP(hipStreamSynchronize(st), "ld scores sync"); // the caller's win_end is read before the call returns
+		for (uint32_t k = 0; k < n_var; k++) {
+			const uint32_t *c = &counts[4 * static_cast<size_t>(k)];
+			const uint32_t called = c[0] + c[1] + c[2], s1 = c[1] + 2 * c[2], s2 = c[1] + 4 * c[2];
+			double self = 0.0;
+			score[k] = pgh::LdR2Term(called, s1, s1, s2, s2, s2, flags, &self) ? 1.0 : 0.0;
+		}
+	}
+
+	// Launches of at most `chunk` band tiles in (anchor tile row, partner tile) order.  Each tile's 96 row sums go to
+	// its anchors and then its 128 column sums to its partners, tile after tile in that order: the result is a function
+	// of the tile list alone, never of where the launches were cut.
+	const uint32_t chunk = ChunkTiles(kScoreChunkEnv, kScoreChunkTiles);
+	const uint32_t tile_rows = (n_var + pgh::kLdTileA - 1) / pgh::kLdTileA;
+	constexpr uint32_t kSlots = pgh::kLdTileScoreSlots;
+	std::vector<pgh::LdTile> tiles;
+	std::vector<double> part;
+	std::vector<uint32_t> cnt;
+	tiles.reserve(chunk);
+	HostSourceFence fence(st); // `tiles` feeds asynchronous uploads
+	DevBuf d_tiles, d_part, d_cnt;
+	PGH_HIP(d_tiles.Alloc(sizeof(pgh::LdTile) * static_cast<size_t>(chunk)), "hipMalloc(ld scores tiles)");
+	PGH_HIP(d_part.Alloc(sizeof(double) * kSlots * static_cast<size_t>(chunk)), "hipMalloc(ld scores partial sums)");
+	PGH_HIP(d_cnt.Alloc(sizeof(uint32_t) * kSlots * static_cast<size_t>(chunk)), "hipMalloc(ld scores partial counts)");
+	uint32_t next_row = 0, next_tile = 0; // the next tile to launch: tile next_tile of tile row next_row
+	while (next_row < tile_rows) {
+		tiles.clear();
+		while (next_row < tile_rows && tiles.size() < chunk) {
+			const BandRow row = RowTiles(next_row, n_var, win_end);
+			while (next_tile < row.count && tiles.size() < chunk) {
+				tiles.push_back(pgh::LdTile {next_row * pgh::kLdTileA, (row.first + next_tile) * pgh::kLdTileB});
+				next_tile++;
+			}
+			if (next_tile == row.count) {
+				next_row++;
+				next_tile = 0;
+			}
+		}
+		if (tiles.empty()) {
+			continue;
+		}
+		const size_t slots = tiles.size() * kSlots;
+		part.resize(slots);
+		cnt.resize(slots);
+		PGH_HIP(hipMemcpyAsync(d_tiles.p, tiles.data(), sizeof(pgh::LdTile) * tiles.size(), hipMemcpyHostToDevice, st),
+		        "ld scores tiles upload");
+		PGH_HIP(pgh::LaunchLdBandScores(call.op, d_tiles.As<pgh::LdTile>(), static_cast<uint32_t>(tiles.size()),
+		                                d_win.As<uint32_t>(), flags, d_part.As<double>(), d_cnt.As<uint32_t>(), st),
+		        "ld band kernel");
+		PGH_HIP(hipMemcpyAsync(part.data(), d_part.p, sizeof(double) * slots, hipMemcpyDeviceToHost, st),
+		        "ld scores partial sums copy");
+		PGH_HIP(hipMemcpyAsync(cnt.data(), d_cnt.p, sizeof(uint32_t) * slots, hipMemcpyDeviceToHost, st),
+		        "ld scores partial counts copy");
+		PGH_HIP(hipStreamSynchronize(st), "ld scores sync");
+		for (size_t ti = 0; ti < tiles.size(); ti++) {
+			const double *p = &part[ti * kSlots];
+			const uint32_t *c = &cnt[ti * kSlots];
+			const uint64_t a0 = tiles[ti].a0, b0 = tiles[ti].b0;
+			for (uint32_t r = 0; r < pgh::kLdTileA && a0 + r < n_var; r++) {
+				score[a0 + r] += p[r];
+				partners[a0 + r] += c[r];
+			}
+			for (uint32_t j = 0; j < pgh::kLdTileB && b0 + j < n_var; j++) {
+				score[b0 + j] += p[pgh::kLdTileA + j];
+				partners[b0 + j] += c[pgh::kLdTileA + j];
+			}
+		}
+	}
+	if (n_partners) {
+		std::memcpy(n_partners, partners.data(), sizeof(uint32_t) * static_cast<size_t>(n_var));
 	}
 	return PGH_OK;
 }

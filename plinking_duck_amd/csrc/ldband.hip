@@ -1,5 +1,5 @@
-// ldband.hip -- the six r2 sums of variant pairs on the int8 matrix cores (pgh_ld_window_sums / pgh_ld_prune;
-// DESIGN.md 3.13).
+// ldband.hip -- the six r2 sums of variant pairs on the int8 matrix cores (pgh_ld_window_sums / pgh_ld_prune /
+// pgh_ld_scores).
 //
 // For two variants a and b the sums over the samples at which both are called are sums over samples of products of
 // per-variant planes, so a tile of variant pairs is a Gram-like product of plane matrices.  Three int8 planes are
@@ -27,6 +27,13 @@
 // a 128 x 128 tile would need 192 of the 256 a wave has at two waves per SIMD).  Two LDS buffers, one barrier per
 // K-step: step k + 1 is loaded before, and expanded after, step k's products.
 // The tiles of a launch come from a list, so only the tiles that meet the band k < u < win_end[k] are run.
+//
+// Three epilogues on the one main loop (template MODE): the six sums of a rectangle (kSums), one "exceeds" bit per
+// band pair (kBits), and the per-row and per-column sums of the band pairs' r2 terms (kScores).  The last adds in a
+// fixed order, a function of the position in the tile alone -- rows: a lane's two partner blocks, a butterfly over the
+// 16 lanes of its row group (xor 1, 2, 4, 8), then the four wc waves in wc order through LDS; columns: a lane's 12
+// rows (block, then register), xor 16, xor 32, then the two wr waves -- so a tile's 224 sums are the same bits on
+// every run.  s_ops is free for this after the loop's last barrier.
 #include "device_utils.hpp"
 #include "ld_math.hpp"
 #include "ldband.hpp"
@@ -47,6 +54,9 @@ constexpr uint32_t kLdsBytes = 2u * kBufBytes;                // double buffered
 constexpr uint32_t kWaveA = 3, kWaveB = 2;                    // 16-row blocks of a wave's tile
 static_assert(2u * kWaveA == kBlocksA && 4u * kWaveB == kBlocksB, "2 x 4 waves cover the tile");
 static_assert(kWaveB * 16u == 32u, "one bit word per wave and anchor row");
+static_assert(kLdTileScoreSlots <= kThreads, "one thread per slot writes a tile's score partials");
+
+enum LdMode : int { kSums = 0, kBits = 1, kScores = 2 };
 
 struct LdBandArgs {
 	const uint8_t *rows;
@@ -63,6 +73,10 @@ struct LdBandArgs {
 	const uint32_t *win_end;
 	double threshold;
 	uint32_t *bits;
+	// scores (win_end as for bits)
+	double *part;
+	uint32_t *cnt;
+	uint32_t flags;
 };
 
 // 16 codes (one 4-byte word) -> 16 int8 of each plane
@@ -88,8 +102,9 @@ __device__ __forceinline__ uint32_t MaskTail(uint32_t w, uint32_t first, uint32_
 	return left >= 16u ? w : (w | (0xffffffffu << (2u * left)));
 }
 
-template <bool BITS>
+template <int MODE>
 __global__ __launch_bounds__(kThreads) void k_ld_band(const LdBandArgs a) {
+	constexpr bool BITS = MODE == kBits, SCORES = MODE == kScores;
 	extern __shared__ __attribute__((aligned(16))) uint8_t s_ops[];
 	const LdTile tile = a.tiles[blockIdx.x];
 	const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
@@ -193,6 +208,18 @@ __global__ __launch_bounds__(kThreads) void k_ld_band(const LdBandArgs a) {
 
 	// ---- epilogue: lane holds column (lane & 15), rows 4 (lane >> 4) + reg of each 16 x 16 block ----
 	const uint32_t nb_out = a.b_end - a.b_begin;
+	// scores: the waves' row and column partials meet in LDS (the operands are done with: the loop ends on a barrier)
+	double *s_row = reinterpret_cast<double *>(s_ops);                          // [4 wc][kLdTileA]
+	double *s_col = s_row + 4u * kLdTileA;                                      // [2 wr][kLdTileB]
+	uint32_t *s_rown = reinterpret_cast<uint32_t *>(s_col + 2u * kLdTileB);     // [4 wc][kLdTileA]
+	uint32_t *s_coln = s_rown + 4u * kLdTileA;                                  // [2 wr][kLdTileB]
+	double col[kWaveB];
+	uint32_t coln[kWaveB];
+#pragma unroll
+	for (uint32_t y = 0; y < kWaveB; y++) {
+		col[y] = 0.0;
+		coln[y] = 0u;
+	}
 #pragma unroll
 	for (uint32_t x = 0; x < kWaveA; x++) {
 #pragma unroll
@@ -200,17 +227,18 @@ __global__ __launch_bounds__(kThreads) void k_ld_band(const LdBandArgs a) {
 			const uint32_t row = wr * (kWaveA * 16u) + x * 16u + (lane >> 4) * 4u + reg; // of the tile
 			const uint32_t k = tile.a0 + row;
 			uint32_t k_end = 0; // partners of k: (k, k_end)
-			if (BITS && k < a.n_var) {
+			if ((BITS || SCORES) && k < a.n_var) {
 				k_end = a.win_end[k];
 			}
 			unsigned long long votes[kWaveB];
+			double terms[kWaveB];
 #pragma unroll
 			for (uint32_t y = 0; y < kWaveB; y++) {
 				const uint32_t u = tile.b0 + wc * (kWaveB * 16u) + y * 16u + (lane & 15u);
 				const uint32_t n = static_cast<uint32_t>(acc[x][y][0][reg]), sa = static_cast<uint32_t>(acc[x][y][1][reg]);
 				const uint32_t sb = static_cast<uint32_t>(acc[x][y][2][reg]), sab = static_cast<uint32_t>(acc[x][y][3][reg]);
 				const uint32_t sa2 = static_cast<uint32_t>(acc[x][y][4][reg]), sb2 = static_cast<uint32_t>(acc[x][y][5][reg]);
-				if (!BITS) {
+				if (MODE == kSums) {
 					if (k >= a.a_begin && k < a.a_end && u >= a.b_begin && u < a.b_end) {
 						uint32_t *o = a.out + static_cast<uint64_t>(k - a.a_begin) * nb_out + (u - a.b_begin);
 						o[0] = n;
@@ -220,9 +248,16 @@ __global__ __launch_bounds__(kThreads) void k_ld_band(const LdBandArgs a) {
 						o[4 * a.plane_stride] = sa2;
 						o[5 * a.plane_stride] = sb2;
 					}
-				} else {
+				} else if (BITS) {
 					const bool pass = u > k && u < k_end && LdExceeds(n, sa, sb, sab, sa2, sb2, a.threshold);
 					votes[y] = __ballot(pass);
+				} else {
+					double term = 0.0;
+					const bool counts = u > k && u < k_end && LdR2Term(n, sa, sb, sab, sa2, sb2, a.flags, &term);
+					terms[y] = counts ? term : 0.0;
+					votes[y] = __ballot(counts);
+					col[y] += terms[y];
+					coln[y] += counts ? 1u : 0u;
 				}
 			}
 			if (BITS && lane < 4u) {
@@ -232,21 +267,69 @@ __global__ __launch_bounds__(kThreads) void k_ld_band(const LdBandArgs a) {
 				const uint32_t my_row = wr * (kWaveA * 16u) + x * 16u + lane * 4u + reg;
 				a.bits[(static_cast<uint64_t>(blockIdx.x) * kLdTileA + my_row) * (kLdTileB / 32u) + wc] = lo | (hi << 16);
 			}
+			if (SCORES) {
+				// this wave's 32 partners of the lane's row: the two blocks, then the 16 lanes of the row group
+				double rs = terms[0] + terms[1];
+#pragma unroll
+				for (int m = 1; m < 16; m <<= 1) {
+					rs += __shfl_xor(rs, m);
+				}
+				if ((lane & 15u) == 0u) {
+					const uint32_t sh = 16u * (lane >> 4);
+					s_row[wc * kLdTileA + row] = rs;
+					s_rown[wc * kLdTileA + row] = __popc(static_cast<uint32_t>(votes[0] >> sh) & 0xffffu) +
+					                              __popc(static_cast<uint32_t>(votes[1] >> sh) & 0xffffu);
+				}
+			}
+		}
+	}
+	if (SCORES) {
+		// this wave's 48 anchors of the lane's columns: the 12 of the lane are in col[], then the four row groups
+#pragma unroll
+		for (uint32_t y = 0; y < kWaveB; y++) {
+			double cs = col[y];
+			uint32_t cn = coln[y];
+			cs += __shfl_xor(cs, 16);
+			cn += __shfl_xor(cn, 16);
+			cs += __shfl_xor(cs, 32);
+			cn += __shfl_xor(cn, 32);
+			if (lane < 16u) {
+				const uint32_t c = wc * (kWaveB * 16u) + y * 16u + lane;
+				s_col[wr * kLdTileB + c] = cs;
+				s_coln[wr * kLdTileB + c] = cn;
+			}
+		}
+		__syncthreads();
+		const uint64_t slot0 = static_cast<uint64_t>(blockIdx.x) * kLdTileScoreSlots;
+		if (t < kLdTileA) {
+			double v = s_row[t];
+			uint32_t c = s_rown[t];
+#pragma unroll
+			for (uint32_t w = 1; w < 4u; w++) {
+				v += s_row[w * kLdTileA + t];
+				c += s_rown[w * kLdTileA + t];
+			}
+			a.part[slot0 + t] = v;
+			a.cnt[slot0 + t] = c;
+		} else if (t < kLdTileScoreSlots) {
+			const uint32_t c = t - kLdTileA;
+			a.part[slot0 + t] = s_col[c] + s_col[kLdTileB + c];
+			a.cnt[slot0 + t] = s_coln[c] + s_coln[kLdTileB + c];
 		}
 	}
 }
 
-template <bool BITS>
+template <int MODE>
 hipError_t Launch(const LdBandArgs &a, uint32_t n_tiles, hipStream_t stream) {
 	if (n_tiles == 0) {
 		return hipSuccess;
 	}
-	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_ld_band<BITS>),
+	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_ld_band<MODE>),
 	                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBytes));
 	if (e != hipSuccess) {
 		return e;
 	}
-	hipLaunchKernelGGL(k_ld_band<BITS>, dim3(n_tiles), dim3(kThreads), kLdsBytes, stream, a);
+	hipLaunchKernelGGL(k_ld_band<MODE>, dim3(n_tiles), dim3(kThreads), kLdsBytes, stream, a);
 	return hipGetLastError();
 }
 
@@ -277,7 +360,7 @@ hipError_t LaunchLdBandSums(const LdBandOperand &op, const LdTile *tiles, uint32
 	a.b_end = b_end;
 	a.out = out;
 	a.plane_stride = static_cast<uint64_t>(a_end - a_begin) * (b_end - b_begin);
-	return Launch<false>(a, n_tiles, stream);
+	return Launch<kSums>(a, n_tiles, stream);
 }
 
 hipError_t LaunchLdBandBits(const LdBandOperand &op, const LdTile *tiles, uint32_t n_tiles, const uint32_t *win_end,
@@ -291,7 +374,22 @@ hipError_t LaunchLdBandBits(const LdBandOperand &op, const LdTile *tiles, uint32
 	a.win_end = win_end;
 	a.threshold = threshold;
 	a.bits = bits;
-	return Launch<true>(a, n_tiles, stream);
+	return Launch<kBits>(a, n_tiles, stream);
+}
+
+hipError_t LaunchLdBandScores(const LdBandOperand &op, const LdTile *tiles, uint32_t n_tiles, const uint32_t *win_end,
+                              uint32_t flags, double *part, uint32_t *cnt, hipStream_t stream) {
+	if (op.n_var == 0 || op.view.sample_ct > kLdBandMaxSamples) {
+		return hipErrorInvalidValue;
+	}
+	LdBandArgs a = Common(op, tiles);
+	a.a_end = op.n_var;
+	a.b_end = op.n_var;
+	a.win_end = win_end;
+	a.flags = flags;
+	a.part = part;
+	a.cnt = cnt;
+	return Launch<kScores>(a, n_tiles, stream);
 }
 
 } // namespace pgh

@@ -35,7 +35,7 @@ EXPORTED_SYMBOLS = [
     "pgh_tally_sample_missing", "pgh_tally_destroy", "pgh_tally_passes_started", "pgh_host_alloc", "pgh_host_free", "pgh_trim_device_cache",
     "pgh_reader_error", "pgh_open_sparse", "pgh_get_sparse_info", "pgh_sparse_opens_started", "pgh_glm", "pgh_glm_multi", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
     "pgh_king_counts", "pgh_king_table", "pgh_king_kinship",
-    "pgh_ld_window_sums", "pgh_ld_prune", "pgh_ld_exceeds",
+    "pgh_ld_window_sums", "pgh_ld_prune", "pgh_ld_exceeds", "pgh_ld_scores", "pgh_ld_r2",
     "pgh_grm", "pgh_grm_standardize",
 ]
 
@@ -85,6 +85,9 @@ KING_PAIR_DTYPE = np.dtype([("i", "<u4"), ("j", "<u4"), ("nsnp", "<u4"), ("hethe
 LD_N, LD_SUM_A, LD_SUM_B, LD_SUM_AB, LD_SUM_A2, LD_SUM_B2, LD_PLANES = 0, 1, 2, 3, 4, 5, 6
 LD_TILE_A, LD_TILE_B = 96, 128
 LD_PRUNE_CHUNK_ENV = "PGH_LD_PRUNE_CHUNK_TILES"
+# pgh_ld_scores' flag and the environment variable that sets its launch size in tiles (results do not depend on it)
+LDSCORE_UNBIASED = 1
+LD_SCORE_CHUNK_ENV = "PGH_LD_SCORE_CHUNK_TILES"
 # pgh_grm's flag, the kernel's tile of sample pairs (a test of tile edges names it) and the environment variable that
 # lowers the byte budget of a band of rows (results do not depend on it)
 GRM_MEANIMPUTE = 1
@@ -217,6 +220,8 @@ def _load():
         "pgh_ld_window_sums": (C.c_int, [vp, vp, u32, u32, vp, u32, u32, u32, u32, vp, cp]),
         "pgh_ld_prune": (C.c_int, [vp, vp, u32, u32, vp, vp, C.c_double, vp, C.POINTER(u64), cp]),
         "pgh_ld_exceeds": (C.c_int, [vp, C.c_double]),
+        "pgh_ld_scores": (C.c_int, [vp, vp, u32, u32, vp, vp, u32, vp, vp, cp]),
+        "pgh_ld_r2": (C.c_int, [vp, u32, C.POINTER(C.c_double)]),
         "pgh_grm": (C.c_int, [vp, vp, u32, u32, vp, vp, u32, u32, u32, u32, u32, vp, vp, C.POINTER(u32), cp]),
         "pgh_grm_standardize": (C.c_double, [u32, u32, u32, vp]),
     }
@@ -286,6 +291,19 @@ def ld_exceeds(sums, r2: float) -> bool:
     if s.shape != (6,):
         raise ValueError(f"ld_exceeds: six sums expected, got shape {s.shape}")
     return bool(_lib.pgh_ld_exceeds(_ptr(s), float(r2)))
+
+
+def ld_r2(sums, unbiased: bool = False):
+    """pgh_ld_r2: the term a pair with sums = (n, sum_a, sum_b, sum_ab, sum_a2, sum_b2) adds to an LD score, or None
+    when the pair has no r2 (n < 2, or n < 3 with unbiased; va <= 0 or vb <= 0).  r2 = (float(num) * float(num)) /
+    (float(va) * float(vb)) as in ld_exceeds; unbiased: r2 - (1.0 - r2) / float(n - 2).  The function ld_scores
+    applies to every pair of its band."""
+    s = np.ascontiguousarray(sums, dtype=np.uint32)
+    if s.shape != (6,):
+        raise ValueError(f"ld_r2: six sums expected, got shape {s.shape}")
+    term = C.c_double(0.0)
+    ok = _lib.pgh_ld_r2(_ptr(s), LDSCORE_UNBIASED if unbiased else 0, C.byref(term))
+    return term.value if ok else None
 
 
 def ld_windows(chrom, pos, kb: float) -> np.ndarray:
@@ -953,26 +971,31 @@ class Dataset:
                                        _ptr(v) if v is not None else None, a0, a1, b0, b1, _ptr(out), eb), eb)
         return out
 
+    def _ld_band_args(self, who, win_end, window, v_begin, v_end, vidx):
+        """The argument checks ld_prune and ld_scores share: (variant_begin, n_var, vidx or None, win_end)."""
+        if (win_end is None) == (window is None):
+            raise ValueError(f"{who}: pass exactly one of win_end and window")
+        v0, n, v = self._range_or_list(v_begin, v_end, vidx)
+        for x in (v0, n):
+            if not 0 <= x <= 0xFFFFFFFF:
+                raise ValueError(f"{who}: {x} is not an unsigned 32-bit index")
+        if window is not None:
+            if not 1 <= int(window) <= 0xFFFFFFFF:
+                raise ValueError(f"{who}: window must be at least 1")
+            w = np.minimum(np.arange(n, dtype=np.int64) + int(window), n).astype(np.uint32)
+        else:
+            w = np.asarray(win_end)
+            if w.shape != (n,) or (n and (w.min() < 0 or w.max() > 0xFFFFFFFF)):
+                raise ValueError(f"{who}: win_end must hold one unsigned 32-bit value per variant ({n})")
+            w = np.ascontiguousarray(w, dtype=np.uint32)
+        return v0, n, v, w
+
     def ld_prune(self, r2: float, win_end=None, window: int | None = None, v_begin: int | None = None,
                  v_end: int | None = None, vidx=None, subset: Subset | None = None) -> np.ndarray:
         """pgh_ld_prune: the boolean keep array of greedy pruning at r2 over a variant range or (strictly increasing)
         list.  Exactly one of win_end (the exclusive end of each variant's window, see ld_windows) and window (W:
         win_end[k] = min(k + W, n_var)) must be given."""
-        if (win_end is None) == (window is None):
-            raise ValueError("ld_prune: pass exactly one of win_end and window")
-        v0, n, v = self._range_or_list(v_begin, v_end, vidx)
-        for x in (v0, n):
-            if not 0 <= x <= 0xFFFFFFFF:
-                raise ValueError(f"ld_prune: {x} is not an unsigned 32-bit index")
-        if window is not None:
-            if not 1 <= int(window) <= 0xFFFFFFFF:
-                raise ValueError("ld_prune: window must be at least 1")
-            w = np.minimum(np.arange(n, dtype=np.int64) + int(window), n).astype(np.uint32)
-        else:
-            w = np.asarray(win_end)
-            if w.shape != (n,) or (n and (w.min() < 0 or w.max() > 0xFFFFFFFF)):
-                raise ValueError(f"ld_prune: win_end must hold one unsigned 32-bit value per variant ({n})")
-            w = np.ascontiguousarray(w, dtype=np.uint32)
+        v0, n, v, w = self._ld_band_args("ld_prune", win_end, window, v_begin, v_end, vidx)
         keep = np.zeros(n, dtype=np.uint8)
         kept = C.c_uint64(0)
         eb = _errbuf()
@@ -980,6 +1003,19 @@ class Dataset:
                                  _ptr(w), float(r2), _ptr(keep), C.byref(kept), eb), eb)
         assert int(keep.sum()) == kept.value
         return keep.astype(bool)
+
+    def ld_scores(self, win_end=None, window: int | None = None, unbiased: bool = False, want_counts: bool = False,
+                  v_begin: int | None = None, v_end: int | None = None, vidx=None, subset: Subset | None = None):
+        """pgh_ld_scores: float64[n_var], the LD score of every variant of a range or (strictly increasing) list:
+        its self term plus ld_r2 of every defined pair of the band k < u < win_end[k] it belongs to, as anchor or as
+        partner.  win_end / window as in ld_prune.  want_counts: (scores, uint32[n_var] defined partners)."""
+        v0, n, v, w = self._ld_band_args("ld_scores", win_end, window, v_begin, v_end, vidx)
+        score = np.zeros(n, dtype=np.float64)
+        partners = np.zeros(n, dtype=np.uint32) if want_counts else None
+        eb = _errbuf()
+        _check(_lib.pgh_ld_scores(self._h, subset._h if subset else None, v0, n, _ptr(v) if v is not None else None,
+                                  _ptr(w), LDSCORE_UNBIASED if unbiased else 0, _ptr(score), _ptr(partners), eb), eb)
+        return (score, partners) if want_counts else score
 
     def unpack_samples(self, vidx, subset: Subset | None = None, missing_code: int = -9) -> np.ndarray:
         """int8[n_out][len(vidx)]: the calls sample-major (read_pfile orient := 'sample')."""
