@@ -527,6 +527,19 @@ int pgh_glm(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, u
 int pgh_glm_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                   uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
                   int model, int firth, pgh_glm_row *out, char *errbuf);
+/* pgh_glm's LINEAR fit for the variants [v_begin, v_end) of a SPARSE-RESIDENT dataset (pgh_open_sparse),
+ * from the variants' entries: cost proportional to the samples that differ from a variant's base code.
+ * Hardcalls only (pgh_open_sparse steps over dosage tracks).  Arguments, row layout, error codes and argument
+ * checks are pgh_glm's.  A dataset that is not sparse-resident is PGH_ERR_ARG
+ * ("needs a sparse-resident dataset").
+ * A row has pgh_glm's errcode, obs_ct and a1_freq for the same file bit for bit, and estimates that agree to
+ * rounding (its sums are accumulated over the entries, in another order); the rows of variants held in the dense
+ * form (pgh_sparse_info.dense_variant_ct) are pgh_glm's bit for bit.  A row is a function of its variant's entries,
+ * the phenotype, the covariates and the subset only: not of v_begin, the chunk or the rows around it, and the same
+ * call returns the same bytes every time.  Logistic and Firth fits over a sparse-resident dataset are not offered. */
+int pgh_glm_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                   const double *phenotype, uint32_t n_covar, const double *covariates,
+                   pgh_glm_row *out, char *errbuf);
 /* two-sided p of Student's t with df degrees of freedom (the reference's TstatToPvalue) */
 double pgh_glm_p_from_t(double t, double df);
 /* two-sided p of a standard normal z (ZstatToPvalue) */

@@ -1,5 +1,6 @@
 // api_glm.cpp -- pgh_glm: plink_glm's per-variant linear / logistic / Firth regressions (glm.hip) behind the C ABI;
-// pgh_glm_multi: the same for many phenotypes in one call.
+// pgh_glm_multi: the same for many phenotypes in one call; pgh_glm_sparse: the linear fit over a sparse-resident
+// dataset, from its entries (glm_sparse.hip).
 #include "api_internal.hpp"
 #include "glm.hpp"
 #include "glm_math.hpp"
@@ -413,11 +414,11 @@ int GlmMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begi
 	return PGH_OK;
 }
 
-// The argument checks of pgh_glm (n_pheno = 1) and pgh_glm_multi.
-int GlmCheckArgs(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end, uint32_t n_pheno,
-                 const double *phenotypes, uint32_t n_covar, const double *covariates, int model, const pgh_glm_row *out,
-                 char *errbuf) {
-	PGH_DENSE_ROWS(ds);
+// The argument checks that pgh_glm (n_pheno = 1), pgh_glm_multi and pgh_glm_sparse share: everything but the
+// resident form of the dataset.
+int GlmCheckCommon(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end, uint32_t n_pheno,
+                   const double *phenotypes, uint32_t n_covar, const double *covariates, int model,
+                   const pgh_glm_row *out, char *errbuf) {
 	int rc = CheckRange(ds, v_begin, v_end, errbuf);
 	if (rc != PGH_OK) {
 		return rc;
@@ -449,6 +450,154 @@ int GlmCheckArgs(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_beg
 			SetErr(errbuf, "covariate " + std::to_string(i / n_out) + " is not finite at sample " +
 			                   std::to_string(i % n_out));
 			return PGH_ERR_ARG;
+		}
+	}
+	return PGH_OK;
+}
+
+// The argument checks of pgh_glm (n_pheno = 1) and pgh_glm_multi.
+int GlmCheckArgs(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end, uint32_t n_pheno,
+                 const double *phenotypes, uint32_t n_covar, const double *covariates, int model, const pgh_glm_row *out,
+                 char *errbuf) {
+	PGH_DENSE_ROWS(ds);
+	return GlmCheckCommon(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, model, out, errbuf);
+}
+
+// pgh_glm_sparse on one sparse-resident dataset.  y and z are staged twice when there is a subset: in output-sample
+// order for the dense kernels (the whole-call Gram and the dense-form rows), and in raw-sample order, NaN y outside
+// the subset, for the entry kernel, whose entries name raw samples.  Without a subset the two orders are one.
+int GlmSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                 const double *phenotype, uint32_t k, const double *covariates, pgh_glm_row *out, char *errbuf) {
+	PGH_ENTER(ds);
+	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct, n_raw = ds->sample_ct;
+	const uint32_t nv_all = v_end - v_begin;
+	const uint32_t kp = pgh::GlmPadCovar(k);
+	hipStream_t st = PghThreadStream();
+
+	// y and z centred over the samples with a phenotype, exactly as GlmOne's linear fit does
+	std::vector<double> hz(static_cast<size_t>(n_out) * kp, 0.0);
+	for (uint32_t j = 0; j < k; j++) {
+		for (uint32_t i = 0; i < n_out; i++) {
+			hz[static_cast<size_t>(i) * kp + j] = covariates[static_cast<size_t>(j) * n_out + i];
+		}
+	}
+	uint32_t n_y = 0;
+	for (uint32_t i = 0; i < n_out; i++) {
+		n_y += std::isnan(phenotype[i]) ? 0u : 1u;
+	}
+	std::vector<double> hy(phenotype, phenotype + n_out);
+	if (n_y) {
+		double my = 0.0;
+		for (uint32_t i = 0; i < n_out; i++) {
+			my += std::isnan(hy[i]) ? 0.0 : hy[i];
+		}
+		my /= n_y;
+		for (uint32_t i = 0; i < n_out; i++) {
+			hy[i] -= my;
+		}
+		for (uint32_t j = 0; j < k; j++) {
+			double mz = 0.0;
+			for (uint32_t i = 0; i < n_out; i++) {
+				mz += std::isnan(hy[i]) ? 0.0 : hz[static_cast<size_t>(i) * kp + j];
+			}
+			mz /= n_y;
+			for (uint32_t i = 0; i < n_out; i++) {
+				hz[static_cast<size_t>(i) * kp + j] -= mz;
+			}
+		}
+	}
+	std::vector<double> hy_raw, hz_raw;
+	if (subset) {
+		hy_raw.assign(n_raw, std::nan(""));
+		hz_raw.assign(static_cast<size_t>(n_raw) * kp, 0.0);
+		for (uint32_t i = 0; i < n_out; i++) {
+			const uint32_t s = subset->sel[i];
+			hy_raw[s] = hy[i];
+			std::copy_n(hz.data() + static_cast<size_t>(i) * kp, kp, hz_raw.data() + static_cast<size_t>(s) * kp);
+		}
+	}
+
+	const uint32_t chunk = std::min(kGlmChunk, std::max(1u, nv_all));
+	// the dense-form rows of a chunk are consecutive pool rows
+	const uint32_t l_begin = v_begin - ds->v_begin;
+	uint32_t dense_max = 0;
+	for (uint32_t c0 = 0; c0 < nv_all; c0 += chunk) {
+		const uint32_t l0 = l_begin + c0, l1 = l0 + std::min(chunk, nv_all - c0);
+		dense_max = std::max(dense_max, ds->sp_dense_before[l1] - ds->sp_dense_before[l0]);
+	}
+	const uint32_t ns = kp + 4, q = k + 2, ne_gram = q * (q + 1) / 2;
+	auto up = [](uint64_t b) { return (b + 255) / 256 * 256; };
+	const uint64_t b_y = up(8ull * n_out), b_z = up(8ull * n_out * kp + 8), b_gram = up(8ull * ne_gram);
+	const uint64_t b_yr = subset ? up(8ull * n_raw) : 0, b_zr = subset ? up(8ull * n_raw * kp + 8) : 0;
+	const uint64_t b_sums = up(8ull * chunk * ns), b_corr = up(8ull * chunk * ne_gram);
+	const uint64_t b_rows = up(sizeof(pgh_glm_row) * chunk);
+	const uint64_t b_dsums = up(8ull * dense_max * ns), b_dcorr = up(8ull * dense_max * ne_gram);
+	const uint64_t b_drows = up(sizeof(pgh_glm_row) * dense_max);
+	const uint64_t total = b_y + b_z + b_gram + b_yr + b_zr + b_sums + b_corr + b_rows + b_dsums + b_dcorr + b_drows;
+	void *scratch = nullptr;
+	PGH_HIP(PghThreadScratch(total, st, &scratch), "glm_sparse scratch");
+	char *cur = static_cast<char *>(scratch);
+	auto take = [&](uint64_t b) {
+		char *p = cur;
+		cur += b;
+		return p;
+	};
+	double *d_y = reinterpret_cast<double *>(take(b_y));
+	double *d_z = reinterpret_cast<double *>(take(b_z));
+	double *d_gram = reinterpret_cast<double *>(take(b_gram));
+	double *d_yr = subset ? reinterpret_cast<double *>(take(b_yr)) : d_y;
+	double *d_zr = subset ? reinterpret_cast<double *>(take(b_zr)) : d_z;
+	double *d_sums = reinterpret_cast<double *>(take(b_sums));
+	double *d_corr = reinterpret_cast<double *>(take(b_corr));
+	pgh_glm_row *d_rows = reinterpret_cast<pgh_glm_row *>(take(b_rows));
+	double *d_dsums = reinterpret_cast<double *>(take(b_dsums));
+	double *d_dcorr = reinterpret_cast<double *>(take(b_dcorr));
+	pgh_glm_row *d_drows = reinterpret_cast<pgh_glm_row *>(take(b_drows));
+
+	std::vector<pgh_glm_row> hdrows(dense_max);
+	HostSourceFence fence(st); // hy, hz, hy_raw, hz_raw feed asynchronous uploads
+	PGH_HIP(hipMemcpyAsync(d_y, hy.data(), 8ull * n_out, hipMemcpyHostToDevice, st), "glm_sparse phenotype upload");
+	if (kp) {
+		PGH_HIP(hipMemcpyAsync(d_z, hz.data(), 8ull * n_out * kp, hipMemcpyHostToDevice, st), "glm_sparse covariate upload");
+	}
+	if (subset) {
+		PGH_HIP(hipMemcpyAsync(d_yr, hy_raw.data(), 8ull * n_raw, hipMemcpyHostToDevice, st),
+		        "glm_sparse phenotype upload (raw order)");
+		if (kp) {
+			PGH_HIP(hipMemcpyAsync(d_zr, hz_raw.data(), 8ull * n_raw * kp, hipMemcpyHostToDevice, st),
+			        "glm_sparse covariate upload (raw order)");
+		}
+	}
+	PGH_HIP(pgh::LaunchGlmGram(nullptr, 1, nullptr, 0, n_y, n_out, d_y, d_z, kp, k, d_gram, st), "glm_sparse gram kernel");
+	for (uint32_t c0 = 0; c0 < nv_all; c0 += chunk) {
+		const uint32_t nv = std::min(chunk, nv_all - c0);
+		const uint32_t l0 = l_begin + c0;
+		PGH_HIP(pgh::LaunchGlmSparse(ds->Sparse(), l0, nv, d_yr, d_zr, kp, k, n_y, d_gram, d_sums, d_corr, st),
+		        "glm_sparse entry kernel");
+		PGH_HIP(pgh::LaunchGlmLinearSolve(nv, d_sums, kp, k, d_gram, d_corr, d_rows, st), "glm_sparse solve kernel");
+		PGH_HIP(hipMemcpyAsync(out + c0, d_rows, sizeof(pgh_glm_row) * nv, hipMemcpyDeviceToHost, st), "glm_sparse rows copy");
+		// the dense-form rows: pgh_glm's kernels over their pool rows
+		const uint32_t dense_first = ds->sp_dense_before[l0];
+		const uint32_t dense_ct = ds->sp_dense_before[l0 + nv] - dense_first;
+		if (dense_ct) {
+			pgh::GlmX g {};
+			g.view = ds->PoolView();
+			g.v0 = dense_first;
+			g.n_out = n_out;
+			g.sel = subset ? subset->d_sel : nullptr;
+			PGH_HIP(pgh::LaunchGlmSums(g, dense_ct, d_y, d_z, kp, d_dsums, st), "glm_sparse sums kernel (dense pool)");
+			PGH_HIP(pgh::LaunchGlmGram(&g, dense_ct, d_dsums, ns, n_y, n_out, d_y, d_z, kp, k, d_dcorr, st),
+			        "glm_sparse correction kernel (dense pool)");
+			PGH_HIP(pgh::LaunchGlmLinearSolve(dense_ct, d_dsums, kp, k, d_gram, d_dcorr, d_drows, st),
+			        "glm_sparse solve kernel (dense pool)");
+			PGH_HIP(hipMemcpyAsync(hdrows.data(), d_drows, sizeof(pgh_glm_row) * dense_ct, hipMemcpyDeviceToHost, st),
+			        "glm_sparse rows copy (dense pool)");
+		}
+		PGH_HIP(hipStreamSynchronize(st), "glm_sparse sync");
+		for (uint32_t i = 0, j = 0; i < nv && j < dense_ct; i++) {
+			if (ds->sp_dense_before[l0 + i + 1] != ds->sp_dense_before[l0 + i]) {
+				out[c0 + i] = hdrows[j++];
+			}
 		}
 	}
 	return PGH_OK;
@@ -517,4 +666,19 @@ extern "C" int pgh_glm_multi(const pgh_dataset *ds, const pgh_subset *subset, ui
 		return PGH_OK;
 	}
 	return GlmMultiOne(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, model, firth, out, errbuf);
+}
+
+extern "C" int pgh_glm_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                              const double *phenotype, uint32_t n_covar, const double *covariates, pgh_glm_row *out,
+                              char *errbuf) {
+	if (ds && !ds->sparse) {
+		SetErr(errbuf, "needs a sparse-resident dataset (pgh_open_sparse)");
+		return PGH_ERR_ARG;
+	}
+	const int rc = GlmCheckCommon(ds, subset, v_begin, v_end, 1, phenotype, n_covar, covariates, PGH_GLM_LINEAR, out,
+	                              errbuf);
+	if (rc != PGH_OK || v_end == v_begin) {
+		return rc;
+	}
+	return GlmSparseOne(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, out, errbuf);
 }

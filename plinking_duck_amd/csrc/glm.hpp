@@ -4,6 +4,7 @@
 
 #include "../../include/pgenhip.h"
 #include "kernels.hpp"
+#include "sparse.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -97,5 +98,16 @@ hipError_t LaunchGlmMultiCorr(const GlmX &g, uint32_t nv, const double *sums, ui
 hipError_t LaunchGlmMultiSolve(uint32_t nv, uint32_t pb, const double *sums, uint32_t kp, uint32_t k,
                                const double *sxy, const double *gram, const double *whole, const double *corr_s,
                                const double *corr_p, pgh_glm_row *rows, hipStream_t stream);
+
+// ---- pgh_glm_sparse (glm_sparse.hip): the linear fit's sums and correction Grams from a sparse row's entries ----
+// A row of more than kGlmSparseLong entries is walked by a whole workgroup, a shorter one by one wave.
+constexpr uint32_t kGlmSparseLong = 1024;
+// For the rows v_first + i (i < nv) of `sv` that are sparse: sums[i][kp+4] in LaunchGlmSums' layout and corr[i] in
+// LaunchGlmGram's per-variant layout, ready for LaunchGlmLinearSolve; zeros for the dense-form rows.
+// y: sv.sample_ct doubles in RAW sample order, NaN = no phenotype or outside the subset; z: sv.sample_ct x kp doubles,
+// raw sample-major.  gram: LaunchGlmGram's whole-call Gram over the n_y samples with a phenotype.
+hipError_t LaunchGlmSparse(const SparseView &sv, uint32_t v_first, uint32_t nv, const double *y, const double *z,
+                           uint32_t kp, uint32_t k, uint32_t n_y, const double *gram, double *sums, double *corr,
+                           hipStream_t stream);
 
 } // namespace pgh
