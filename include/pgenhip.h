@@ -540,6 +540,56 @@ int pgh_glm_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_be
 int pgh_glm_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                    const double *phenotype, uint32_t n_covar, const double *covariates,
                    pgh_glm_row *out, char *errbuf);
+/* Gene-set BURDEN tests over a SPARSE-RESIDENT dataset (pgh_open_sparse), from the variants' entries: per set, the
+ * variants are collapsed into one weighted burden per sample and the phenotype is regressed on it (linear).
+ *
+ * Inputs.  phenotype, n_covar, covariates and subset are pgh_glm_sparse's.  The n_sets >= 1 sets are in CSR form:
+ * set_off[n_sets + 1] (set_off[0] == 0, not decreasing) and set_vidx[set_off[n_sets]], set s being the memberships
+ * set_off[s] .. set_off[s + 1] - 1.  A set_vidx entry is a variant index OF THE DATASET: 0 names the first resident
+ * variant (pgh_info.variant_begin), and every entry is below variant_end - variant_begin.  Any order; a repeated
+ * variant counts each time; an empty set is allowed.  weight: NULL (every weight 1.0) or one finite double per
+ * membership.
+ *
+ * Values.  S = the output samples with a phenotype, n_y = |S|.  val(c) = c for the codes 0, 1, 2 and val(3) = 0: a
+ * MISSING CALL CONTRIBUTES NOTHING, i.e. it is imputed hom-ref.  (This is a definition.  It has not been compared
+ * with any other program's output.)  For set s with memberships m = 0, 1, .. in set order, variant v_m, weight w_m and
+ * b_m the base code of v_m's resident row (pgh_open_sparse: the row's majority code; 0 for a row held in the dense
+ * form, whose entries are then its samples with code 1 or 2):
+ *   c_s = sum_m w_m val(b_m);
+ *   d_i, for a sample i of S, starts at 0.0 and takes, for each membership in set order at which sample i has an entry
+ *        with code c, d_i = d_i + w_m * (double)(val(c) - val(b_m)): one multiply and one add in FP64, so d_i is a
+ *        bit-defined function of the set;
+ *   B_i = c_s + d_i, the burden.
+ *
+ * Fit.  OLS of y on [B, 1, z] over S.  The intercept absorbs c_s, so the fit runs on the sums over d (n = n_y,
+ * sum d, sum d^2, sum d y, sum d z_j; y and z centred over S as pgh_glm centres them) and pgh_glm's linear solve:
+ * its pivot rule, df = n_y - n_covar - 2 and the t p-value.
+ *
+ * Decisions, in this order: n_y < n_covar + 3: PGH_GLM_TOO_FEW_SAMPLES for every row.  PGH_GLM_CONST_ALLELE iff
+ * min over S of d_i == max over S of d_i, an exact FP compare (samples without an entry have d_i = 0; an empty set
+ * and a set with no carrier in S land here).  Otherwise PGH_GLM_SINGULAR_MATRIX and PGH_GLM_ZERO_VARIANCE as the
+ * solve decides them.
+ *
+ * out: one row per set, in set order.  A set's row is a function of its memberships and weights, of the phenotype,
+ * the covariates and the subset alone: not of the other sets of the call or its place among them, of how many
+ * workgroups ran or which took the set, or of the window the dataset was opened with; the same call returns the same
+ * bytes every time.  PGH_BURDEN_SCRATCH_BYTES (read at every call; default 1 GiB) bounds the device scratch of the
+ * per-set accumulation and with it the number of sets in flight; the result does not depend on it.
+ *
+ * PGH_ERR_ARG, out untouched: a dataset that is not sparse-resident ("needs a sparse-resident dataset"), a shard
+ * group, n_sets == 0, set_off[0] != 0 or a decreasing set_off, a set_vidx entry that is not below the variant count,
+ * a weight that is not finite, and whatever pgh_glm_sparse refuses in the arguments they share. */
+typedef struct pgh_burden_row {
+	double beta, se, stat, p;  /* NaN where the row is undecided                     */
+	double mean;               /* c_s + (sum d) / n_y; NaN when n_y == 0             */
+	uint32_t obs_ct;           /* n_y                                                */
+	uint32_t n_nonzero;        /* samples of S with d_i != 0.0                       */
+	uint8_t errcode;           /* PGH_GLM_*                                          */
+	uint8_t pad[7];
+} pgh_burden_row;
+int pgh_burden_sparse(const pgh_dataset *ds, const pgh_subset *subset, const double *phenotype, uint32_t n_covar,
+                      const double *covariates, uint32_t n_sets, const uint64_t *set_off, const uint32_t *set_vidx,
+                      const double *weight /* NULL or one per membership */, pgh_burden_row *out, char *errbuf);
 /* two-sided p of Student's t with df degrees of freedom (the reference's TstatToPvalue) */
 double pgh_glm_p_from_t(double t, double df);
 /* two-sided p of a standard normal z (ZstatToPvalue) */

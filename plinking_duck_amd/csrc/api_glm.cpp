@@ -1,6 +1,7 @@
 // api_glm.cpp -- pgh_glm: plink_glm's per-variant linear / logistic / Firth regressions (glm.hip) behind the C ABI;
 // pgh_glm_multi: the same for many phenotypes in one call; pgh_glm_sparse: the linear fit over a sparse-resident
-// dataset, from its entries (glm_sparse.hip).
+// dataset, from its entries (glm_sparse.hip); pgh_burden_sparse: gene-set burden fits over such a dataset
+// (burden_sparse.hip).
 #include "api_internal.hpp"
 #include "glm.hpp"
 #include "glm_math.hpp"
@@ -463,19 +464,21 @@ int GlmCheckArgs(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_beg
 	return GlmCheckCommon(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, model, out, errbuf);
 }
 
-// pgh_glm_sparse on one sparse-resident dataset.  y and z are staged twice when there is a subset: in output-sample
-// order for the dense kernels (the whole-call Gram and the dense-form rows), and in raw-sample order, NaN y outside
-// the subset, for the entry kernel, whose entries name raw samples.  Without a subset the two orders are one.
-int GlmSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
-                 const double *phenotype, uint32_t k, const double *covariates, pgh_glm_row *out, char *errbuf) {
-	PGH_ENTER(ds);
-	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct, n_raw = ds->sample_ct;
-	const uint32_t nv_all = v_end - v_begin;
-	const uint32_t kp = pgh::GlmPadCovar(k);
-	hipStream_t st = PghThreadStream();
+// y and z of a linear fit as the kernels read them: z sample-major and zero padded to kp columns, both centred over
+// the samples with a phenotype exactly as GlmOne's linear fit centres them; and, with a subset, the same in raw-sample
+// order with NaN y outside the subset, for the kernels whose entries name raw samples (empty without a subset: the
+// two orders are one).
+struct GlmStaged {
+	std::vector<double> hy, hz, hy_raw, hz_raw;
+	uint32_t n_y = 0;
+};
 
-	// y and z centred over the samples with a phenotype, exactly as GlmOne's linear fit does
-	std::vector<double> hz(static_cast<size_t>(n_out) * kp, 0.0);
+GlmStaged GlmStageLinear(const pgh_dataset *ds, const pgh_subset *subset, const double *phenotype, uint32_t k,
+                         uint32_t kp, const double *covariates) {
+	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct, n_raw = ds->sample_ct;
+	GlmStaged sg;
+	std::vector<double> &hz = sg.hz, &hy = sg.hy;
+	hz.assign(static_cast<size_t>(n_out) * kp, 0.0);
 	for (uint32_t j = 0; j < k; j++) {
 		for (uint32_t i = 0; i < n_out; i++) {
 			hz[static_cast<size_t>(i) * kp + j] = covariates[static_cast<size_t>(j) * n_out + i];
@@ -485,7 +488,8 @@ int GlmSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_beg
 	for (uint32_t i = 0; i < n_out; i++) {
 		n_y += std::isnan(phenotype[i]) ? 0u : 1u;
 	}
-	std::vector<double> hy(phenotype, phenotype + n_out);
+	sg.n_y = n_y;
+	hy.assign(phenotype, phenotype + n_out);
 	if (n_y) {
 		double my = 0.0;
 		for (uint32_t i = 0; i < n_out; i++) {
@@ -506,16 +510,32 @@ int GlmSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_beg
 			}
 		}
 	}
-	std::vector<double> hy_raw, hz_raw;
 	if (subset) {
-		hy_raw.assign(n_raw, std::nan(""));
-		hz_raw.assign(static_cast<size_t>(n_raw) * kp, 0.0);
+		sg.hy_raw.assign(n_raw, std::nan(""));
+		sg.hz_raw.assign(static_cast<size_t>(n_raw) * kp, 0.0);
 		for (uint32_t i = 0; i < n_out; i++) {
 			const uint32_t s = subset->sel[i];
-			hy_raw[s] = hy[i];
-			std::copy_n(hz.data() + static_cast<size_t>(i) * kp, kp, hz_raw.data() + static_cast<size_t>(s) * kp);
+			sg.hy_raw[s] = hy[i];
+			std::copy_n(hz.data() + static_cast<size_t>(i) * kp, kp, sg.hz_raw.data() + static_cast<size_t>(s) * kp);
 		}
 	}
+	return sg;
+}
+
+// pgh_glm_sparse on one sparse-resident dataset.  y and z are staged twice when there is a subset: in output-sample
+// order for the dense kernels (the whole-call Gram and the dense-form rows), and in raw-sample order, NaN y outside
+// the subset, for the entry kernel, whose entries name raw samples.  Without a subset the two orders are one.
+int GlmSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                 const double *phenotype, uint32_t k, const double *covariates, pgh_glm_row *out, char *errbuf) {
+	PGH_ENTER(ds);
+	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct, n_raw = ds->sample_ct;
+	const uint32_t nv_all = v_end - v_begin;
+	const uint32_t kp = pgh::GlmPadCovar(k);
+	hipStream_t st = PghThreadStream();
+
+	const GlmStaged sg = GlmStageLinear(ds, subset, phenotype, k, kp, covariates);
+	const std::vector<double> &hy = sg.hy, &hz = sg.hz, &hy_raw = sg.hy_raw, &hz_raw = sg.hz_raw;
+	const uint32_t n_y = sg.n_y;
 
 	const uint32_t chunk = std::min(kGlmChunk, std::max(1u, nv_all));
 	// the dense-form rows of a chunk are consecutive pool rows
@@ -603,6 +623,129 @@ int GlmSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_beg
 	return PGH_OK;
 }
 
+constexpr uint64_t kBurdenScratchBytes = 1ull << 30;
+const char *const kBurdenScratchEnv = "PGH_BURDEN_SCRATCH_BYTES";
+
+// The byte budget of the workgroups' private vectors (read at every call; the result does not depend on it: it only
+// bounds how many sets are in flight, and anything below one vector still gives one workgroup).
+uint64_t BurdenScratchBytes() {
+	const char *s = std::getenv(kBurdenScratchEnv);
+	if (s && *s) {
+		char *end = nullptr;
+		const unsigned long long v = std::strtoull(s, &end, 10);
+		if (end && *end == '\0') {
+			return v;
+		}
+	}
+	return kBurdenScratchBytes;
+}
+
+// pgh_burden_sparse on one sparse-resident dataset, after the argument checks.  n_memb = set_off[n_sets].
+int BurdenSparseOne(const pgh_dataset *ds, const pgh_subset *subset, const double *phenotype, uint32_t k,
+                    const double *covariates, uint32_t n_sets, const uint64_t *set_off, const uint32_t *set_vidx,
+                    const double *weight, pgh_burden_row *out, char *errbuf) {
+	PGH_ENTER(ds);
+	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct, n_raw = ds->sample_ct;
+	const uint32_t kp = pgh::GlmPadCovar(k);
+	const uint64_t n_memb = set_off[n_sets];
+	hipStream_t st = PghThreadStream();
+	const GlmStaged sg = GlmStageLinear(ds, subset, phenotype, k, kp, covariates);
+	const uint32_t n_y = sg.n_y;
+
+	// the grid: a private vector per workgroup within the byte budget, at most eight workgroups per compute unit
+	int device = 0, cus = 0;
+	PGH_HIP(hipGetDevice(&device), "burden_sparse device");
+	PGH_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device), "burden_sparse device attribute");
+	const uint64_t per_group = pgh::BurdenScratchPerGroup(n_raw);
+	const uint32_t n_groups = static_cast<uint32_t>(std::min<uint64_t>(
+	    std::min<uint64_t>(n_sets, 8ull * static_cast<uint32_t>(std::max(cus, 1))),
+	    std::max<uint64_t>(1, BurdenScratchBytes() / per_group)));
+	DevBuf vectors;
+	PGH_HIP(vectors.Alloc(per_group * n_groups), "burden_sparse vectors");
+
+	const uint32_t ns = kp + 4, q = k + 2, ne_gram = q * (q + 1) / 2;
+	auto up = [](uint64_t b) { return (b + 255) / 256 * 256; };
+	const uint64_t b_y = up(8ull * n_out), b_z = up(8ull * n_out * kp + 8), b_gram = up(8ull * ne_gram);
+	const uint64_t b_yr = subset ? up(8ull * n_raw) : 0, b_zr = subset ? up(8ull * n_raw * kp + 8) : 0;
+	const uint64_t b_off = up(8ull * (n_sets + 1ull)), b_vidx = up(4ull * n_memb + 4), b_w = weight ? up(8ull * n_memb + 8) : 0;
+	const uint64_t b_ctr = 256, b_sums = up(8ull * n_sets * ns), b_aux = up(sizeof(pgh::BurdenAux) * n_sets);
+	const uint64_t b_flag = up(n_sets), b_rows = up(sizeof(pgh_glm_row) * n_sets);
+	const uint64_t total = b_y + b_z + b_gram + b_yr + b_zr + b_off + b_vidx + b_w + b_ctr + b_sums + b_aux + b_flag + b_rows;
+	void *scratch = nullptr;
+	PGH_HIP(PghThreadScratch(total, st, &scratch), "burden_sparse scratch");
+	char *cur = static_cast<char *>(scratch);
+	auto take = [&](uint64_t b) {
+		char *p = cur;
+		cur += b;
+		return p;
+	};
+	double *d_y = reinterpret_cast<double *>(take(b_y));
+	double *d_z = reinterpret_cast<double *>(take(b_z));
+	double *d_gram = reinterpret_cast<double *>(take(b_gram));
+	double *d_yr = subset ? reinterpret_cast<double *>(take(b_yr)) : d_y;
+	double *d_zr = subset ? reinterpret_cast<double *>(take(b_zr)) : d_z;
+	uint64_t *d_off = reinterpret_cast<uint64_t *>(take(b_off));
+	uint32_t *d_vidx = reinterpret_cast<uint32_t *>(take(b_vidx));
+	double *d_w = weight ? reinterpret_cast<double *>(take(b_w)) : nullptr;
+	uint32_t *d_ctr = reinterpret_cast<uint32_t *>(take(b_ctr));
+	double *d_sums = reinterpret_cast<double *>(take(b_sums));
+	pgh::BurdenAux *d_aux = reinterpret_cast<pgh::BurdenAux *>(take(b_aux));
+	uint8_t *d_flag = reinterpret_cast<uint8_t *>(take(b_flag));
+	pgh_glm_row *d_rows = reinterpret_cast<pgh_glm_row *>(take(b_rows));
+
+	std::vector<pgh_glm_row> rows(n_sets);
+	std::vector<pgh::BurdenAux> aux(n_sets);
+	HostSourceFence fence(st); // sg's vectors and the caller's set arrays feed asynchronous uploads
+	PGH_HIP(hipMemcpyAsync(d_y, sg.hy.data(), 8ull * n_out, hipMemcpyHostToDevice, st), "burden_sparse phenotype upload");
+	if (kp) {
+		PGH_HIP(hipMemcpyAsync(d_z, sg.hz.data(), 8ull * n_out * kp, hipMemcpyHostToDevice, st),
+		        "burden_sparse covariate upload");
+	}
+	if (subset) {
+		PGH_HIP(hipMemcpyAsync(d_yr, sg.hy_raw.data(), 8ull * n_raw, hipMemcpyHostToDevice, st),
+		        "burden_sparse phenotype upload (raw order)");
+		if (kp) {
+			PGH_HIP(hipMemcpyAsync(d_zr, sg.hz_raw.data(), 8ull * n_raw * kp, hipMemcpyHostToDevice, st),
+			        "burden_sparse covariate upload (raw order)");
+		}
+	}
+	PGH_HIP(hipMemcpyAsync(d_off, set_off, 8ull * (n_sets + 1ull), hipMemcpyHostToDevice, st), "burden_sparse set upload");
+	if (n_memb) {
+		PGH_HIP(hipMemcpyAsync(d_vidx, set_vidx, 4ull * n_memb, hipMemcpyHostToDevice, st), "burden_sparse member upload");
+		if (weight) {
+			PGH_HIP(hipMemcpyAsync(d_w, weight, 8ull * n_memb, hipMemcpyHostToDevice, st), "burden_sparse weight upload");
+		}
+	}
+	// zeroed at every call: nothing is assumed of what an earlier call, or another user of the block, left there
+	PGH_HIP(hipMemsetAsync(vectors.p, 0, per_group * n_groups, st), "burden_sparse vectors clear");
+	PGH_HIP(hipMemsetAsync(d_ctr, 0, b_ctr, st), "burden_sparse counter clear");
+	PGH_HIP(pgh::LaunchGlmGram(nullptr, 1, nullptr, 0, n_y, n_out, d_y, d_z, kp, k, d_gram, st), "burden_sparse gram kernel");
+	PGH_HIP(pgh::LaunchBurdenSparse(ds->Sparse(), n_sets, d_off, d_vidx, d_w, d_yr, d_zr, kp, k, n_y, n_groups, vectors.p,
+	                                d_ctr, d_sums, d_aux, d_flag, st),
+	        "burden_sparse set kernel");
+	PGH_HIP(pgh::LaunchGlmLinearSolve(n_sets, d_sums, kp, k, d_gram, nullptr, d_rows, st, d_flag),
+	        "burden_sparse solve kernel");
+	PGH_HIP(hipMemcpyAsync(rows.data(), d_rows, sizeof(pgh_glm_row) * n_sets, hipMemcpyDeviceToHost, st),
+	        "burden_sparse rows copy");
+	PGH_HIP(hipMemcpyAsync(aux.data(), d_aux, sizeof(pgh::BurdenAux) * n_sets, hipMemcpyDeviceToHost, st),
+	        "burden_sparse sums copy");
+	PGH_HIP(hipStreamSynchronize(st), "burden_sparse sync");
+	for (uint32_t s = 0; s < n_sets; s++) {
+		pgh_burden_row r;
+		std::memset(&r, 0, sizeof r);
+		r.beta = rows[s].beta;
+		r.se = rows[s].se;
+		r.stat = rows[s].stat;
+		r.p = rows[s].p;
+		r.mean = n_y ? aux[s].c + aux[s].sum_d / n_y : std::nan("");
+		r.obs_ct = n_y;
+		r.n_nonzero = aux[s].n_nonzero;
+		r.errcode = rows[s].errcode;
+		out[s] = r;
+	}
+	return PGH_OK;
+}
+
 } // namespace
 
 extern "C" double pgh_glm_p_from_t(double t, double df) {
@@ -681,4 +824,59 @@ extern "C" int pgh_glm_sparse(const pgh_dataset *ds, const pgh_subset *subset, u
 		return rc;
 	}
 	return GlmSparseOne(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, out, errbuf);
+}
+
+extern "C" int pgh_burden_sparse(const pgh_dataset *ds, const pgh_subset *subset, const double *phenotype,
+                                 uint32_t n_covar, const double *covariates, uint32_t n_sets, const uint64_t *set_off,
+                                 const uint32_t *set_vidx, const double *weight, pgh_burden_row *out, char *errbuf) {
+	PGH_ONE_DEVICE(ds);
+	if (ds && !ds->sparse) {
+		SetErr(errbuf, "needs a sparse-resident dataset (pgh_open_sparse)");
+		return PGH_ERR_ARG;
+	}
+	// the arguments pgh_glm_sparse has too, over the whole resident range (its `out` is checked below)
+	const int rc = GlmCheckCommon(ds, subset, ds ? ds->v_begin : 0, ds ? ds->v_begin : 0, 1, phenotype, n_covar, covariates,
+	                              PGH_GLM_LINEAR, nullptr, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
+	}
+	if (n_sets == 0) {
+		SetErr(errbuf, "at least one set is needed");
+		return PGH_ERR_ARG;
+	}
+	if (!set_off || !out) {
+		SetErr(errbuf, "null argument");
+		return PGH_ERR_ARG;
+	}
+	if (set_off[0] != 0) {
+		SetErr(errbuf, "set_off[0] must be 0, got " + std::to_string(set_off[0]));
+		return PGH_ERR_ARG;
+	}
+	for (uint32_t s = 0; s < n_sets; s++) {
+		if (set_off[s + 1] < set_off[s]) {
+			SetErr(errbuf, "set_off decreases at set " + std::to_string(s) + " (" + std::to_string(set_off[s]) + " -> " +
+			                   std::to_string(set_off[s + 1]) + ")");
+			return PGH_ERR_ARG;
+		}
+	}
+	const uint64_t n_memb = set_off[n_sets];
+	const uint32_t n_var = ds->v_end - ds->v_begin;
+	if (n_memb && !set_vidx) {
+		SetErr(errbuf, "null argument");
+		return PGH_ERR_ARG;
+	}
+	for (uint64_t m = 0; m < n_memb; m++) {
+		if (set_vidx[m] >= n_var) {
+			SetErr(errbuf, "set_vidx[" + std::to_string(m) + "] = " + std::to_string(set_vidx[m]) +
+			                   " is not below the dataset's variant count " + std::to_string(n_var));
+			return PGH_ERR_ARG;
+		}
+	}
+	for (uint64_t m = 0; weight && m < n_memb; m++) {
+		if (!std::isfinite(weight[m])) {
+			SetErr(errbuf, "weight " + std::to_string(m) + " is not finite");
+			return PGH_ERR_ARG;
+		}
+	}
+	return BurdenSparseOne(ds, subset, phenotype, n_covar, covariates, n_sets, set_off, set_vidx, weight, out, errbuf);
 }

@@ -218,9 +218,12 @@ __device__ inline bool GlmConstant(double n, double sx, double sxx) {
 	return a < b || (a == b && a_lo <= b_lo);
 }
 
+// FLAGGED (pgh_burden_sparse): x is not on the dosage grid, so CONST_ALLELE is decided by the caller (x_const[v] != 0)
+// and the correction Gram is zero (corr is not read).  FLAGGED == false is the kernel of pgh_glm and pgh_glm_sparse.
+template <bool FLAGGED>
 __global__ void GlmLinearSolveKernel(uint32_t nv, const double *__restrict__ sums, uint32_t kp, uint32_t k,
                                      const double *__restrict__ gram, const double *__restrict__ corr,
-                                     pgh_glm_row *__restrict__ rows) {
+                                     const uint8_t *__restrict__ x_const, pgh_glm_row *__restrict__ rows) {
 	const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
 	if (v >= nv) {
 		return;
@@ -240,7 +243,13 @@ __global__ void GlmLinearSolveKernel(uint32_t nv, const double *__restrict__ sum
 	}
 	r.a1_freq = s[1] / (2.0 * n);
 	// with no covariates the reference takes its one-pass closed form, and its test with it
-	if (k ? GlmConstant(n, s[1], s[2]) : s[2] - s[1] * s[1] / n < 1e-20) {
+	bool constant;
+	if constexpr (FLAGGED) {
+		constant = x_const[v] != 0;
+	} else {
+		constant = k ? GlmConstant(n, s[1], s[2]) : s[2] - s[1] * s[1] / n < 1e-20;
+	}
+	if (constant) {
 		r.errcode = PGH_GLM_CONST_ALLELE;
 		rows[v] = r;
 		return;
@@ -253,7 +262,7 @@ __global__ void GlmLinearSolveKernel(uint32_t nv, const double *__restrict__ sum
 	for (int ua = 0; ua < static_cast<int>(q); ua++) {
 		for (int ub = ua; ub < static_cast<int>(q); ub++) {
 			const int e = PackIdx(ua, ub, q);
-			const double val = gram[e] - c[e];
+			const double val = FLAGGED ? gram[e] : gram[e] - c[e];
 			const int ia = uidx(ua), ib = uidx(ub);
 			a[ib * M + ia] = val; // lower triangle: ib >= ia
 		}
@@ -1050,11 +1059,15 @@ hipError_t LaunchGlmGram(const GlmX *g, uint32_t nv, const double *sums, uint32_
 }
 
 hipError_t LaunchGlmLinearSolve(uint32_t nv, const double *sums, uint32_t kp, uint32_t k, const double *gram,
-                                const double *corr, pgh_glm_row *rows, hipStream_t stream) {
+                                const double *corr, pgh_glm_row *rows, hipStream_t stream, const uint8_t *x_const) {
 	if (nv == 0) {
 		return hipSuccess;
 	}
-	GlmLinearSolveKernel<<<Blocks(nv, 64), 64, 0, stream>>>(nv, sums, kp, k, gram, corr, rows);
+	if (x_const) {
+		GlmLinearSolveKernel<true><<<Blocks(nv, 64), 64, 0, stream>>>(nv, sums, kp, k, gram, nullptr, x_const, rows);
+	} else {
+		GlmLinearSolveKernel<false><<<Blocks(nv, 64), 64, 0, stream>>>(nv, sums, kp, k, gram, corr, nullptr, rows);
+	}
 	return hipGetLastError();
 }
 

@@ -52,8 +52,11 @@ hipError_t LaunchGlmGram(const GlmX *g, uint32_t nv, const double *sums, uint32_
                          uint32_t n_out, const double *y, const double *z, uint32_t kp, uint32_t k, double *out,
                          hipStream_t stream);
 // The OLS per variant from the sums, the whole-call Gram and the variant's correction Gram.
+// x_const != null (pgh_burden_sparse, whose x is off the 2^-14 dosage grid that the solve's own constancy test is
+// written for): row v is CONST_ALLELE iff x_const[v] != 0, and the correction Grams are zero (corr is not read).
 hipError_t LaunchGlmLinearSolve(uint32_t nv, const double *sums, uint32_t kp, uint32_t k, const double *gram,
-                                const double *corr, pgh_glm_row *rows, hipStream_t stream);
+                                const double *corr, pgh_glm_row *rows, hipStream_t stream,
+                                const uint8_t *x_const = nullptr);
 // Logistic: TOO_FEW_SAMPLES / CONST_ALLELE from the kp = 0 sums, beta = 0 for the others.
 hipError_t LaunchGlmLogisticInit(uint32_t nv, const double *sums, uint32_t kp, uint32_t k, GlmState *st, double *beta,
                                  pgh_glm_row *rows, hipStream_t stream);
@@ -109,5 +112,25 @@ constexpr uint32_t kGlmSparseLong = 1024;
 hipError_t LaunchGlmSparse(const SparseView &sv, uint32_t v_first, uint32_t nv, const double *y, const double *z,
                            uint32_t kp, uint32_t k, uint32_t n_y, const double *gram, double *sums, double *corr,
                            hipStream_t stream);
+
+// ---- pgh_burden_sparse (burden_sparse.hip): the linear fit's sums of a weighted burden per variant set ----
+// What the kernel leaves per set beside its sums row.
+struct BurdenAux {
+	double c;           // c_s = sum w_m val(b_m)
+	double sum_d;       // sums[s][1] again, for the row's mean
+	uint32_t n_nonzero; // samples with a phenotype and d_i != 0.0
+	uint32_t touched;   // samples with a phenotype and an entry in some member
+};
+// Bytes of the private vector one workgroup needs for `sample_ct` samples (a double and a visited mark each).
+uint64_t BurdenScratchPerGroup(uint32_t sample_ct);
+// For the sets s < n_sets (CSR: set_off / set_vidx name LOCAL rows of sv, weight may be null = 1.0):
+// sums[s][kp+4] = {n_y, sum d, sum d^2, sum d y, sum d z_j} in LaunchGlmSums' layout, aux[s], and x_const[s] = 1
+// iff min d == max d over the n_y samples with a phenotype (LaunchGlmLinearSolve's x_const).  y, z: raw-sample order,
+// as for LaunchGlmSparse.  scratch: n_groups x BurdenScratchPerGroup bytes, ALL ZERO on entry and on exit;
+// counter: one uint32, zero on entry.  Nothing in the output depends on n_groups (>= 1).
+hipError_t LaunchBurdenSparse(const SparseView &sv, uint32_t n_sets, const uint64_t *set_off, const uint32_t *set_vidx,
+                              const double *weight, const double *y, const double *z, uint32_t kp, uint32_t k,
+                              uint32_t n_y, uint32_t n_groups, void *scratch, uint32_t *counter, double *sums,
+                              BurdenAux *aux, uint8_t *x_const, hipStream_t stream);
 
 } // namespace pgh

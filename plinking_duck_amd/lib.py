@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = [
     "pgh_reader_unpack_start", "pgh_reader_unpack_wait", "pgh_get_2bit", "pgh_get_counts", "pgh_get_missingness", "pgh_get_int8", "pgh_get_dosage_f64", "pgh_get_phased",
     "pgh_tally_start", "pgh_tally_request", "pgh_tally_wait", "pgh_tally_counts", "pgh_tally_hwe_lnp",
     "pgh_tally_sample_missing", "pgh_tally_destroy", "pgh_tally_passes_started", "pgh_host_alloc", "pgh_host_free", "pgh_trim_device_cache",
-    "pgh_reader_error", "pgh_open_sparse", "pgh_get_sparse_info", "pgh_sparse_opens_started", "pgh_glm", "pgh_glm_multi", "pgh_glm_sparse", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
+    "pgh_reader_error", "pgh_open_sparse", "pgh_get_sparse_info", "pgh_sparse_opens_started", "pgh_glm", "pgh_glm_multi", "pgh_glm_sparse", "pgh_burden_sparse", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
     "pgh_king_counts", "pgh_king_table", "pgh_king_kinship",
     "pgh_ld_window_sums", "pgh_ld_prune", "pgh_ld_exceeds", "pgh_ld_scores", "pgh_ld_r2",
     "pgh_grm", "pgh_grm_standardize",
@@ -75,6 +75,13 @@ class PghGlmRow(C.Structure):
     ]
 
 
+class PghBurdenRow(C.Structure):
+    _fields_ = [
+        ("beta", C.c_double), ("se", C.c_double), ("stat", C.c_double), ("p", C.c_double), ("mean", C.c_double),
+        ("obs_ct", C.c_uint32), ("n_nonzero", C.c_uint32), ("errcode", C.c_uint8), ("pad", C.c_uint8 * 7),
+    ]
+
+
 # pgh_king_counts' planes, pgh_king_pair, and the kernel's tile of sample pairs (a test of tile edges names it)
 KING_NSNP, KING_HETHET, KING_IBS0, KING_HET1HOM2, KING_HET2HOM1, KING_PLANES = 0, 1, 2, 3, 4, 5
 KING_TILE = 128
@@ -95,6 +102,11 @@ GRM_TILE = 128
 GRM_BAND_ENV = "PGH_GRM_BAND_BYTES"
 GLM_ROW_DTYPE = np.dtype([("beta", "<f8"), ("se", "<f8"), ("stat", "<f8"), ("p", "<f8"), ("a1_freq", "<f8"),
                           ("obs_ct", "<u4"), ("errcode", "u1"), ("firth", "u1"), ("pad", "u1", (2,))])
+# pgh_burden_row, and the environment variable that bounds pgh_burden_sparse's device scratch (results do not depend
+# on it)
+BURDEN_ROW_DTYPE = np.dtype([("beta", "<f8"), ("se", "<f8"), ("stat", "<f8"), ("p", "<f8"), ("mean", "<f8"),
+                             ("obs_ct", "<u4"), ("n_nonzero", "<u4"), ("errcode", "u1"), ("pad", "u1", (7,))])
+BURDEN_SCRATCH_ENV = "PGH_BURDEN_SCRATCH_BYTES"
 
 
 class PghError(IOError):
@@ -213,6 +225,7 @@ def _load():
         "pgh_glm": (C.c_int, [vp, vp, u32, u32, vp, u32, vp, C.c_int, C.c_int, vp, cp]),
         "pgh_glm_multi": (C.c_int, [vp, vp, u32, u32, u32, vp, u32, vp, C.c_int, C.c_int, vp, cp]),
         "pgh_glm_sparse": (C.c_int, [vp, vp, u32, u32, vp, u32, vp, vp, cp]),
+        "pgh_burden_sparse": (C.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, cp]),
         "pgh_glm_p_from_t": (C.c_double, [C.c_double, C.c_double]),
         "pgh_glm_p_from_z": (C.c_double, [C.c_double]),
         "pgh_king_counts": (C.c_int, [vp, vp, u32, u32, vp, u32, u32, u32, u32, vp, cp]),
@@ -907,6 +920,50 @@ class Dataset:
             "errcode": np.array([GLM_ERRCODES[c] for c in rows["errcode"]], dtype=object),
             "firth": rows["firth"].astype(bool),
         }
+
+    def burden_sparse(self, phenotype, set_off, set_vidx, weights=None, covariates=None,
+                      subset: Subset | None = None) -> np.ndarray:
+        """pgh_burden_sparse: per variant set, the linear fit of phenotype on the weighted burden of the set's variants
+        plus covariates, over a sparse-resident dataset.  The sets are in CSR form: set s is
+        set_vidx[set_off[s]:set_off[s + 1]], indices into the dataset's resident variants (0 = v_begin), any order,
+        repeats counted; weights: None (1.0) or one per membership.  Returns one BURDEN_ROW_DTYPE row per set
+        (errcode: an index into GLM_ERRCODES)."""
+        n_out = subset.size if subset else self.n_samples
+        y = np.ascontiguousarray(phenotype, dtype=np.float64)
+        if y.shape != (n_out,):
+            raise ValueError(f"phenotype must hold one value per output sample ({n_out}), got shape {y.shape}")
+        if covariates is None:
+            z = np.zeros((0, n_out), dtype=np.float64)
+        else:
+            z = np.ascontiguousarray(np.atleast_2d(np.asarray(covariates, dtype=np.float64)))
+            if z.shape[1] != n_out:
+                raise ValueError(f"covariates must be n_covar x {n_out}, got shape {z.shape}")
+        off = np.asarray(set_off)
+        vidx = np.asarray(set_vidx)
+        for name, a in (("set_off", off), ("set_vidx", vidx)):
+            if a.ndim != 1 or (a.size and (a.dtype.kind not in "iu" or int(a.min()) < 0)):
+                raise ValueError(f"{name} must be a one-dimensional array of non-negative integers")
+        if off.size == 0:
+            raise ValueError("set_off must hold n_sets + 1 offsets")
+        if vidx.size and int(vidx.max()) > 0xFFFFFFFF:
+            raise ValueError("set_vidx holds an index that is not an unsigned 32-bit number")
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        vidx = np.ascontiguousarray(vidx, dtype=np.uint32)
+        n_sets = off.size - 1
+        # the library reads set_off[n_sets] memberships: the arrays must hold them (the rest is the library's to check)
+        if n_sets and np.all(off[1:] >= off[:-1]) and int(off[-1]) != vidx.size:
+            raise ValueError(f"set_vidx must hold set_off[-1] = {int(off[-1])} memberships, got {vidx.size}")
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64)
+            if w.shape != vidx.shape:
+                raise ValueError(f"weights must hold one value per membership ({vidx.size}), got shape {w.shape}")
+        rows = np.zeros(n_sets, dtype=BURDEN_ROW_DTYPE)
+        eb = _errbuf()
+        _check(_lib.pgh_burden_sparse(self._h, subset._h if subset else None, _ptr(y), z.shape[0],
+                                      _ptr(z) if z.size else None, n_sets, _ptr(off), _ptr(vidx) if vidx.size else None,
+                                      _ptr(w) if w is not None and w.size else None, _ptr(rows), eb), eb)
+        return rows
 
     def king_counts(self, v_begin: int | None = None, v_end: int | None = None, vidx=None,
                     subset: Subset | None = None, i_range=None, j_range=None) -> np.ndarray:
