@@ -2,6 +2,7 @@
 // window from the ordinary decoder (PghOpenRows of [w0, w1): every record type, LD bases before the window, .pgi
 // tables), each window's rows classified and compacted on the device, the window dropped, the windows' parts
 // concatenated at the end.  Peak device memory: the sparse data twice plus one window.
+// Also pgh_score_sparse, plink_score over such a dataset (kernels in score_sparse.hip).
 #include "api_internal.hpp"
 
 #include <atomic>
@@ -372,3 +373,185 @@ int CopyRowsToHost(const pgh_dataset *ds, uint32_t v_begin, uint32_t v_end, uint
 }
 
 } // namespace pgh_sparse
+
+namespace {
+
+// PGH_SCORE_SPARSE_SLICES (read at every call): the row slices per sample tile of pgh_score_sparse's walks, 0 or unset
+// = chosen from the list's entries.  The result does not depend on it.
+uint32_t ScoreSparseSlices() {
+	const char *s = std::getenv("PGH_SCORE_SPARSE_SLICES");
+	if (s && *s) {
+		char *end = nullptr;
+		const unsigned long v = std::strtoul(s, &end, 10);
+		if (end && *end == '\0') {
+			return static_cast<uint32_t>(std::min<unsigned long>(v, 65535));
+		}
+	}
+	return 0;
+}
+
+// pgh_score_sparse on one sparse-resident dataset, after the argument checks (n_scored >= 1).
+int ScoreSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t n_scored, const uint32_t *vidx,
+                   const double *weights, const uint8_t *flip, uint32_t n_cols, int mode, double *score_sum,
+                   double *dosage_sum, uint32_t *allele_ct, char *errbuf) {
+	PGH_ENTER(ds);
+	const uint32_t N = ds->sample_ct;
+	hipStream_t st = PghThreadStream();
+	std::vector<uint32_t> local(n_scored);
+	uint32_t l_min = UINT32_MAX, l_max = 0;
+	uint64_t dense_listed = 0;
+	for (uint32_t i = 0; i < n_scored; i++) {
+		const uint32_t l = vidx[i] - ds->v_begin;
+		local[i] = l;
+		l_min = std::min(l_min, l);
+		l_max = std::max(l_max, l);
+		dense_listed += ds->sp_dense_before[l + 1] - ds->sp_dense_before[l];
+	}
+	const uint32_t span = l_max - l_min + 1;
+	const uint64_t rows = std::max<uint64_t>(1, ds->v_end - ds->v_begin);
+	const uint64_t entries_hint = ds->sp_entry_ct * n_scored / rows + dense_listed * (N / 4);
+	// CENTER keeps no dosage sum (its td tables are zero): the output is 0.0, as pgh_score's
+	const bool track = dosage_sum && mode != PGH_SCORE_CENTER;
+
+	DevBuf d_score, d_dos, d_alc, work;
+	PGH_HIP(d_score.Alloc(8ull * N * n_cols), "hipMalloc(score_sparse out)");
+	if (track) {
+		PGH_HIP(d_dos.Alloc(8ull * N), "hipMalloc(score_sparse out)");
+	}
+	PGH_HIP(d_alc.Alloc(4ull * N), "hipMalloc(score_sparse out)");
+	auto up = [](uint64_t b) { return (b + 255) / 256 * 256; };
+	const uint64_t b_vlist = up(4ull * n_scored), b_w = up(8ull * n_scored * n_cols), b_flip = flip ? up(n_scored) : 0;
+	const uint64_t b_range = up(16ull * span), b_counts = up(16ull * n_scored), b_tab = up(32ull * n_scored);
+	const uint64_t b_ac = up(4ull * n_scored), b_part = up(16ull * (n_cols + 1ull) * pgh::kScoreSparseParts);
+	const uint64_t b_k0 = up(8ull * (n_cols + 1ull)), b_kexp = up(4ull * (n_cols + 1ull)), b_alc0 = 256;
+	// (not PghThreadScratch: CountsRangeDev below takes that block for the dense rows' counts)
+	PGH_HIP(work.Alloc(b_vlist + b_w + b_flip + b_range + b_counts + 2 * b_tab + b_ac + b_part + b_k0 + b_kexp + b_alc0),
+	        "hipMalloc(score_sparse)");
+	char *cur = work.As<char>();
+	auto take = [&](uint64_t b) {
+		char *p = cur;
+		cur += b;
+		return p;
+	};
+	uint32_t *d_vlist = reinterpret_cast<uint32_t *>(take(b_vlist));
+	double *d_w = reinterpret_cast<double *>(take(b_w));
+	uint8_t *d_flip = flip ? reinterpret_cast<uint8_t *>(take(b_flip)) : nullptr;
+	uint32_t *d_range = reinterpret_cast<uint32_t *>(take(b_range));
+	uint32_t *d_counts = reinterpret_cast<uint32_t *>(take(b_counts));
+	double *d_ts = reinterpret_cast<double *>(take(b_tab));
+	double *d_td = reinterpret_cast<double *>(take(b_tab));
+	uint32_t *d_ac = reinterpret_cast<uint32_t *>(take(b_ac));
+	double *d_part = reinterpret_cast<double *>(take(b_part));
+	double *d_k0 = reinterpret_cast<double *>(take(b_k0));
+	int32_t *d_kexp = reinterpret_cast<int32_t *>(take(b_kexp));
+	uint32_t *d_alc0 = reinterpret_cast<uint32_t *>(take(b_alc0));
+
+	std::vector<double> h_score(static_cast<size_t>(N) * n_cols), h_dos(track ? N : 0);
+	std::vector<uint32_t> h_ac(N);
+	HostSourceFence fence(st); // local and the caller's arrays feed asynchronous uploads, the three above take downloads
+	PGH_HIP(hipMemcpyAsync(d_vlist, local.data(), 4ull * n_scored, hipMemcpyHostToDevice, st), "score_sparse upload");
+	PGH_HIP(hipMemcpyAsync(d_w, weights, 8ull * n_scored * n_cols, hipMemcpyHostToDevice, st), "score_sparse upload");
+	if (flip) {
+		PGH_HIP(hipMemcpyAsync(d_flip, flip, n_scored, hipMemcpyHostToDevice, st), "score_sparse upload");
+	}
+	PGH_HIP(hipMemsetAsync(d_score.p, 0, 8ull * N * n_cols, st), "score_sparse clear");
+	if (track) {
+		PGH_HIP(hipMemsetAsync(d_dos.p, 0, 8ull * N, st), "score_sparse clear");
+	}
+	PGH_HIP(hipMemsetAsync(d_alc.p, 0, 4ull * N, st), "score_sparse clear");
+	// the subset's counts of the rows the list spans, the listed ones picked out, and the reference's tables from them
+	const int rc = pgh_sparse::CountsRangeDev(ds, subset, ds->v_begin + l_min, ds->v_begin + l_min + span, d_range, st,
+	                                          errbuf);
+	if (rc != PGH_OK) {
+		return rc;
+	}
+	PGH_HIP(pgh::LaunchScoreSparseGather(d_range, d_vlist, l_min, n_scored, d_counts, st), "score_sparse gather kernel");
+	PGH_HIP(pgh::LaunchScoreTables(d_counts, d_flip, n_scored, mode, d_ts, d_td, d_ac, st), "score table kernel");
+	PGH_HIP(pgh::LaunchScoreSparseStats(ds->Sparse(), d_vlist, n_scored, d_w, n_cols, d_ts, d_td, d_ac, d_part, d_k0,
+	                                    d_kexp, d_alc0, st),
+	        "score_sparse column kernels");
+	const uint32_t slices = ScoreSparseSlices();
+	for (uint32_t c0 = 0; c0 < n_cols; c0 += pgh::kScoreSparseChunk) {
+		const bool first = c0 == 0;
+		PGH_HIP(pgh::LaunchScoreSparse(ds->Sparse(), subset ? subset->d_include : nullptr, d_vlist, n_scored, d_w, n_cols,
+		                               c0, std::min(pgh::kScoreSparseChunk, n_cols - c0), d_ts, d_td, d_ac, d_kexp,
+		                               entries_hint, slices, d_score.As<unsigned long long>(),
+		                               first && track ? d_dos.As<unsigned long long>() : nullptr,
+		                               first ? d_alc.As<uint32_t>() : nullptr, st),
+		        "score_sparse entry kernel");
+	}
+	PGH_HIP(pgh::LaunchScoreSparseFlush(N, n_cols, d_k0, d_kexp, d_alc0, d_score.As<unsigned long long>(),
+	                                    track ? d_dos.As<unsigned long long>() : nullptr, d_alc.As<uint32_t>(), st),
+	        "score_sparse flush kernels");
+	PGH_HIP(hipMemcpyAsync(h_score.data(), d_score.p, 8ull * N * n_cols, hipMemcpyDeviceToHost, st), "score_sparse copy");
+	if (track) {
+		PGH_HIP(hipMemcpyAsync(h_dos.data(), d_dos.p, 8ull * N, hipMemcpyDeviceToHost, st), "score_sparse copy");
+	}
+	PGH_HIP(hipMemcpyAsync(h_ac.data(), d_alc.p, 4ull * N, hipMemcpyDeviceToHost, st), "score_sparse copy");
+	PGH_HIP(hipStreamSynchronize(st), "score_sparse sync");
+	Compact<double>(subset, h_score.data(), n_cols, score_sum, N);
+	if (track) {
+		Compact<double>(subset, h_dos.data(), 1, dosage_sum, N);
+	} else if (dosage_sum) {
+		std::fill_n(dosage_sum, subset ? subset->n_out : N, 0.0);
+	}
+	Compact<uint32_t>(subset, h_ac.data(), 1, allele_ct, N);
+	return PGH_OK;
+}
+
+} // namespace
+
+extern "C" int pgh_score_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32_t n_scored, const uint32_t *vidx,
+                                const double *weights, const uint8_t *flip, uint32_t n_cols, int mode, double *score_sum,
+                                double *dosage_sum, uint32_t *allele_ct, char *errbuf) {
+	if (!ds) {
+		SetErr(errbuf, "null dataset");
+		return PGH_ERR_ARG;
+	}
+	PGH_ONE_DEVICE(ds);
+	if (!ds->sparse) {
+		SetErr(errbuf, "needs a sparse-resident dataset (pgh_open_sparse)");
+		return PGH_ERR_ARG;
+	}
+	if (!score_sum || !allele_ct || (n_scored && (!vidx || !weights))) {
+		SetErr(errbuf, "null argument");
+		return PGH_ERR_ARG;
+	}
+	if (mode < 0 || mode > 2) {
+		SetErr(errbuf, "unknown score mode");
+		return PGH_ERR_ARG;
+	}
+	if (n_cols == 0 || n_cols > 4096) {
+		SetErr(errbuf, "n_cols must be between 1 and 4096");
+		return PGH_ERR_ARG;
+	}
+	const int rc = CheckSubset(ds, subset, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
+	}
+	for (uint32_t i = 0; i < n_scored; i++) {
+		if (vidx[i] < ds->v_begin || vidx[i] >= ds->v_end) {
+			SetErr(errbuf, "scored variant index outside the resident range");
+			return PGH_ERR_ARG;
+		}
+	}
+	const size_t total = static_cast<size_t>(n_scored) * n_cols;
+	for (size_t j = 0; j < total; j++) {
+		if (!std::isfinite(weights[j])) {
+			SetErr(errbuf, "non-finite weight at variant " + std::to_string(j / n_cols) + ", column " +
+			                   std::to_string(j % n_cols) + ": pgh_score_sparse accumulates in fixed point");
+			return PGH_ERR_ARG;
+		}
+	}
+	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct;
+	if (n_scored == 0) { // pgh_score's answer for an empty list
+		std::fill_n(score_sum, static_cast<size_t>(n_out) * n_cols, 0.0);
+		if (dosage_sum) {
+			std::fill_n(dosage_sum, n_out, 0.0);
+		}
+		std::fill_n(allele_ct, n_out, 0u);
+		return PGH_OK;
+	}
+	return ScoreSparseOne(ds, subset, n_scored, vidx, weights, flip, n_cols, mode, score_sum, dosage_sum, allele_ct,
+	                      errbuf);
+}

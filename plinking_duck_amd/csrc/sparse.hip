@@ -171,26 +171,6 @@ __global__ void __launch_bounds__(256) k_sparse_counts(const int32_t *row_of, co
 	}
 }
 
-// First index in [lo, hi) whose entry's sample is >= s0 (hi if none), by the whole wave: 64 probes per step.
-__device__ __forceinline__ uint64_t WaveLowerBound(const uint32_t *entries, uint64_t lo, uint64_t hi, uint32_t s0,
-                                                   uint32_t lane) {
-	while (hi - lo > 64) {
-		const uint64_t step = (hi - lo + 63) / 64;
-		const uint64_t p = lo + lane * step;
-		const bool below = p < hi && (entries[p] >> 2) < s0;
-		const uint32_t k = static_cast<uint32_t>(__popcll(__ballot(below))); // probes below s0: a prefix of the lanes
-		if (k == 0) {
-			return lo;
-		}
-		const uint64_t nlo = lo + (k - 1) * step + 1;
-		hi = std::min<uint64_t>(hi, lo + k * step);
-		lo = nlo;
-	}
-	const uint64_t p = lo + lane;
-	const bool below = p < hi && (entries[p] >> 2) < s0;
-	return lo + static_cast<uint64_t>(__popcll(__ballot(below)));
-}
-
 // Per-sample het / hom-alt / missing over the sparse rows.  A workgroup owns one tile of kSparseTile samples
 // (privatised in LDS) and a slice of the rows; each wave takes a row, finds the tile's first entry by a 64-way
 // search (the entries are sorted) and walks the tile's entries: +1 to the entry's class, -1 to the base class when

@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = [
     "pgh_reader_unpack_start", "pgh_reader_unpack_wait", "pgh_get_2bit", "pgh_get_counts", "pgh_get_missingness", "pgh_get_int8", "pgh_get_dosage_f64", "pgh_get_phased",
     "pgh_tally_start", "pgh_tally_request", "pgh_tally_wait", "pgh_tally_counts", "pgh_tally_hwe_lnp",
     "pgh_tally_sample_missing", "pgh_tally_destroy", "pgh_tally_passes_started", "pgh_host_alloc", "pgh_host_free", "pgh_trim_device_cache",
-    "pgh_reader_error", "pgh_open_sparse", "pgh_get_sparse_info", "pgh_sparse_opens_started", "pgh_glm", "pgh_glm_multi", "pgh_glm_sparse", "pgh_burden_sparse", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
+    "pgh_reader_error", "pgh_open_sparse", "pgh_get_sparse_info", "pgh_sparse_opens_started", "pgh_glm", "pgh_glm_multi", "pgh_glm_sparse", "pgh_burden_sparse", "pgh_score_sparse", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
     "pgh_king_counts", "pgh_king_table", "pgh_king_kinship",
     "pgh_ld_window_sums", "pgh_ld_prune", "pgh_ld_exceeds", "pgh_ld_scores", "pgh_ld_r2",
     "pgh_grm", "pgh_grm_standardize",
@@ -107,6 +107,12 @@ GLM_ROW_DTYPE = np.dtype([("beta", "<f8"), ("se", "<f8"), ("stat", "<f8"), ("p",
 BURDEN_ROW_DTYPE = np.dtype([("beta", "<f8"), ("se", "<f8"), ("stat", "<f8"), ("p", "<f8"), ("mean", "<f8"),
                              ("obs_ct", "<u4"), ("n_nonzero", "<u4"), ("errcode", "u1"), ("pad", "u1", (7,))])
 BURDEN_SCRATCH_ENV = "PGH_BURDEN_SCRATCH_BYTES"
+# pgh_score_sparse: weight columns per walk of the entries, the LDS bytes of a sample tile's accumulators (a tile holds
+# SCORE_SPARSE_ACC_BYTES // (8 * accumulators + 4) samples, rounded down to a multiple of 64) and the environment
+# variable that sets the row slices per tile (results do not depend on it)
+SCORE_SPARSE_CHUNK = 8
+SCORE_SPARSE_ACC_BYTES = 131072
+SCORE_SPARSE_SLICES_ENV = "PGH_SCORE_SPARSE_SLICES"
 
 
 class PghError(IOError):
@@ -226,6 +232,7 @@ def _load():
         "pgh_glm_multi": (C.c_int, [vp, vp, u32, u32, u32, vp, u32, vp, C.c_int, C.c_int, vp, cp]),
         "pgh_glm_sparse": (C.c_int, [vp, vp, u32, u32, vp, u32, vp, vp, cp]),
         "pgh_burden_sparse": (C.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, cp]),
+        "pgh_score_sparse": (C.c_int, [vp, vp, u32, vp, vp, vp, u32, C.c_int, vp, vp, vp, cp]),
         "pgh_glm_p_from_t": (C.c_double, [C.c_double, C.c_double]),
         "pgh_glm_p_from_z": (C.c_double, [C.c_double]),
         "pgh_king_counts": (C.c_int, [vp, vp, u32, u32, vp, u32, u32, u32, u32, vp, cp]),
@@ -964,6 +971,36 @@ class Dataset:
                                       _ptr(z) if z.size else None, n_sets, _ptr(off), _ptr(vidx) if vidx.size else None,
                                       _ptr(w) if w is not None and w.size else None, _ptr(rows), eb), eb)
         return rows
+
+    def score_sparse(self, vidx, weights, flip=None, mode: int = SCORE_MEAN_IMPUTE, subset: Subset | None = None,
+                     dosage_sum: bool = True):
+        """pgh_score_sparse: score() over a sparse-resident dataset (Dataset.open(..., sparse=True)), from the listed
+        variants' entries.  weights: n_scored finite values, or n_scored x n_cols.  Returns what score() returns:
+        (score_sum [n_out][n_cols], dosage_sum [n_out] or None, allele_ct [n_out])."""
+        v = np.asarray(vidx)
+        if v.ndim != 1 or (v.size and (v.dtype.kind not in "iu" or int(v.min()) < 0 or int(v.max()) > 0xFFFFFFFF)):
+            raise ValueError("vidx must be a one-dimensional array of unsigned 32-bit variant indices")
+        v = np.ascontiguousarray(v, dtype=np.uint32)
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.ndim == 1:
+            w = w.reshape(-1, 1)
+        if w.ndim != 2 or w.shape[0] != v.size:
+            raise ValueError(f"weights must be n_scored ({v.size}) values or n_scored x n_cols, got shape {w.shape}")
+        n_scored, n_cols = w.shape
+        flip_a = None
+        if flip is not None:
+            flip_a = np.ascontiguousarray(flip, dtype=np.uint8)
+            if flip_a.shape != (n_scored,):
+                raise ValueError(f"flip must hold one value per scored variant ({n_scored}), got shape {flip_a.shape}")
+        n_out = subset.size if subset else self.n_samples
+        score = np.zeros((n_out, n_cols), dtype=np.float64)
+        dos = np.zeros(n_out, dtype=np.float64) if dosage_sum else None
+        ac = np.zeros(n_out, dtype=np.uint32)
+        eb = _errbuf()
+        _check(_lib.pgh_score_sparse(self._h, subset._h if subset else None, n_scored, _ptr(v) if n_scored else None,
+                                     _ptr(w) if w.size else None, _ptr(flip_a) if n_scored and flip_a is not None else None,
+                                     n_cols, int(mode), _ptr(score), _ptr(dos), _ptr(ac), eb), eb)
+        return score, dos, ac
 
     def king_counts(self, v_begin: int | None = None, v_end: int | None = None, vidx=None,
                     subset: Subset | None = None, i_range=None, j_range=None) -> np.ndarray:
