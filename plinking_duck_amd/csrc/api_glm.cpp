@@ -15,16 +15,40 @@ namespace {
 constexpr uint32_t kGlmChunk = 16384;
 constexpr uint64_t kGlmDosageBytes = 512ull << 20;
 
-int GlmOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end, const double *phenotype,
-           uint32_t k, const double *covariates, int model, int firth, pgh_glm_row *out, char *errbuf) {
-	PGH_ENTER(ds);
-	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct;
-	const uint32_t nv_all = v_end - v_begin;
-	const uint32_t kp = pgh::GlmPadCovar(k);
-	hipStream_t st = PghThreadStream();
+// The mean of y over its n_y samples with a value (NaN = missing).  One pass in sample order, here and in every sum
+// of GlmStage: the entry points agree bit for bit only because they all sum in this order.
+double GlmMean(const double *y, uint32_t n_out, uint32_t n_y) {
+	double my = 0.0;
+	for (uint32_t i = 0; i < n_out; i++) {
+		my += std::isnan(y[i]) ? 0.0 : y[i];
+	}
+	return my / (n_y ? n_y : 1u);
+}
 
-	// host staging: y (NaN = missing) and z sample-major, zero padded to kp columns
-	std::vector<double> hz(static_cast<size_t>(n_out) * kp, 0.0);
+// y and z of a fit as the kernels read them: hy the phenotype (NaN = missing), hz the covariates sample-major and zero
+// padded to kp columns; and, for the kernels whose entries name raw samples, the same in raw-sample order with NaN y
+// outside the subset (hy_raw, hz_raw: only with a subset -- without one the two orders are one).
+struct GlmStaged {
+	std::vector<double> hy, hz, hy_raw, hz_raw;
+	uint32_t n_y = 0, kp = 0;
+	bool raw = false; // hy_raw, hz_raw are staged
+};
+
+// What GlmStage centres on its mean over the samples with a phenotype.  kYZ, the linear fit: y and the covariates; the
+// intercept absorbs the shift, so beta, SE and RSS are unchanged, and the whole-call Gram minus a variant's correction
+// Gram then subtracts numbers of the data's spread rather than of its offset.  kZ, pgh_glm_multi's linear fit: the
+// covariates over the samples of a missing-value pattern, hy being the pattern itself (every phenotype of the pattern
+// is centred on its own mean as its block is staged).  kNone: the logistic fit.
+enum class GlmCentre { kNone, kZ, kYZ };
+
+GlmStaged GlmStage(const pgh_dataset *ds, const pgh_subset *subset, const double *phenotype, uint32_t k,
+                   const double *covariates, GlmCentre centre, bool raw_order) {
+	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct, n_raw = ds->sample_ct;
+	const uint32_t kp = pgh::GlmPadCovar(k);
+	GlmStaged sg;
+	sg.kp = kp;
+	std::vector<double> &hz = sg.hz, &hy = sg.hy;
+	hz.assign(static_cast<size_t>(n_out) * kp, 0.0);
 	for (uint32_t j = 0; j < k; j++) {
 		for (uint32_t i = 0; i < n_out; i++) {
 			hz[static_cast<size_t>(i) * kp + j] = covariates[static_cast<size_t>(j) * n_out + i];
@@ -34,18 +58,14 @@ int GlmOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, ui
 	for (uint32_t i = 0; i < n_out; i++) {
 		n_y += std::isnan(phenotype[i]) ? 0u : 1u;
 	}
-	// Linear: y and the covariates centred on their means over the samples with a phenotype.  The intercept absorbs
-	// the shift, so beta, SE and RSS are unchanged, and the whole-call Gram minus a variant's correction Gram then
-	// subtracts numbers of the data's spread rather than of its offset.
-	std::vector<double> hy(phenotype, phenotype + n_out);
-	if (model == PGH_GLM_LINEAR && n_y) {
-		double my = 0.0;
-		for (uint32_t i = 0; i < n_out; i++) {
-			my += std::isnan(hy[i]) ? 0.0 : hy[i];
-		}
-		my /= n_y;
-		for (uint32_t i = 0; i < n_out; i++) {
-			hy[i] -= my;
+	sg.n_y = n_y;
+	hy.assign(phenotype, phenotype + n_out);
+	if (centre != GlmCentre::kNone && n_y) {
+		if (centre == GlmCentre::kYZ) {
+			const double my = GlmMean(hy.data(), n_out, n_y);
+			for (uint32_t i = 0; i < n_out; i++) {
+				hy[i] -= my;
+			}
 		}
 		for (uint32_t j = 0; j < k; j++) {
 			double mz = 0.0;
@@ -58,91 +78,160 @@ int GlmOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, ui
 			}
 		}
 	}
-	// which resident variants carry a dosage track
-	std::vector<int32_t> slot_all(nv_all, -1);
-	for (uint32_t v = v_begin; v < v_end && ds->dos_rows; v++) {
-		if (ds->dos_row_of[v - ds->v_begin] >= 0) {
-			slot_all[v - v_begin] = 0;
+	if (subset && raw_order) {
+		sg.raw = true;
+		sg.hy_raw.assign(n_raw, std::nan(""));
+		sg.hz_raw.assign(static_cast<size_t>(n_raw) * kp, 0.0);
+		for (uint32_t i = 0; i < n_out; i++) {
+			const uint32_t s = subset->sel[i];
+			sg.hy_raw[s] = hy[i];
+			std::copy_n(hz.data() + static_cast<size_t>(i) * kp, kp, sg.hz_raw.data() + static_cast<size_t>(s) * kp);
 		}
 	}
-	const bool any_dos = std::any_of(slot_all.begin(), slot_all.end(), [](int32_t s) { return s >= 0; });
-	uint32_t chunk = std::min(kGlmChunk, std::max(1u, nv_all));
-	if (any_dos) {
-		chunk = static_cast<uint32_t>(std::min<uint64_t>(chunk, std::max<uint64_t>(1, kGlmDosageBytes / (8ull * std::max(1u, n_out)))));
+	return sg;
+}
+
+// Uploads sg's y and z to d_y / d_z and, where sg holds the raw-order copies, those to d_yr / d_zr.  sg must outlive
+// the copies (the caller's HostSourceFence).  `who` and `y_name` go into the error text.
+int GlmUpload(const GlmStaged &sg, double *d_y, double *d_z, double *d_yr, double *d_zr, hipStream_t st, const char *who,
+              const char *y_name, char *errbuf) {
+	const auto what = [&](const char *name, const char *tail) { return std::string(who) + " " + name + " upload" + tail; };
+	PGH_HIP(hipMemcpyAsync(d_y, sg.hy.data(), 8ull * sg.hy.size(), hipMemcpyHostToDevice, st), what(y_name, "").c_str());
+	if (sg.kp) {
+		PGH_HIP(hipMemcpyAsync(d_z, sg.hz.data(), 8ull * sg.hz.size(), hipMemcpyHostToDevice, st),
+		        what("covariate", "").c_str());
+	}
+	if (sg.raw) {
+		PGH_HIP(hipMemcpyAsync(d_yr, sg.hy_raw.data(), 8ull * sg.hy_raw.size(), hipMemcpyHostToDevice, st),
+		        what(y_name, " (raw order)").c_str());
+		if (sg.kp) {
+			PGH_HIP(hipMemcpyAsync(d_zr, sg.hz_raw.data(), 8ull * sg.hz_raw.size(), hipMemcpyHostToDevice, st),
+			        what("covariate", " (raw order)").c_str());
+		}
+	}
+	return PGH_OK;
+}
+
+// The dosage tracks of a call over the variants [v_begin, v_end) of a dense-resident dataset.  Its vectors feed
+// asynchronous uploads: declare it before the caller's HostSourceFence.
+struct GlmDosage {
+	const pgh_dataset *ds;
+	const pgh_subset *subset;
+	uint32_t v_begin, n_out;
+	std::vector<int32_t> slot_all; // per variant of the call: >= 0 with a track
+	bool any;
+	std::vector<int32_t> slot;   // per variant of a chunk: its row of the chunk's dense dosages, or -1
+	std::vector<uint32_t> vlist; // the chunk's variants with a track (resident row indices)
+
+	// Once per call: which variants carry a track; with any, *chunk shrinks until a chunk's dense dosage rows keep
+	// kGlmDosageBytes.
+	GlmDosage(const pgh_dataset *ds_, const pgh_subset *subset_, uint32_t v_begin_, uint32_t v_end, uint32_t *chunk)
+	    : ds(ds_), subset(subset_), v_begin(v_begin_), n_out(subset_ ? subset_->n_out : ds_->sample_ct),
+	      slot_all(v_end - v_begin_, -1) {
+		for (uint32_t v = v_begin; v < v_end && ds->dos_rows; v++) {
+			if (ds->dos_row_of[v - ds->v_begin] >= 0) {
+				slot_all[v - v_begin] = 0;
+			}
+		}
+		any = std::any_of(slot_all.begin(), slot_all.end(), [](int32_t s) { return s >= 0; });
+		if (any) {
+			*chunk = static_cast<uint32_t>(
+			    std::min<uint64_t>(*chunk, std::max<uint64_t>(1, kGlmDosageBytes / (8ull * std::max(1u, n_out)))));
+		}
+		slot.resize(*chunk);
+		vlist.resize(*chunk);
 	}
 
+	// Per chunk: *g for the nv variants from c0 of the call, their tracks unpacked into d_dos (d_slot: each variant's
+	// row there) when the chunk has any.
+	int Chunk(uint32_t c0, uint32_t nv, int32_t *d_slot, uint32_t *d_list, double *d_dos, hipStream_t st, const char *who,
+	          pgh::GlmX *g, char *errbuf) {
+		*g = pgh::GlmX {};
+		g->view = ds->View();
+		g->v0 = v_begin + c0 - ds->v_begin;
+		g->n_out = n_out;
+		g->sel = subset ? subset->d_sel : nullptr;
+		uint32_t n_dos = 0;
+		if (any) {
+			for (uint32_t i = 0; i < nv; i++) {
+				slot[i] = slot_all[c0 + i] >= 0 ? static_cast<int32_t>(n_dos) : -1;
+				if (slot[i] >= 0) {
+					vlist[n_dos++] = g->v0 + i;
+				}
+			}
+		}
+		if (n_dos) {
+			const std::string w(who);
+			PGH_HIP(hipMemcpyAsync(d_slot, slot.data(), 4ull * nv, hipMemcpyHostToDevice, st),
+			        (w + " slot upload").c_str());
+			PGH_HIP(hipMemcpyAsync(d_list, vlist.data(), 4ull * n_dos, hipMemcpyHostToDevice, st),
+			        (w + " dosage list upload").c_str());
+			PGH_HIP(pgh::LaunchDosageUnpack(ds->View(), ds->Dosage(), 0, d_list, n_dos, g->sel, n_out, d_dos, n_out, st),
+			        (w + " dosage unpack").c_str());
+			g->slot = d_slot;
+			g->dos = d_dos;
+		}
+		return PGH_OK;
+	}
+};
+
+int GlmOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end, const double *phenotype,
+           uint32_t k, const double *covariates, int model, int firth, pgh_glm_row *out, char *errbuf) {
+	PGH_ENTER(ds);
+	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct;
+	const uint32_t nv_all = v_end - v_begin;
+	const uint32_t kp = pgh::GlmPadCovar(k);
+	hipStream_t st = PghThreadStream();
+
 	const bool logistic = model == PGH_GLM_LOGISTIC;
+	const GlmStaged sg = GlmStage(ds, subset, phenotype, k, covariates, logistic ? GlmCentre::kNone : GlmCentre::kYZ, false);
+	const uint32_t n_y = sg.n_y;
+	uint32_t chunk = std::min(kGlmChunk, std::max(1u, nv_all));
+	GlmDosage dos(ds, subset, v_begin, v_end, &chunk);
+
 	const uint32_t ns = kp + 4, q = k + 2, ne_gram = q * (q + 1) / 2;
 	const uint32_t ne_irls = pgh::GlmIrlsEntries(kp), pp = kp + 2;
-	const uint64_t hm = static_cast<uint64_t>(pgh::kGlmMaxP) * pgh::kGlmMaxP;
-	// one scratch block, carved in 256-byte pieces
-	auto up = [](uint64_t b) { return (b + 255) / 256 * 256; };
-	const uint64_t b_y = up(8ull * n_out), b_z = up(8ull * n_out * kp + 8), b_gram = up(8ull * ne_gram);
-	const uint64_t b_sums = up(8ull * chunk * ns), b_corr = up(8ull * chunk * ne_gram);
-	const uint64_t b_rows = up(sizeof(pgh_glm_row) * chunk), b_slot = up(4ull * chunk), b_list = up(4ull * chunk);
-	const uint64_t b_st = logistic ? up(sizeof(pgh::GlmState) * chunk) : 0, b_beta = logistic ? up(8ull * chunk * pp) : 0;
-	const uint64_t b_acc = logistic ? up(8ull * chunk * ne_irls) : 0, b_hm = logistic ? up(8ull * chunk * hm) : 0;
-	const uint64_t b_h0 = logistic && firth ? up(8ull * chunk * pp * pp) : 0;
-	const uint64_t b_dos = any_dos ? up(8ull * chunk * n_out) : 0;
-	const uint64_t total = b_y + b_z + b_gram + b_sums + b_corr + b_rows + b_slot + b_list + b_st + b_beta + b_acc + b_hm +
-	                       b_h0 + b_dos;
+	const uint64_t hm = static_cast<uint64_t>(pgh::kGlmMaxP) * pgh::kGlmMaxP, n = n_out, c = chunk;
+	double *d_y, *d_z, *d_gram, *d_sums, *d_corr, *d_beta, *d_acc, *d_hm, *d_h0, *d_dos;
+	pgh_glm_row *d_rows;
+	int32_t *d_slot;
+	uint32_t *d_list;
+	pgh::GlmState *d_st;
+	ScratchLayout lay;
+	lay.Add(&d_y, n);
+	lay.Add(&d_z, n * kp + 1); // one element of slack
+	lay.Add(&d_gram, ne_gram);
+	lay.Add(&d_sums, c * ns);
+	lay.Add(&d_corr, c * ne_gram);
+	lay.Add(&d_rows, c);
+	lay.Add(&d_slot, c);
+	lay.Add(&d_list, c);
+	lay.Add(&d_st, c, logistic);
+	lay.Add(&d_beta, c * pp, logistic);
+	lay.Add(&d_acc, c * ne_irls, logistic);
+	lay.Add(&d_hm, c * hm, logistic);
+	lay.Add(&d_h0, c * pp * pp, logistic && firth);
+	lay.Add(&d_dos, c * n, dos.any);
 	void *scratch = nullptr;
-	PGH_HIP(PghThreadScratch(total, st, &scratch), "glm scratch");
-	char *cur = static_cast<char *>(scratch);
-	auto take = [&](uint64_t b) {
-		char *p = cur;
-		cur += b;
-		return p;
-	};
-	double *d_y = reinterpret_cast<double *>(take(b_y));
-	double *d_z = reinterpret_cast<double *>(take(b_z));
-	double *d_gram = reinterpret_cast<double *>(take(b_gram));
-	double *d_sums = reinterpret_cast<double *>(take(b_sums));
-	double *d_corr = reinterpret_cast<double *>(take(b_corr));
-	pgh_glm_row *d_rows = reinterpret_cast<pgh_glm_row *>(take(b_rows));
-	int32_t *d_slot = reinterpret_cast<int32_t *>(take(b_slot));
-	uint32_t *d_list = reinterpret_cast<uint32_t *>(take(b_list));
-	pgh::GlmState *d_st = reinterpret_cast<pgh::GlmState *>(take(b_st));
-	double *d_beta = reinterpret_cast<double *>(take(b_beta));
-	double *d_acc = reinterpret_cast<double *>(take(b_acc));
-	double *d_hm = reinterpret_cast<double *>(take(b_hm));
-	double *d_h0 = reinterpret_cast<double *>(take(b_h0));
-	double *d_dos = reinterpret_cast<double *>(take(b_dos));
+	PGH_HIP(PghThreadScratch(lay.total, st, &scratch), "glm scratch");
+	lay.Bind(scratch);
 
-	std::vector<int32_t> slot(chunk);
-	std::vector<uint32_t> vlist(chunk), flist;
+	std::vector<uint32_t> flist;
 	std::vector<pgh::GlmState> hst;
-	HostSourceFence fence(st); // hy, hz, slot, vlist, flist feed asynchronous uploads
-	PGH_HIP(hipMemcpyAsync(d_y, hy.data(), 8ull * n_out, hipMemcpyHostToDevice, st), "glm phenotype upload");
-	if (kp) {
-		PGH_HIP(hipMemcpyAsync(d_z, hz.data(), 8ull * n_out * kp, hipMemcpyHostToDevice, st), "glm covariate upload");
+	HostSourceFence fence(st); // sg, dos, flist feed asynchronous uploads
+	int rc = GlmUpload(sg, d_y, d_z, nullptr, nullptr, st, "glm", "phenotype", errbuf);
+	if (rc != PGH_OK) {
+		return rc;
 	}
 	if (!logistic) {
 		PGH_HIP(pgh::LaunchGlmGram(nullptr, 1, nullptr, 0, n_y, n_out, d_y, d_z, kp, k, d_gram, st), "glm gram kernel");
 	}
 	for (uint32_t c0 = 0; c0 < nv_all; c0 += chunk) {
 		const uint32_t nv = std::min(chunk, nv_all - c0);
-		pgh::GlmX g {};
-		g.view = ds->View();
-		g.v0 = v_begin + c0 - ds->v_begin;
-		g.n_out = n_out;
-		g.sel = subset ? subset->d_sel : nullptr;
-		uint32_t n_dos = 0;
-		if (any_dos) {
-			for (uint32_t i = 0; i < nv; i++) {
-				slot[i] = slot_all[c0 + i] >= 0 ? static_cast<int32_t>(n_dos) : -1;
-				if (slot[i] >= 0) {
-					vlist[n_dos++] = g.v0 + i;
-				}
-			}
-		}
-		if (n_dos) {
-			PGH_HIP(hipMemcpyAsync(d_slot, slot.data(), 4ull * nv, hipMemcpyHostToDevice, st), "glm slot upload");
-			PGH_HIP(hipMemcpyAsync(d_list, vlist.data(), 4ull * n_dos, hipMemcpyHostToDevice, st), "glm dosage list upload");
-			PGH_HIP(pgh::LaunchDosageUnpack(ds->View(), ds->Dosage(), 0, d_list, n_dos, g.sel, n_out, d_dos, n_out, st),
-			        "glm dosage unpack");
-			g.slot = d_slot;
-			g.dos = d_dos;
+		pgh::GlmX g;
+		rc = dos.Chunk(c0, nv, d_slot, d_list, d_dos, st, "glm", &g, errbuf);
+		if (rc != PGH_OK) {
+			return rc;
 		}
 		if (!logistic) {
 			PGH_HIP(pgh::LaunchGlmSums(g, nv, d_y, d_z, kp, d_sums, st), "glm sums kernel");
@@ -245,95 +334,56 @@ int GlmMultiLinear(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_b
 	const uint32_t np = static_cast<uint32_t>(idx.size());
 	hipStream_t st = PghThreadStream();
 
-	const double *ypat = phenotypes + static_cast<size_t>(idx[0]) * n_out; // NaN exactly at the pattern
-	std::vector<double> hz(static_cast<size_t>(n_out) * kp, 0.0);
-	for (uint32_t j = 0; j < k; j++) {
-		for (uint32_t i = 0; i < n_out; i++) {
-			hz[static_cast<size_t>(i) * kp + j] = covariates[static_cast<size_t>(j) * n_out + i];
-		}
-	}
-	uint32_t n_y = 0;
-	for (uint32_t i = 0; i < n_out; i++) {
-		n_y += std::isnan(ypat[i]) ? 0u : 1u;
-	}
-	if (n_y) {
-		for (uint32_t j = 0; j < k; j++) {
-			double mz = 0.0;
-			for (uint32_t i = 0; i < n_out; i++) {
-				mz += std::isnan(ypat[i]) ? 0.0 : hz[static_cast<size_t>(i) * kp + j];
-			}
-			mz /= n_y;
-			for (uint32_t i = 0; i < n_out; i++) {
-				hz[static_cast<size_t>(i) * kp + j] -= mz;
-			}
-		}
-	}
-	std::vector<int32_t> slot_all(nv_all, -1);
-	for (uint32_t v = v_begin; v < v_end && ds->dos_rows; v++) {
-		if (ds->dos_row_of[v - ds->v_begin] >= 0) {
-			slot_all[v - v_begin] = 0;
-		}
-	}
-	const bool any_dos = std::any_of(slot_all.begin(), slot_all.end(), [](int32_t s) { return s >= 0; });
+	// sg.hy: the group's first phenotype as it is, NaN exactly at the pattern
+	const GlmStaged sg = GlmStage(ds, subset, phenotypes + static_cast<size_t>(idx[0]) * n_out, k, covariates, GlmCentre::kZ,
+	                              false);
+	const uint32_t n_y = sg.n_y;
 
 	const uint32_t pb_max = std::min(pgh::kGlmMultiPb, np);
 	const uint32_t ns = kp + 4, q = k + 2, ne_gram = q * (q + 1) / 2, nes = (k + 1) * (k + 2) / 2;
 	const uint64_t per_variant = 8ull * (ns + nes) + static_cast<uint64_t>(pb_max) * (8 + 8 * q + sizeof(pgh_glm_row)) + 8;
 	uint32_t chunk = std::min(kGlmMultiChunk, std::max(1u, nv_all));
 	chunk = static_cast<uint32_t>(std::min<uint64_t>(chunk, std::max<uint64_t>(1, kGlmMultiChunkBytes / per_variant)));
-	if (any_dos) {
-		chunk = static_cast<uint32_t>(std::min<uint64_t>(chunk, std::max<uint64_t>(1, kGlmDosageBytes / (8ull * std::max(1u, n_out)))));
-	}
-	auto up = [](uint64_t b) { return (b + 255) / 256 * 256; };
-	const uint64_t b_pat = up(8ull * n_out), b_z = up(8ull * n_out * kp + 8), b_yb = up(8ull * n_out * pb_max);
-	const uint64_t b_gram = up(8ull * ne_gram), b_whole = up(8ull * pb_max * q), b_sums = up(8ull * chunk * ns);
-	const uint64_t b_sxy = up(8ull * chunk * pb_max), b_cs = up(8ull * chunk * nes), b_cp = up(8ull * chunk * pb_max * q);
-	const uint64_t b_rows = up(sizeof(pgh_glm_row) * chunk * pb_max), b_slot = up(4ull * chunk), b_list = up(4ull * chunk);
-	const uint64_t b_dos = any_dos ? up(8ull * chunk * n_out) : 0;
-	const uint64_t total = b_pat + b_z + b_yb + b_gram + b_whole + b_sums + b_sxy + b_cs + b_cp + b_rows + b_slot + b_list +
-	                       b_dos;
+	GlmDosage dos(ds, subset, v_begin, v_end, &chunk);
+
+	const uint64_t n = n_out, c = chunk;
+	double *d_pat, *d_z, *d_yb, *d_gram, *d_whole, *d_sums, *d_sxy, *d_cs, *d_cp, *d_dos;
+	pgh_glm_row *d_rows;
+	int32_t *d_slot;
+	uint32_t *d_list;
+	ScratchLayout lay;
+	lay.Add(&d_pat, n);
+	lay.Add(&d_z, n * kp + 1); // one element of slack
+	lay.Add(&d_yb, n * pb_max);
+	lay.Add(&d_gram, ne_gram);
+	lay.Add(&d_whole, static_cast<uint64_t>(pb_max) * q);
+	lay.Add(&d_sums, c * ns);
+	lay.Add(&d_sxy, c * pb_max);
+	lay.Add(&d_cs, c * nes);
+	lay.Add(&d_cp, c * pb_max * q);
+	lay.Add(&d_rows, c * pb_max);
+	lay.Add(&d_slot, c);
+	lay.Add(&d_list, c);
+	lay.Add(&d_dos, c * n, dos.any);
 	void *scratch = nullptr;
-	PGH_HIP(PghThreadScratch(total, st, &scratch), "glm_multi scratch");
-	char *cur = static_cast<char *>(scratch);
-	auto take = [&](uint64_t b) {
-		char *p = cur;
-		cur += b;
-		return p;
-	};
-	double *d_pat = reinterpret_cast<double *>(take(b_pat));
-	double *d_z = reinterpret_cast<double *>(take(b_z));
-	double *d_yb = reinterpret_cast<double *>(take(b_yb));
-	double *d_gram = reinterpret_cast<double *>(take(b_gram));
-	double *d_whole = reinterpret_cast<double *>(take(b_whole));
-	double *d_sums = reinterpret_cast<double *>(take(b_sums));
-	double *d_sxy = reinterpret_cast<double *>(take(b_sxy));
-	double *d_cs = reinterpret_cast<double *>(take(b_cs));
-	double *d_cp = reinterpret_cast<double *>(take(b_cp));
-	pgh_glm_row *d_rows = reinterpret_cast<pgh_glm_row *>(take(b_rows));
-	int32_t *d_slot = reinterpret_cast<int32_t *>(take(b_slot));
-	uint32_t *d_list = reinterpret_cast<uint32_t *>(take(b_list));
-	double *d_dos = reinterpret_cast<double *>(take(b_dos));
+	PGH_HIP(PghThreadScratch(lay.total, st, &scratch), "glm_multi scratch");
+	lay.Bind(scratch);
 
 	std::vector<double> hyb(static_cast<size_t>(n_out) * pb_max);
 	std::vector<pgh_glm_row> hrows(static_cast<size_t>(chunk) * pb_max);
-	std::vector<int32_t> slot(chunk);
-	std::vector<uint32_t> vlist(chunk);
-	HostSourceFence fence(st); // hz, hyb, slot, vlist feed asynchronous uploads
-	PGH_HIP(hipMemcpyAsync(d_pat, ypat, 8ull * n_out, hipMemcpyHostToDevice, st), "glm_multi pattern upload");
-	if (kp) {
-		PGH_HIP(hipMemcpyAsync(d_z, hz.data(), 8ull * n_out * kp, hipMemcpyHostToDevice, st), "glm_multi covariate upload");
+	HostSourceFence fence(st); // sg, dos, hyb feed asynchronous uploads
+	int rc = GlmUpload(sg, d_pat, d_z, nullptr, nullptr, st, "glm_multi", "pattern", errbuf);
+	if (rc != PGH_OK) {
+		return rc;
 	}
 	PGH_HIP(pgh::LaunchGlmGram(nullptr, 1, nullptr, 0, n_y, n_out, d_pat, d_z, kp, k, d_gram, st), "glm_multi gram kernel");
 	for (uint32_t b0 = 0; b0 < np; b0 += pb_max) {
 		const uint32_t pb = std::min(pb_max, np - b0);
 		// every upload of the previous block has completed: each chunk below ends with a stream synchronisation
 		for (uint32_t j = 0; j < pb; j++) {
+			// NaN becomes 0.0 here; GlmStage's single phenotype keeps its NaN
 			const double *y = phenotypes + static_cast<size_t>(idx[b0 + j]) * n_out;
-			double my = 0.0;
-			for (uint32_t i = 0; i < n_out; i++) {
-				my += std::isnan(y[i]) ? 0.0 : y[i];
-			}
-			my /= n_y ? n_y : 1u;
+			const double my = GlmMean(y, n_out, n_y);
 			double *dst = hyb.data() + static_cast<size_t>(j) * n_out;
 			for (uint32_t i = 0; i < n_out; i++) {
 				dst[i] = std::isnan(y[i]) ? 0.0 : y[i] - my;
@@ -343,28 +393,10 @@ int GlmMultiLinear(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_b
 		PGH_HIP(pgh::LaunchGlmMultiWhole(n_out, d_yb, pb, d_z, kp, k, d_whole, st), "glm_multi whole-call kernel");
 		for (uint32_t c0 = 0; c0 < nv_all; c0 += chunk) {
 			const uint32_t nv = std::min(chunk, nv_all - c0);
-			pgh::GlmX g {};
-			g.view = ds->View();
-			g.v0 = v_begin + c0 - ds->v_begin;
-			g.n_out = n_out;
-			g.sel = subset ? subset->d_sel : nullptr;
-			uint32_t n_dos = 0;
-			if (any_dos) {
-				for (uint32_t i = 0; i < nv; i++) {
-					slot[i] = slot_all[c0 + i] >= 0 ? static_cast<int32_t>(n_dos) : -1;
-					if (slot[i] >= 0) {
-						vlist[n_dos++] = g.v0 + i;
-					}
-				}
-			}
-			if (n_dos) {
-				PGH_HIP(hipMemcpyAsync(d_slot, slot.data(), 4ull * nv, hipMemcpyHostToDevice, st), "glm_multi slot upload");
-				PGH_HIP(hipMemcpyAsync(d_list, vlist.data(), 4ull * n_dos, hipMemcpyHostToDevice, st),
-				        "glm_multi dosage list upload");
-				PGH_HIP(pgh::LaunchDosageUnpack(ds->View(), ds->Dosage(), 0, d_list, n_dos, g.sel, n_out, d_dos, n_out, st),
-				        "glm_multi dosage unpack");
-				g.slot = d_slot;
-				g.dos = d_dos;
+			pgh::GlmX g;
+			rc = dos.Chunk(c0, nv, d_slot, d_list, d_dos, st, "glm_multi", &g, errbuf);
+			if (rc != PGH_OK) {
+				return rc;
 			}
 			PGH_HIP(pgh::LaunchGlmSums(g, nv, d_pat, d_z, kp, d_sums, st), "glm_multi sums kernel");
 			PGH_HIP(pgh::LaunchGlmMultiXy(g, nv, d_yb, pb, d_sxy, st), "glm_multi genotype x phenotype kernel");
@@ -437,9 +469,9 @@ int GlmCheckCommon(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_b
 		                   std::to_string(n_covar));
 		return PGH_ERR_ARG;
 	}
-	if (subset && subset->ds != ds) {
-		SetErr(errbuf, "sample subset belongs to a different dataset");
-		return PGH_ERR_ARG;
+	rc = CheckSubset(ds, subset, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
 	}
 	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct;
 	if ((n_out && !phenotypes) || (n_covar && n_out && !covariates) || (v_end > v_begin && !out)) {
@@ -464,64 +496,6 @@ int GlmCheckArgs(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_beg
 	return GlmCheckCommon(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, model, out, errbuf);
 }
 
-// y and z of a linear fit as the kernels read them: z sample-major and zero padded to kp columns, both centred over
-// the samples with a phenotype exactly as GlmOne's linear fit centres them; and, with a subset, the same in raw-sample
-// order with NaN y outside the subset, for the kernels whose entries name raw samples (empty without a subset: the
-// two orders are one).
-struct GlmStaged {
-	std::vector<double> hy, hz, hy_raw, hz_raw;
-	uint32_t n_y = 0;
-};
-
-GlmStaged GlmStageLinear(const pgh_dataset *ds, const pgh_subset *subset, const double *phenotype, uint32_t k,
-                         uint32_t kp, const double *covariates) {
-	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct, n_raw = ds->sample_ct;
-	GlmStaged sg;
-	std::vector<double> &hz = sg.hz, &hy = sg.hy;
-	hz.assign(static_cast<size_t>(n_out) * kp, 0.0);
-	for (uint32_t j = 0; j < k; j++) {
-		for (uint32_t i = 0; i < n_out; i++) {
-			hz[static_cast<size_t>(i) * kp + j] = covariates[static_cast<size_t>(j) * n_out + i];
-		}
-	}
-	uint32_t n_y = 0;
-	for (uint32_t i = 0; i < n_out; i++) {
-		n_y += std::isnan(phenotype[i]) ? 0u : 1u;
-	}
-	sg.n_y = n_y;
-	hy.assign(phenotype, phenotype + n_out);
-	if (n_y) {
-		double my = 0.0;
-		for (uint32_t i = 0; i < n_out; i++) {
-			my += std::isnan(hy[i]) ? 0.0 : hy[i];
-		}
-		my /= n_y;
-		for (uint32_t i = 0; i < n_out; i++) {
-			hy[i] -= my;
-		}
-		for (uint32_t j = 0; j < k; j++) {
-			double mz = 0.0;
-			for (uint32_t i = 0; i < n_out; i++) {
-				mz += std::isnan(hy[i]) ? 0.0 : hz[static_cast<size_t>(i) * kp + j];
-			}
-			mz /= n_y;
-			for (uint32_t i = 0; i < n_out; i++) {
-				hz[static_cast<size_t>(i) * kp + j] -= mz;
-			}
-		}
-	}
-	if (subset) {
-		sg.hy_raw.assign(n_raw, std::nan(""));
-		sg.hz_raw.assign(static_cast<size_t>(n_raw) * kp, 0.0);
-		for (uint32_t i = 0; i < n_out; i++) {
-			const uint32_t s = subset->sel[i];
-			sg.hy_raw[s] = hy[i];
-			std::copy_n(hz.data() + static_cast<size_t>(i) * kp, kp, sg.hz_raw.data() + static_cast<size_t>(s) * kp);
-		}
-	}
-	return sg;
-}
-
 // pgh_glm_sparse on one sparse-resident dataset.  y and z are staged twice when there is a subset: in output-sample
 // order for the dense kernels (the whole-call Gram and the dense-form rows), and in raw-sample order, NaN y outside
 // the subset, for the entry kernel, whose entries name raw samples.  Without a subset the two orders are one.
@@ -532,9 +506,7 @@ int GlmSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_beg
 	const uint32_t nv_all = v_end - v_begin;
 	const uint32_t kp = pgh::GlmPadCovar(k);
 	hipStream_t st = PghThreadStream();
-
-	const GlmStaged sg = GlmStageLinear(ds, subset, phenotype, k, kp, covariates);
-	const std::vector<double> &hy = sg.hy, &hz = sg.hz, &hy_raw = sg.hy_raw, &hz_raw = sg.hz_raw;
+	const GlmStaged sg = GlmStage(ds, subset, phenotype, k, covariates, GlmCentre::kYZ, true);
 	const uint32_t n_y = sg.n_y;
 
 	const uint32_t chunk = std::min(kGlmChunk, std::max(1u, nv_all));
@@ -546,47 +518,34 @@ int GlmSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_beg
 		dense_max = std::max(dense_max, ds->sp_dense_before[l1] - ds->sp_dense_before[l0]);
 	}
 	const uint32_t ns = kp + 4, q = k + 2, ne_gram = q * (q + 1) / 2;
-	auto up = [](uint64_t b) { return (b + 255) / 256 * 256; };
-	const uint64_t b_y = up(8ull * n_out), b_z = up(8ull * n_out * kp + 8), b_gram = up(8ull * ne_gram);
-	const uint64_t b_yr = subset ? up(8ull * n_raw) : 0, b_zr = subset ? up(8ull * n_raw * kp + 8) : 0;
-	const uint64_t b_sums = up(8ull * chunk * ns), b_corr = up(8ull * chunk * ne_gram);
-	const uint64_t b_rows = up(sizeof(pgh_glm_row) * chunk);
-	const uint64_t b_dsums = up(8ull * dense_max * ns), b_dcorr = up(8ull * dense_max * ne_gram);
-	const uint64_t b_drows = up(sizeof(pgh_glm_row) * dense_max);
-	const uint64_t total = b_y + b_z + b_gram + b_yr + b_zr + b_sums + b_corr + b_rows + b_dsums + b_dcorr + b_drows;
+	const uint64_t n = n_out, nr = n_raw, c = chunk, dm = dense_max;
+	double *d_y, *d_z, *d_gram, *d_yr, *d_zr, *d_sums, *d_corr, *d_dsums, *d_dcorr;
+	pgh_glm_row *d_rows, *d_drows;
+	ScratchLayout lay;
+	lay.Add(&d_y, n);
+	lay.Add(&d_z, n * kp + 1); // one element of slack, here and in d_zr
+	lay.Add(&d_gram, ne_gram);
+	lay.Add(&d_yr, nr, subset != nullptr);
+	lay.Add(&d_zr, nr * kp + 1, subset != nullptr);
+	lay.Add(&d_sums, c * ns);
+	lay.Add(&d_corr, c * ne_gram);
+	lay.Add(&d_rows, c);
+	lay.Add(&d_dsums, dm * ns);
+	lay.Add(&d_dcorr, dm * ne_gram);
+	lay.Add(&d_drows, dm);
 	void *scratch = nullptr;
-	PGH_HIP(PghThreadScratch(total, st, &scratch), "glm_sparse scratch");
-	char *cur = static_cast<char *>(scratch);
-	auto take = [&](uint64_t b) {
-		char *p = cur;
-		cur += b;
-		return p;
-	};
-	double *d_y = reinterpret_cast<double *>(take(b_y));
-	double *d_z = reinterpret_cast<double *>(take(b_z));
-	double *d_gram = reinterpret_cast<double *>(take(b_gram));
-	double *d_yr = subset ? reinterpret_cast<double *>(take(b_yr)) : d_y;
-	double *d_zr = subset ? reinterpret_cast<double *>(take(b_zr)) : d_z;
-	double *d_sums = reinterpret_cast<double *>(take(b_sums));
-	double *d_corr = reinterpret_cast<double *>(take(b_corr));
-	pgh_glm_row *d_rows = reinterpret_cast<pgh_glm_row *>(take(b_rows));
-	double *d_dsums = reinterpret_cast<double *>(take(b_dsums));
-	double *d_dcorr = reinterpret_cast<double *>(take(b_dcorr));
-	pgh_glm_row *d_drows = reinterpret_cast<pgh_glm_row *>(take(b_drows));
+	PGH_HIP(PghThreadScratch(lay.total, st, &scratch), "glm_sparse scratch");
+	lay.Bind(scratch);
+	if (!subset) {
+		d_yr = d_y;
+		d_zr = d_z;
+	}
 
 	std::vector<pgh_glm_row> hdrows(dense_max);
-	HostSourceFence fence(st); // hy, hz, hy_raw, hz_raw feed asynchronous uploads
-	PGH_HIP(hipMemcpyAsync(d_y, hy.data(), 8ull * n_out, hipMemcpyHostToDevice, st), "glm_sparse phenotype upload");
-	if (kp) {
-		PGH_HIP(hipMemcpyAsync(d_z, hz.data(), 8ull * n_out * kp, hipMemcpyHostToDevice, st), "glm_sparse covariate upload");
-	}
-	if (subset) {
-		PGH_HIP(hipMemcpyAsync(d_yr, hy_raw.data(), 8ull * n_raw, hipMemcpyHostToDevice, st),
-		        "glm_sparse phenotype upload (raw order)");
-		if (kp) {
-			PGH_HIP(hipMemcpyAsync(d_zr, hz_raw.data(), 8ull * n_raw * kp, hipMemcpyHostToDevice, st),
-			        "glm_sparse covariate upload (raw order)");
-		}
+	HostSourceFence fence(st); // sg feeds asynchronous uploads
+	const int rc = GlmUpload(sg, d_y, d_z, d_yr, d_zr, st, "glm_sparse", "phenotype", errbuf);
+	if (rc != PGH_OK) {
+		return rc;
 	}
 	PGH_HIP(pgh::LaunchGlmGram(nullptr, 1, nullptr, 0, n_y, n_out, d_y, d_z, kp, k, d_gram, st), "glm_sparse gram kernel");
 	for (uint32_t c0 = 0; c0 < nv_all; c0 += chunk) {
@@ -649,7 +608,7 @@ int BurdenSparseOne(const pgh_dataset *ds, const pgh_subset *subset, const doubl
 	const uint32_t kp = pgh::GlmPadCovar(k);
 	const uint64_t n_memb = set_off[n_sets];
 	hipStream_t st = PghThreadStream();
-	const GlmStaged sg = GlmStageLinear(ds, subset, phenotype, k, kp, covariates);
+	const GlmStaged sg = GlmStage(ds, subset, phenotype, k, covariates, GlmCentre::kYZ, true);
 	const uint32_t n_y = sg.n_y;
 
 	// the grid: a private vector per workgroup within the byte budget, at most eight workgroups per compute unit
@@ -664,50 +623,41 @@ int BurdenSparseOne(const pgh_dataset *ds, const pgh_subset *subset, const doubl
 	PGH_HIP(vectors.Alloc(per_group * n_groups), "burden_sparse vectors");
 
 	const uint32_t ns = kp + 4, q = k + 2, ne_gram = q * (q + 1) / 2;
-	auto up = [](uint64_t b) { return (b + 255) / 256 * 256; };
-	const uint64_t b_y = up(8ull * n_out), b_z = up(8ull * n_out * kp + 8), b_gram = up(8ull * ne_gram);
-	const uint64_t b_yr = subset ? up(8ull * n_raw) : 0, b_zr = subset ? up(8ull * n_raw * kp + 8) : 0;
-	const uint64_t b_off = up(8ull * (n_sets + 1ull)), b_vidx = up(4ull * n_memb + 4), b_w = weight ? up(8ull * n_memb + 8) : 0;
-	const uint64_t b_ctr = 256, b_sums = up(8ull * n_sets * ns), b_aux = up(sizeof(pgh::BurdenAux) * n_sets);
-	const uint64_t b_flag = up(n_sets), b_rows = up(sizeof(pgh_glm_row) * n_sets);
-	const uint64_t total = b_y + b_z + b_gram + b_yr + b_zr + b_off + b_vidx + b_w + b_ctr + b_sums + b_aux + b_flag + b_rows;
+	const uint64_t n = n_out, nr = n_raw, nsets = n_sets, ctr_bytes = 256;
+	double *d_y, *d_z, *d_gram, *d_yr, *d_zr, *d_w, *d_sums;
+	uint64_t *d_off;
+	uint32_t *d_vidx, *d_ctr;
+	pgh::BurdenAux *d_aux;
+	uint8_t *d_flag;
+	pgh_glm_row *d_rows;
+	ScratchLayout lay;
+	lay.Add(&d_y, n);
+	lay.Add(&d_z, n * kp + 1); // one element of slack, here and in d_zr, d_vidx, d_w
+	lay.Add(&d_gram, ne_gram);
+	lay.Add(&d_yr, nr, subset != nullptr);
+	lay.Add(&d_zr, nr * kp + 1, subset != nullptr);
+	lay.Add(&d_off, nsets + 1);
+	lay.Add(&d_vidx, n_memb + 1);
+	lay.Add(&d_w, n_memb + 1, weight != nullptr);
+	lay.Add(&d_ctr, ctr_bytes / 4);
+	lay.Add(&d_sums, nsets * ns);
+	lay.Add(&d_aux, nsets);
+	lay.Add(&d_flag, nsets);
+	lay.Add(&d_rows, nsets);
 	void *scratch = nullptr;
-	PGH_HIP(PghThreadScratch(total, st, &scratch), "burden_sparse scratch");
-	char *cur = static_cast<char *>(scratch);
-	auto take = [&](uint64_t b) {
-		char *p = cur;
-		cur += b;
-		return p;
-	};
-	double *d_y = reinterpret_cast<double *>(take(b_y));
-	double *d_z = reinterpret_cast<double *>(take(b_z));
-	double *d_gram = reinterpret_cast<double *>(take(b_gram));
-	double *d_yr = subset ? reinterpret_cast<double *>(take(b_yr)) : d_y;
-	double *d_zr = subset ? reinterpret_cast<double *>(take(b_zr)) : d_z;
-	uint64_t *d_off = reinterpret_cast<uint64_t *>(take(b_off));
-	uint32_t *d_vidx = reinterpret_cast<uint32_t *>(take(b_vidx));
-	double *d_w = weight ? reinterpret_cast<double *>(take(b_w)) : nullptr;
-	uint32_t *d_ctr = reinterpret_cast<uint32_t *>(take(b_ctr));
-	double *d_sums = reinterpret_cast<double *>(take(b_sums));
-	pgh::BurdenAux *d_aux = reinterpret_cast<pgh::BurdenAux *>(take(b_aux));
-	uint8_t *d_flag = reinterpret_cast<uint8_t *>(take(b_flag));
-	pgh_glm_row *d_rows = reinterpret_cast<pgh_glm_row *>(take(b_rows));
+	PGH_HIP(PghThreadScratch(lay.total, st, &scratch), "burden_sparse scratch");
+	lay.Bind(scratch);
+	if (!subset) {
+		d_yr = d_y;
+		d_zr = d_z;
+	}
 
 	std::vector<pgh_glm_row> rows(n_sets);
 	std::vector<pgh::BurdenAux> aux(n_sets);
 	HostSourceFence fence(st); // sg's vectors and the caller's set arrays feed asynchronous uploads
-	PGH_HIP(hipMemcpyAsync(d_y, sg.hy.data(), 8ull * n_out, hipMemcpyHostToDevice, st), "burden_sparse phenotype upload");
-	if (kp) {
-		PGH_HIP(hipMemcpyAsync(d_z, sg.hz.data(), 8ull * n_out * kp, hipMemcpyHostToDevice, st),
-		        "burden_sparse covariate upload");
-	}
-	if (subset) {
-		PGH_HIP(hipMemcpyAsync(d_yr, sg.hy_raw.data(), 8ull * n_raw, hipMemcpyHostToDevice, st),
-		        "burden_sparse phenotype upload (raw order)");
-		if (kp) {
-			PGH_HIP(hipMemcpyAsync(d_zr, sg.hz_raw.data(), 8ull * n_raw * kp, hipMemcpyHostToDevice, st),
-			        "burden_sparse covariate upload (raw order)");
-		}
+	const int rc = GlmUpload(sg, d_y, d_z, d_yr, d_zr, st, "burden_sparse", "phenotype", errbuf);
+	if (rc != PGH_OK) {
+		return rc;
 	}
 	PGH_HIP(hipMemcpyAsync(d_off, set_off, 8ull * (n_sets + 1ull), hipMemcpyHostToDevice, st), "burden_sparse set upload");
 	if (n_memb) {
@@ -718,7 +668,7 @@ int BurdenSparseOne(const pgh_dataset *ds, const pgh_subset *subset, const doubl
 	}
 	// zeroed at every call: nothing is assumed of what an earlier call, or another user of the block, left there
 	PGH_HIP(hipMemsetAsync(vectors.p, 0, per_group * n_groups, st), "burden_sparse vectors clear");
-	PGH_HIP(hipMemsetAsync(d_ctr, 0, b_ctr, st), "burden_sparse counter clear");
+	PGH_HIP(hipMemsetAsync(d_ctr, 0, ctr_bytes, st), "burden_sparse counter clear");
 	PGH_HIP(pgh::LaunchGlmGram(nullptr, 1, nullptr, 0, n_y, n_out, d_y, d_z, kp, k, d_gram, st), "burden_sparse gram kernel");
 	PGH_HIP(pgh::LaunchBurdenSparse(ds->Sparse(), n_sets, d_off, d_vidx, d_w, d_yr, d_zr, kp, k, n_y, n_groups, vectors.p,
 	                                d_ctr, d_sums, d_aux, d_flag, st),
@@ -759,28 +709,17 @@ extern "C" double pgh_glm_p_from_z(double z) {
 extern "C" int pgh_glm(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                        const double *phenotype, uint32_t n_covar, const double *covariates, int model, int firth,
                        pgh_glm_row *out, char *errbuf) {
-	int rc = GlmCheckArgs(ds, subset, v_begin, v_end, 1, phenotype, n_covar, covariates, model, out, errbuf);
-	if (rc != PGH_OK) {
+	const int rc = GlmCheckArgs(ds, subset, v_begin, v_end, 1, phenotype, n_covar, covariates, model, out, errbuf);
+	if (rc != PGH_OK || v_end == v_begin) {
 		return rc;
-	}
-	if (v_end == v_begin) {
-		return PGH_OK;
 	}
 	if (ds->IsGroup()) {
 		// every shard fills its own slice of out; nothing is exchanged
-		for (size_t k = 0; k < ds->shards.size(); k++) {
-			const pgh_dataset *s = ds->shards[k];
-			const uint32_t lo = std::max(v_begin, s->v_begin), hi = std::min(v_end, s->v_end);
-			if (lo >= hi) {
-				continue;
-			}
-			rc = GlmOne(s, subset ? subset->parts[k] : nullptr, lo, hi, phenotype, n_covar, covariates, model, firth,
-			            out + (lo - v_begin), errbuf);
-			if (rc != PGH_OK) {
-				return rc;
-			}
-		}
-		return PGH_OK;
+		return ForShardSlices(ds, subset, v_begin, v_end,
+		                      [&](const pgh_dataset *s, const pgh_subset *part, uint32_t lo, uint32_t hi) {
+			                      return GlmOne(s, part, lo, hi, phenotype, n_covar, covariates, model, firth,
+			                                    out + (lo - v_begin), errbuf);
+		                      });
 	}
 	return GlmOne(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, model, firth, out, errbuf);
 }
@@ -788,25 +727,17 @@ extern "C" int pgh_glm(const pgh_dataset *ds, const pgh_subset *subset, uint32_t
 extern "C" int pgh_glm_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                              uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
                              int model, int firth, pgh_glm_row *out, char *errbuf) {
-	int rc = GlmCheckArgs(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, model, out, errbuf);
+	const int rc = GlmCheckArgs(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, model, out, errbuf);
 	if (rc != PGH_OK || v_end == v_begin) {
 		return rc;
 	}
 	if (ds->IsGroup()) {
 		// every shard fills its own slice of out, as in pgh_glm
-		for (size_t k = 0; k < ds->shards.size(); k++) {
-			const pgh_dataset *s = ds->shards[k];
-			const uint32_t lo = std::max(v_begin, s->v_begin), hi = std::min(v_end, s->v_end);
-			if (lo >= hi) {
-				continue;
-			}
-			rc = GlmMultiOne(s, subset ? subset->parts[k] : nullptr, lo, hi, n_pheno, phenotypes, n_covar, covariates,
-			                 model, firth, out + static_cast<size_t>(lo - v_begin) * n_pheno, errbuf);
-			if (rc != PGH_OK) {
-				return rc;
-			}
-		}
-		return PGH_OK;
+		return ForShardSlices(ds, subset, v_begin, v_end,
+		                      [&](const pgh_dataset *s, const pgh_subset *part, uint32_t lo, uint32_t hi) {
+			                      return GlmMultiOne(s, part, lo, hi, n_pheno, phenotypes, n_covar, covariates, model, firth,
+			                                         out + static_cast<size_t>(lo - v_begin) * n_pheno, errbuf);
+		                      });
 	}
 	return GlmMultiOne(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, model, firth, out, errbuf);
 }
@@ -814,10 +745,7 @@ extern "C" int pgh_glm_multi(const pgh_dataset *ds, const pgh_subset *subset, ui
 extern "C" int pgh_glm_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                               const double *phenotype, uint32_t n_covar, const double *covariates, pgh_glm_row *out,
                               char *errbuf) {
-	if (ds && !ds->sparse) {
-		SetErr(errbuf, "needs a sparse-resident dataset (pgh_open_sparse)");
-		return PGH_ERR_ARG;
-	}
+	PGH_SPARSE_ROWS(ds);
 	const int rc = GlmCheckCommon(ds, subset, v_begin, v_end, 1, phenotype, n_covar, covariates, PGH_GLM_LINEAR, out,
 	                              errbuf);
 	if (rc != PGH_OK || v_end == v_begin) {
@@ -830,10 +758,7 @@ extern "C" int pgh_burden_sparse(const pgh_dataset *ds, const pgh_subset *subset
                                  uint32_t n_covar, const double *covariates, uint32_t n_sets, const uint64_t *set_off,
                                  const uint32_t *set_vidx, const double *weight, pgh_burden_row *out, char *errbuf) {
 	PGH_ONE_DEVICE(ds);
-	if (ds && !ds->sparse) {
-		SetErr(errbuf, "needs a sparse-resident dataset (pgh_open_sparse)");
-		return PGH_ERR_ARG;
-	}
+	PGH_SPARSE_ROWS(ds);
 	// the arguments pgh_glm_sparse has too, over the whole resident range (its `out` is checked below)
 	const int rc = GlmCheckCommon(ds, subset, ds ? ds->v_begin : 0, ds ? ds->v_begin : 0, 1, phenotype, n_covar, covariates,
 	                              PGH_GLM_LINEAR, nullptr, errbuf);

@@ -193,6 +193,15 @@ struct DeviceScope {
 		}                                                                                                              \
 	} while (0)
 
+// entry points that read the entries of the sparse-resident form: a dense-resident dataset is refused
+#define PGH_SPARSE_ROWS(ds_)                                                                                           \
+	do {                                                                                                               \
+		if ((ds_) && !(ds_)->sparse) {                                                                                 \
+			SetErr(errbuf, "needs a sparse-resident dataset (pgh_open_sparse)");                                       \
+			return PGH_ERR_ARG;                                                                                        \
+		}                                                                                                              \
+	} while (0)
+
 // the sparse-resident forms of the entry points that serve such a dataset (api_sparse.cpp)
 namespace pgh_sparse {
 int CountsRangeDev(const pgh_dataset *ds, const pgh_subset *ss, uint32_t v_begin, uint32_t v_end, void *d_out,
@@ -348,6 +357,30 @@ struct DevBuf {
 	}
 };
 
+// One device block cut into typed buffers.  Step one: Add(&p, count) declares a buffer of `count` elements for the
+// pointer p, rounded up to 256 bytes, and `total` grows by it; a buffer that is not `present` takes no bytes.  Step
+// two, once a block of `total` bytes exists: Bind(block) sets every declared pointer, the absent ones to nullptr.
+struct ScratchLayout {
+	struct Piece {
+		void *slot; // the T* to set
+		uint64_t off;
+		bool present;
+	};
+	std::vector<Piece> pieces;
+	uint64_t total = 0;
+	template <class T>
+	void Add(T **p, uint64_t count, bool present = true) {
+		pieces.push_back({p, total, present});
+		total += present ? (sizeof(T) * count + 255) / 256 * 256 : 0;
+	}
+	void Bind(void *block) const {
+		for (const Piece &pc : pieces) {
+			void *at = pc.present ? static_cast<char *>(block) + pc.off : nullptr;
+			std::memcpy(pc.slot, &at, sizeof at); // every object pointer has void*'s representation
+		}
+	}
+};
+
 // HIP does not promise that hipMemcpyAsync has finished with a PAGEABLE source when it returns (this runtime
 // happens to stage it first, tools/pageable_async_probe.hip), so a frame-local container that feeds one must
 // outlive the copy on EVERY exit path, the PGH_HIP early returns included.  Declare one of these right after
@@ -382,6 +415,27 @@ struct HostSourceFence {
 	if (ss && ss->ds != ds) {
 		SetErr(errbuf, "sample subset belongs to a different dataset");
 		return PGH_ERR_ARG;
+	}
+	return PGH_OK;
+}
+
+// Shard k's slice of [v_begin, v_end) over a group: fn(shard, the subset's part for it or nullptr, lo, hi) when the
+// shard holds some of the range, PGH_OK when it holds none.
+template <class Fn>
+int ShardSlice(const pgh_dataset *g, const pgh_subset *ss, size_t k, uint32_t v_begin, uint32_t v_end, Fn fn) {
+	const pgh_dataset *s = g->shards[k];
+	const uint32_t lo = std::max(v_begin, s->v_begin), hi = std::min(v_end, s->v_end);
+	return lo < hi ? fn(s, ss ? ss->parts[k] : nullptr, lo, hi) : static_cast<int>(PGH_OK);
+}
+
+// The slices of every shard in turn, on the calling thread; the first failure ends the walk.
+template <class Fn>
+int ForShardSlices(const pgh_dataset *g, const pgh_subset *ss, uint32_t v_begin, uint32_t v_end, Fn fn) {
+	for (size_t k = 0; k < g->shards.size(); k++) {
+		const int rc = ShardSlice(g, ss, k, v_begin, v_end, fn);
+		if (rc != PGH_OK) {
+			return rc;
+		}
 	}
 	return PGH_OK;
 }

@@ -613,10 +613,10 @@ int SubsetCreate(const pgh_dataset *g, const uint64_t *sample_include, pgh_subse
 int CopyRowsToHost(const pgh_dataset *g, uint32_t v_begin, uint32_t v_end, uint8_t *rows, size_t row_stride,
                    char *errbuf) {
 	return ForShards(g, errbuf, [&](size_t k, char *eb) {
-		const pgh_dataset *s = g->shards[k];
-		const uint32_t lo = std::max(v_begin, s->v_begin), hi = std::min(v_end, s->v_end);
-		return lo < hi ? pgh_copy_rows_to_host(s, lo, hi, rows + static_cast<size_t>(lo - v_begin) * row_stride, row_stride, eb)
-		               : PGH_OK;
+		return ShardSlice(g, nullptr, k, v_begin, v_end,
+		                  [&](const pgh_dataset *s, const pgh_subset *, uint32_t lo, uint32_t hi) {
+			return pgh_copy_rows_to_host(s, lo, hi, rows + static_cast<size_t>(lo - v_begin) * row_stride, row_stride, eb);
+		});
 	});
 }
 
@@ -631,9 +631,10 @@ int CountsRange(const pgh_dataset *g, const pgh_subset *ss, uint32_t v_begin, ui
 		return rc;
 	}
 	return ForShards(g, errbuf, [&](size_t k, char *eb) {
-		const pgh_dataset *s = g->shards[k];
-		const uint32_t lo = std::max(v_begin, s->v_begin), hi = std::min(v_end, s->v_end);
-		return lo < hi ? pgh_counts_range(s, PartOf(ss, k), lo, hi, out + (lo - v_begin), eb) : PGH_OK;
+		return ShardSlice(g, ss, k, v_begin, v_end,
+		                  [&](const pgh_dataset *s, const pgh_subset *part, uint32_t lo, uint32_t hi) {
+			return pgh_counts_range(s, part, lo, hi, out + (lo - v_begin), eb);
+		});
 	});
 }
 
@@ -646,14 +647,12 @@ int UnpackRange(const pgh_dataset *g, const pgh_subset *ss, uint32_t v_begin, ui
 	const size_t n_out = ss ? ss->n_out : g->sample_ct;
 	const size_t val_words = (n_out + 63) / 64;
 	return ForShards(g, errbuf, [&](size_t k, char *eb) {
-		const pgh_dataset *s = g->shards[k];
-		const uint32_t lo = std::max(v_begin, s->v_begin), hi = std::min(v_end, s->v_end);
-		if (lo >= hi) {
-			return static_cast<int>(PGH_OK);
-		}
-		const size_t r0 = lo - v_begin;
-		return pgh_unpack_range(s, PartOf(ss, k), lo, hi, out ? out + r0 * n_out : nullptr,
-		                        validity ? validity + r0 * val_words : nullptr, missing_code, eb);
+		return ShardSlice(g, ss, k, v_begin, v_end,
+		                  [&](const pgh_dataset *s, const pgh_subset *part, uint32_t lo, uint32_t hi) {
+			const size_t r0 = lo - v_begin;
+			return pgh_unpack_range(s, part, lo, hi, out ? out + r0 * n_out : nullptr,
+			                        validity ? validity + r0 * val_words : nullptr, missing_code, eb);
+		});
 	});
 }
 
@@ -787,13 +786,11 @@ int MissingPerSample(const pgh_dataset *g, const pgh_subset *ss, uint32_t v_begi
 	const size_t n_out = ss ? ss->n_out : g->sample_ct;
 	std::vector<std::vector<uint32_t>> part(g->shards.size());
 	rc = ForShards(g, errbuf, [&](size_t k, char *eb) {
-		const pgh_dataset *s = g->shards[k];
-		const uint32_t lo = std::max(v_begin, s->v_begin), hi = std::min(v_end, s->v_end);
-		if (lo >= hi) {
-			return static_cast<int>(PGH_OK);
-		}
-		part[k].resize(n_out);
-		return pgh_missing_per_sample(s, PartOf(ss, k), lo, hi, part[k].data(), eb);
+		return ShardSlice(g, ss, k, v_begin, v_end,
+		                  [&](const pgh_dataset *s, const pgh_subset *sk, uint32_t lo, uint32_t hi) {
+			part[k].resize(n_out);
+			return pgh_missing_per_sample(s, sk, lo, hi, part[k].data(), eb);
+		});
 	});
 	if (rc != PGH_OK) {
 		return rc;

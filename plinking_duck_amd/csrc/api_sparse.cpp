@@ -419,32 +419,27 @@ int ScoreSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t n_s
 		PGH_HIP(d_dos.Alloc(8ull * N), "hipMalloc(score_sparse out)");
 	}
 	PGH_HIP(d_alc.Alloc(4ull * N), "hipMalloc(score_sparse out)");
-	auto up = [](uint64_t b) { return (b + 255) / 256 * 256; };
-	const uint64_t b_vlist = up(4ull * n_scored), b_w = up(8ull * n_scored * n_cols), b_flip = flip ? up(n_scored) : 0;
-	const uint64_t b_range = up(16ull * span), b_counts = up(16ull * n_scored), b_tab = up(32ull * n_scored);
-	const uint64_t b_ac = up(4ull * n_scored), b_part = up(16ull * (n_cols + 1ull) * pgh::kScoreSparseParts);
-	const uint64_t b_k0 = up(8ull * (n_cols + 1ull)), b_kexp = up(4ull * (n_cols + 1ull)), b_alc0 = 256;
+	const uint64_t ns = n_scored, nc1 = n_cols + 1ull, alc0_bytes = 256;
+	uint32_t *d_vlist, *d_range, *d_counts, *d_ac, *d_alc0;
+	double *d_w, *d_ts, *d_td, *d_part, *d_k0;
+	uint8_t *d_flip;
+	int32_t *d_kexp;
+	ScratchLayout lay;
+	lay.Add(&d_vlist, ns);
+	lay.Add(&d_w, ns * n_cols);
+	lay.Add(&d_flip, ns, flip != nullptr);
+	lay.Add(&d_range, 4ull * span);
+	lay.Add(&d_counts, 4 * ns);
+	lay.Add(&d_ts, 4 * ns);
+	lay.Add(&d_td, 4 * ns);
+	lay.Add(&d_ac, ns);
+	lay.Add(&d_part, 2 * nc1 * pgh::kScoreSparseParts);
+	lay.Add(&d_k0, nc1);
+	lay.Add(&d_kexp, nc1);
+	lay.Add(&d_alc0, alc0_bytes / 4);
 	// (not PghThreadScratch: CountsRangeDev below takes that block for the dense rows' counts)
-	PGH_HIP(work.Alloc(b_vlist + b_w + b_flip + b_range + b_counts + 2 * b_tab + b_ac + b_part + b_k0 + b_kexp + b_alc0),
-	        "hipMalloc(score_sparse)");
-	char *cur = work.As<char>();
-	auto take = [&](uint64_t b) {
-		char *p = cur;
-		cur += b;
-		return p;
-	};
-	uint32_t *d_vlist = reinterpret_cast<uint32_t *>(take(b_vlist));
-	double *d_w = reinterpret_cast<double *>(take(b_w));
-	uint8_t *d_flip = flip ? reinterpret_cast<uint8_t *>(take(b_flip)) : nullptr;
-	uint32_t *d_range = reinterpret_cast<uint32_t *>(take(b_range));
-	uint32_t *d_counts = reinterpret_cast<uint32_t *>(take(b_counts));
-	double *d_ts = reinterpret_cast<double *>(take(b_tab));
-	double *d_td = reinterpret_cast<double *>(take(b_tab));
-	uint32_t *d_ac = reinterpret_cast<uint32_t *>(take(b_ac));
-	double *d_part = reinterpret_cast<double *>(take(b_part));
-	double *d_k0 = reinterpret_cast<double *>(take(b_k0));
-	int32_t *d_kexp = reinterpret_cast<int32_t *>(take(b_kexp));
-	uint32_t *d_alc0 = reinterpret_cast<uint32_t *>(take(b_alc0));
+	PGH_HIP(work.Alloc(lay.total), "hipMalloc(score_sparse)");
+	lay.Bind(work.p);
 
 	std::vector<double> h_score(static_cast<size_t>(N) * n_cols), h_dos(track ? N : 0);
 	std::vector<uint32_t> h_ac(N);
@@ -509,10 +504,7 @@ extern "C" int pgh_score_sparse(const pgh_dataset *ds, const pgh_subset *subset,
 		return PGH_ERR_ARG;
 	}
 	PGH_ONE_DEVICE(ds);
-	if (!ds->sparse) {
-		SetErr(errbuf, "needs a sparse-resident dataset (pgh_open_sparse)");
-		return PGH_ERR_ARG;
-	}
+	PGH_SPARSE_ROWS(ds);
 	if (!score_sum || !allele_ct || (n_scored && (!vidx || !weights))) {
 		SetErr(errbuf, "null argument");
 		return PGH_ERR_ARG;

@@ -18,6 +18,7 @@
 // of the call, on the workgroup that took it or on how many workgroups there are.  Entries whose staged y is NaN
 // (outside the subset, or no phenotype) are skipped in both passes.  A dense-form member is read from its pool row as
 // base 0 with one entry per sample whose code is 1 or 2, 16 samples per word per lane.
+#include "device_utils.hpp"
 #include "glm.hpp"
 
 #include <hip/hip_runtime.h>
@@ -28,20 +29,6 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
-
-__device__ inline double WaveSum(double x) {
-	for (int d = 32; d >= 1; d >>= 1) {
-		x += __shfl_xor(x, d);
-	}
-	return x;
-}
-
-__device__ inline uint32_t WaveSum(uint32_t x) {
-	for (int d = 32; d >= 1; d >>= 1) {
-		x += __shfl_xor(x, d);
-	}
-	return x;
-}
 
 // The entries of row v that count, at stride over the workgroup: f(sample, val(code) - val(base), y[sample]).
 template <class F>

@@ -11,12 +11,23 @@ namespace {
 
 constexpr uint32_t kLow = 0x55555555u; // low bit of every 2-bit slot
 
-__device__ __forceinline__ uint32_t WaveSum(uint32_t x) {
+// The sum of x over the 64 lanes of a wave, on every lane (butterfly: xor 32, 16, 8, 4, 2, 1).
+template <class T>
+__device__ __forceinline__ T WaveSumOf(T x) {
 #pragma unroll
 	for (int off = 32; off > 0; off >>= 1) {
 		x += __shfl_xor(x, off, 64);
 	}
 	return x;
+}
+__device__ __forceinline__ uint32_t WaveSum(uint32_t x) {
+	return WaveSumOf(x);
+}
+__device__ __forceinline__ double WaveSum(double x) {
+	return WaveSumOf(x);
+}
+__device__ __forceinline__ long long WaveSum(long long x) {
+	return WaveSumOf(x);
 }
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));

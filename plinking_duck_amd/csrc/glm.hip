@@ -10,6 +10,7 @@
 //
 // Determinism: a thread always owns the same samples (stride 256) and reductions run in one fixed order, so a
 // variant's sums do not depend on its place in a tile, chunk or shard.
+#include "device_utils.hpp"
 #include "glm.hpp"
 #include "glm_math.hpp"
 
@@ -34,13 +35,6 @@ __device__ inline double GlmValue(const GlmX &g, uint32_t v, uint32_t i) {
 	const uint8_t *row = g.view.rows + static_cast<uint64_t>(g.v0 + v) * g.view.pitch;
 	const uint32_t c = (row[raw >> 2] >> (2 * (raw & 3))) & 3u;
 	return c == 3u ? -9.0 : static_cast<double>(c);
-}
-
-__device__ inline double WaveSum(double x) {
-	for (int d = 32; d >= 1; d >>= 1) {
-		x += __shfl_xor(x, d);
-	}
-	return x;
 }
 
 // Block sum of NE per-thread values in a fixed order: butterfly within each wave, then waves 0..3 in turn.

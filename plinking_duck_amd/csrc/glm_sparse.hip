@@ -15,6 +15,7 @@
 // entries of the Gram set are compacted in entry order into an LDS list, and every Gram entry belongs to one thread
 // that walks the list in order, as in GlmGramKernel.  Nothing depends on which rows share a workgroup, on the chunk
 // or on where the range starts.
+#include "device_utils.hpp"
 #include "glm.hpp"
 
 #include <hip/hip_runtime.h>
@@ -26,20 +27,6 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 constexpr int kMaxNe = 253; // (k + 2)(k + 3) / 2 at k = PGH_GLM_MAX_COVAR
-
-__device__ inline double WaveSum(double x) {
-	for (int d = 32; d >= 1; d >>= 1) {
-		x += __shfl_xor(x, d);
-	}
-	return x;
-}
-
-__device__ inline long long WaveSum(long long x) {
-	for (int d = 32; d >= 1; d >>= 1) {
-		x += __shfl_xor(x, d);
-	}
-	return x;
-}
 
 // Orders a team's LDS writes before its LDS reads.  A wave's LDS instructions complete in issue order, so a team of
 // one wave only has to keep the compiler from moving them.

@@ -12,6 +12,7 @@
 //
 // A workgroup (rows >= 4 KiB) or a wave (shorter rows) takes one anchor row against up to four
 // consecutive partner rows, so the anchor's words are loaded once for the four.
+#include "device_utils.hpp"
 #include "ld.hpp"
 
 namespace pgh {
@@ -41,13 +42,6 @@ __device__ inline void Tally(PairAcc &acc, uint32_t a, uint32_t a_ok, uint32_t b
 	acc.lh += __popc(alo & bhi);
 	acc.hl += __popc(ahi & blo);
 	acc.hh += __popc(ahi & bhi);
-}
-
-__device__ inline uint32_t WaveSum32(uint32_t v) {
-	for (int d = 32; d > 0; d >>= 1) {
-		v += __shfl_xor(v, d, 64);
-	}
-	return v;
 }
 
 // LANES = 256: one workgroup per task; LANES = 64: one wave per task, four tasks per workgroup
@@ -112,7 +106,7 @@ __global__ __launch_bounds__(256) void k_ld_pairs(const uint8_t *__restrict__ ro
 		                 acc[p].ll,   acc[p].lh,   acc[p].hl,   acc[p].hh};
 #pragma unroll
 		for (int k = 0; k < 9; k++) {
-			v[k] = WaveSum32(v[k]);
+			v[k] = WaveSum(v[k]);
 		}
 		if (LANES == 256) {
 			if ((threadIdx.x & 63u) == 0) {

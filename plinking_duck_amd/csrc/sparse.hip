@@ -1,5 +1,6 @@
 // sparse.hip -- gfx950 kernels of the sparse-resident form (sparse.hpp): classify and compact the rows of a decoded
 // window, per-variant class counts, per-sample class tallies and the expansion back to 2-bit rows.
+#include "device_utils.hpp"
 #include "sparse.hpp"
 
 #include <algorithm>
@@ -9,13 +10,6 @@ namespace pgh {
 namespace {
 
 constexpr uint64_t kLo = 0x5555555555555555ull;
-
-__device__ __forceinline__ uint32_t WaveSum(uint32_t x) {
-	for (int off = 32; off > 0; off >>= 1) {
-		x += __shfl_xor(x, off, 64);
-	}
-	return x;
-}
 
 // mask of the 2-bit slots of word wi (32 samples per uint64) that hold a sample
 __device__ __forceinline__ uint64_t SlotMask(uint64_t wi, uint32_t sample_ct) {

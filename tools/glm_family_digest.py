@@ -1,0 +1,192 @@
+#!/usr/bin/env python3
+"""One SHA-256 per case over the result bytes of the GLM family (pgh_glm, pgh_glm_multi, pgh_glm_sparse,
+pgh_burden_sparse), pgh_score_sparse, and the plink_ld pair sums and sparse counts that share their wave sums: the
+paths a change to the family's host staging, scratch layout or chunk loops can touch.  Two builds of the library
+compute the same rows bit for bit exactly when their outputs of this tool are equal line for line; PGENHIP_LIB names
+the build (plinking_duck_amd/lib.py).  A case that differs between two runs of ONE build is not deterministic from
+run to run and its line says nothing.
+
+The inputs are small seeded files: every record type through tests/pgen_writer.py, carrier lists through
+tools/sparse_bench.py, and the library's own synthetic rows for the two shapes that need many variants or samples (a
+range past one 16384-variant chunk; 70,001 samples, where 512 MiB of dense dosages split a 2100-variant call).
+
+usage: python tools/glm_family_digest.py [--dir DIR]"""
+import argparse
+import hashlib
+import os
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import pgen_writer as W  # noqa: E402
+import plinking_duck_amd.lib as L  # noqa: E402
+from tools.sparse_bench import carrier_rows, write_carrier_pfile  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--dir", default=None, help="where the input files go (default: a temporary directory)")
+args = ap.parse_args()
+tmp = tempfile.TemporaryDirectory() if args.dir is None else None
+out_dir = args.dir or tmp.name
+os.makedirs(out_dir, exist_ok=True)
+
+
+def emit(name, *results):
+    h = hashlib.sha256()
+    for r in results:
+        if isinstance(r, dict):
+            r = [r[key] for key in sorted(r)]
+        for a in r if isinstance(r, (list, tuple)) else [r]:
+            if a is None:
+                h.update(b"none")
+            elif a.dtype == object:
+                h.update(repr(a.tolist()).encode())
+            else:
+                h.update(np.ascontiguousarray(a).tobytes())
+    print(f"{name} {h.hexdigest()}", flush=True)
+
+
+def pheno(rng, n, Z, kind="linear", missing=0.03):
+    eta = (Z.sum(axis=0) * 0.2 if Z is not None and len(Z) else 0.0) + rng.standard_normal(n)
+    y = eta if kind == "linear" else (rng.random(n) < 1 / (1 + np.exp(-eta))).astype(np.float64)
+    y[rng.random(n) < missing] = np.nan
+    return y
+
+
+def covar(rng, k, n):
+    return rng.normal(size=(k, n)) * (10.0 ** (np.arange(k) % 3 - 1.0))[:, None] if k else None
+
+
+# ---- dense: pgh_glm and pgh_glm_multi --------------------------------------------------------------------------
+rng = np.random.default_rng(20261018)
+M, N = 300, 517
+geno = rng.choice(np.array([0, 1, 2, 3], dtype=np.uint8), size=(M, N), p=[0.6, 0.27, 0.1, 0.03])
+geno[5] = 0  # a constant row
+dos16 = np.where(rng.random((M, N)) < 0.3, rng.integers(0, 32769, (M, N)), 0xFFFF).astype(np.uint16)
+dos_kinds = [int(rng.choice([0, 0x20, 0x40, 0x60])) for _ in range(M)]
+plain = os.path.join(out_dir, "plain.pgen")
+tracks = os.path.join(out_dir, "tracks.pgen")
+W.write_pgen(plain, geno, W.choose_kinds(geno, rng))
+W.write_pgen(tracks, geno, W.choose_kinds(geno, rng), dosage=dos16, dosage_kinds=dos_kinds)
+ds = L.Dataset.open(plain)
+dt = L.Dataset.open(tracks)
+assert dt.info.dosage_variant_ct > 0
+keep = rng.random(N) < 0.7
+ss, st = ds.subset(keep), dt.subset(keep)
+n_keep = int(keep.sum())
+
+for k in (0, 3, 20):
+    Z = covar(rng, k, N)
+    emit(f"glm linear k={k}", ds.glm(pheno(rng, N, Z), Z, model="linear"))
+Z2 = covar(rng, 2, N)
+emit("glm logistic k=2", ds.glm(pheno(rng, N, Z2, "logistic"), Z2, model="logistic"))
+y_sep = (geno[0] > 0).astype(np.float64)  # separated by variant 0's genotype, with a few flips elsewhere
+emit("glm firth separated", ds.glm(y_sep, None, model="logistic", firth=True),
+     ds.glm(y_sep, None, model="logistic", firth=False))
+Zs = covar(rng, 3, n_keep)
+emit("glm subset linear k=3", ds.glm(pheno(rng, n_keep, Zs), Zs, model="linear", subset=ss))
+emit("glm subset logistic k=3", ds.glm(pheno(rng, n_keep, Zs, "logistic"), Zs, model="logistic", subset=ss))
+emit("glm dosage tracks", dt.glm(pheno(rng, N, Z2), Z2, model="linear"),
+     dt.glm(pheno(rng, N, Z2, "logistic"), Z2, model="logistic"),
+     dt.glm(pheno(rng, n_keep, Zs), Zs, model="linear", subset=st, v_begin=7, v_end=M - 3))
+
+
+def phenos(rng, n, P, Z, patterns, kind="linear"):
+    masks = [rng.random(n) < 0.05 for _ in range(patterns)]
+    Y = np.stack([pheno(rng, n, Z, kind, missing=0.0) for _ in range(P)])
+    for p in range(P):
+        Y[p, masks[p % patterns]] = np.nan
+    return Y
+
+
+Z3 = covar(rng, 3, N)
+emit("glm_multi P=7 two patterns", ds.glm_multi(phenos(rng, N, 7, Z3, 2), Z3))
+emit("glm_multi P=65", ds.glm_multi(phenos(rng, N, 65, Z3, 1), Z3))
+emit("glm_multi subset", ds.glm_multi(phenos(rng, n_keep, 5, Zs, 2), Zs, subset=ss))
+emit("glm_multi logistic P=3", ds.glm_multi(phenos(rng, N, 3, Z2, 2, "logistic"), Z2, model="logistic", v_end=40))
+emit("glm_multi dosage tracks", dt.glm_multi(phenos(rng, N, 7, Z3, 2), Z3),
+     dt.glm_multi(phenos(rng, n_keep, 3, Zs, 1), Zs, subset=st))
+
+# the plink_ld pair sums: a wave per pair on these rows, a workgroup per pair on the 70,001-sample rows below
+a, b = rng.integers(0, M, 400), rng.integers(0, M, 400)
+emit("ld_pairs short rows", ds.ld_pairs(a, b), ds.ld_pairs(a, b, subset=ss))
+
+# a range past one chunk of 16384 variants, starting inside the resident range
+N_L = 203
+long_ds = L.Dataset.synth(100, 17100, N_L, 7, 0.02)
+Zl = covar(rng, 2, N_L)
+emit("glm range past a chunk", long_ds.glm(pheno(rng, N_L, Zl), Zl, model="linear", v_begin=150),
+     long_ds.glm(pheno(rng, N_L, Zl, "logistic"), Zl, model="logistic", v_begin=150))
+long_ds.close()
+
+# dosage chunks that split: 958 variants of 70,001 samples per 512 MiB of dense dosages
+M_D, N_D = 2100, 70001
+L.synth_write_dosage_files(os.path.join(out_dir, "dos"), M_D, N_D, 21, 0.02, 0.3)
+dd = L.Dataset.open(os.path.join(out_dir, "dos.pgen"))
+assert dd.info.dosage_variant_ct > 0
+Zd = covar(rng, 2, N_D)
+emit("glm dosage chunks split", dd.glm(pheno(rng, N_D, Zd), Zd, model="linear"))
+emit("glm_multi dosage chunks split", dd.glm_multi(phenos(rng, N_D, 3, Zd, 2), Zd))
+a, b = rng.integers(0, M_D, 200), rng.integers(0, M_D, 200)
+emit("ld_pairs long rows", dd.ld_pairs(a, b))
+dd.close()
+for d in (ss, st, ds, dt):
+    d.close()
+
+# ---- sparse-resident: pgh_glm_sparse, pgh_burden_sparse, pgh_score_sparse ----------------------------------------
+M_R, N_R = 160, 4099
+rare = W.rare_matrix(M_R, N_R, rng)
+for v, rate in ((7, 0.01), (8, 0.3)):  # het-majority rows: rare_matrix draws none
+    hit = rng.random(N_R) < rate
+    rare[v] = 1
+    rare[v, hit] = rng.integers(0, 4, hit.sum(), dtype=np.uint8)
+rare[9] = 0  # a row past kGlmSparseLong entries
+rare[9, rng.permutation(N_R)[:1500]] = rng.integers(1, 4, 1500, dtype=np.uint8)
+minor = N_R - np.array([np.bincount(r, minlength=4).max() for r in rare])
+assert (minor > 1024).any() and ((minor > 0) & (minor <= 1024)).any()  # both sides of kGlmSparseLong
+rare_path = os.path.join(out_dir, "rare.pgen")
+W.write_pgen(rare_path, rare, W.choose_kinds(rare, rng))
+keep_r = rng.random(N_R) < 0.7
+n_keep_r = int(keep_r.sum())
+Zr, Zrs = covar(rng, 3, N_R), covar(rng, 3, n_keep_r)
+yr, yrs = pheno(rng, N_R, Zr), pheno(rng, n_keep_r, Zrs)
+set_off = np.concatenate([[0], np.cumsum(rng.integers(0, 12, 40))]).astype(np.uint64)
+set_vidx = rng.integers(0, M_R, int(set_off[-1])).astype(np.uint32)
+set_w = rng.normal(size=len(set_vidx))
+scored = rng.permutation(M_R)[:120].astype(np.uint32)
+flip = (rng.random(len(scored)) < 0.5).astype(np.uint8)
+for max_minor, form in ((N_R, "entries only"), (1, "with dense-form rows")):
+    sp = L.Dataset.open(rare_path, sparse=True, max_minor=max_minor)
+    info = sp.sparse_info()
+    if max_minor == N_R:
+        assert info.dense_variant_ct == 0 and all(info.base_hist[c] > 0 for c in range(4))
+    else:
+        assert info.dense_variant_ct > 0 and info.sparse_variant_ct > 0
+    sub = sp.subset(keep_r)
+    emit(f"glm_sparse {form}", sp.glm_sparse(yr, Zr), sp.glm_sparse(yr, None))
+    emit(f"glm_sparse {form}, subset", sp.glm_sparse(yrs, Zrs, subset=sub, v_begin=3, v_end=M_R - 2))
+    emit(f"burden_sparse {form}, weighted", sp.burden_sparse(yr, set_off, set_vidx, weights=set_w, covariates=Zr))
+    emit(f"burden_sparse {form}, unweighted", sp.burden_sparse(yr, set_off, set_vidx, covariates=Zr))
+    emit(f"burden_sparse {form}, subset", sp.burden_sparse(yrs, set_off, set_vidx, weights=set_w, covariates=Zrs,
+                                                              subset=sub))
+    for n_cols in (1, 9):
+        w = rng.normal(size=(len(scored), n_cols))
+        for mode in (L.SCORE_MEAN_IMPUTE, L.SCORE_CENTER, L.SCORE_NO_MEAN_IMPUTATION):
+            emit(f"score_sparse {form}, n_cols={n_cols} mode={mode}", sp.score_sparse(scored, w, mode=mode),
+                 sp.score_sparse(scored, w, flip=flip, mode=mode), sp.score_sparse(scored, w, flip=flip, mode=mode, subset=sub))
+    emit(f"sparse counts and sample classes {form}", sp.counts_range(), sp.counts_range(subset=sub), sp.sample_counts(),
+         sp.sample_counts(vidx=scored, subset=sub))
+    sub.close()
+    sp.close()
+
+# carrier lists across a chunk boundary of pgh_glm_sparse (16384 variants)
+M_C, N_C = 17000, 311
+prefix = os.path.join(out_dir, "carriers")
+write_carrier_pfile(prefix, M_C, N_C, carrier_rows(M_C, N_C, 0.02, 5))
+sp = L.Dataset.open(prefix + ".pgen", sparse=True)
+Zc = covar(rng, 2, N_C)
+emit("glm_sparse across a chunk", sp.glm_sparse(pheno(rng, N_C, Zc), Zc))
+sp.close()
