@@ -144,7 +144,7 @@ void pgh_close(pgh_dataset *ds);
  * choice.  Hardcalls only (dosage and phase tracks are stepped over; pgh_info still reports them), one device,
  * fewer than 2^30 samples (PGH_ERR_ARG otherwise).  Served by pgh_get_info, pgh_close, pgh_counts_range(_dev),
  * pgh_sample_counts(_dev), pgh_copy_rows_to_host, pgh_subset_* and the entry points made for this form:
- * pgh_glm_sparse, pgh_burden_sparse and pgh_score_sparse; every other entry point that reads rows (pgh_score,
+ * pgh_glm_sparse, pgh_glm_score_sparse, pgh_burden_sparse and pgh_score_sparse; every other entry point that reads rows (pgh_score,
  * pgh_score_dev and the score plans among them) returns PGH_ERR_ARG, and pgh_device_rows returns NULL. */
 typedef struct pgh_sparse_info {
 	uint32_t sparse_variant_ct; /* variants held as base + entries                                  */
@@ -537,10 +537,51 @@ int pgh_glm_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_be
  * rounding (its sums are accumulated over the entries, in another order); the rows of variants held in the dense
  * form (pgh_sparse_info.dense_variant_ct) are pgh_glm's bit for bit.  A row is a function of its variant's entries,
  * the phenotype, the covariates and the subset only: not of v_begin, the chunk or the rows around it, and the same
- * call returns the same bytes every time.  Logistic and Firth fits over a sparse-resident dataset are not offered. */
+ * call returns the same bytes every time.  Logistic Wald and Firth fits over a sparse-resident dataset are not offered
+ * (the logistic score test is: pgh_glm_score_sparse). */
 int pgh_glm_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                    const double *phenotype, uint32_t n_covar, const double *covariates,
                    pgh_glm_row *out, char *errbuf);
+/* The logistic SCORE TEST of every variant of [v_begin, v_end) of a SPARSE-RESIDENT dataset (pgh_open_sparse), from
+ * the variants' entries: the covariates-only model is fitted once, and a variant then costs in proportion to the
+ * samples that differ from its base code.  Arguments, argument checks, row layout and error codes are
+ * pgh_glm_sparse's (hardcalls only, one row per variant; a shard group or a dataset that is not sparse-resident is
+ * PGH_ERR_ARG, the latter "needs a sparse-resident dataset").  In addition every non-NaN phenotype value must be
+ * exactly 0.0 or 1.0 (glm_model()'s 1/2 coding is the caller's to apply) and at least one case and one control must
+ * have a phenotype; otherwise PGH_ERR_ARG ("phenotype must be 0 or 1", "no cases or no controls") and `out` is
+ * untouched.
+ *
+ * Null model.  S = the output samples with a phenotype, n_y = |S|, Zt_i = [1, z_i1 .. z_ik] with the covariates
+ * centred over S (the intercept absorbs the shift).  Logistic y ~ Zt over S by Newton steps from beta = 0 in FP64:
+ * H = sum_S w Zt Zt', g = sum_S Zt (y - mu), delta = H^-1 g, w = mu (1 - mu).  The fit has converged after the first
+ * step with max_j |delta_j| <= 1e-10; mu, w, r = y - mu, H and g_S are then recomputed at the final beta.  The
+ * Cholesky of H fails on a pivot that is not positive or is at most 1e-10 of its own diagonal entry.  A pivot failure
+ * at the first step (every w is 1/4: collinear covariates) gives every row not decided earlier SINGULAR_MATRIX; one
+ * at a later step, a non-finite step, or no convergence after 25 steps gives NO_CONVERGENCE.  With n_y < k + 3 the
+ * fit is skipped (every row is then TOO_FEW_SAMPLES).
+ *
+ * Per variant.  M = the samples of S whose call is missing, N = S without M, n = |N|, x_i = the ALT count.  The row is the
+ * one-step efficient score of x given Zt over N:
+ *   H_N = sum_N w Zt Zt'   g_N = sum_N Zt r   c = sum_N w x Zt   A = sum_N w x^2   U0 = sum_N x r
+ *   t = H_N^-1 c   V = A - c't   U = U0 - t'g_N   beta = U / V   se = 1 / sqrt(V)   stat = U / sqrt(V)
+ *   p = pgh_glm_p_from_z(stat)
+ * U and V do not change when a multiple of a column of Zt is added to x, so the sums are taken with d = x - b for the
+ * row's base code b (d = x under a missing-majority base), over the row's called entries alone; A is defined with d.
+ * n, sum x and sum x^2 are integers, so obs_ct, a1_freq, TOO_FEW_SAMPLES (n < k + 3) and CONST_ALLELE (every called
+ * value equal) are pgh_glm's with model = PGH_GLM_LOGISTIC for the same file, bit for bit.
+ * Decisions, in order: TOO_FEW_SAMPLES; CONST_ALLELE; the null model's status; SINGULAR_MATRIX when the Cholesky of
+ * [[H_N, c], [c', A]] fails the 1e-10 pivot rule (its last pivot is V, against A); otherwise the row is fitted.
+ * ZERO_VARIANCE and SEPARATION are never produced and firth is 0.  Undecided fields are NaN; obs_ct is always filled
+ * and a1_freq where pgh_glm fills it.  A row held in the dense form is treated as a base-0 row whose entries are its
+ * samples with a code other than 0: the same formulas, the same contract.
+ *
+ * A row is a function of its variant's entries, the phenotype, the covariates and the subset only: not of v_begin,
+ * the chunk, the window the dataset was opened with or the rows around it, and the same call returns the same bytes
+ * every time, the null fit included.  Datasets opened with another max_minor hold other base codes; their rows agree
+ * to rounding (1e-9 on the scale of the estimates), not bit for bit. */
+int pgh_glm_score_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                         const double *phenotype, uint32_t n_covar, const double *covariates,
+                         pgh_glm_row *out, char *errbuf);
 /* Gene-set BURDEN tests over a SPARSE-RESIDENT dataset (pgh_open_sparse), from the variants' entries: per set, the
  * variants are collapsed into one weighted burden per sample and the phenotype is regressed on it (linear).
  *

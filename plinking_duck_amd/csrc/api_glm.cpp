@@ -1,7 +1,8 @@
 // api_glm.cpp -- pgh_glm: plink_glm's per-variant linear / logistic / Firth regressions (glm.hip) behind the C ABI;
 // pgh_glm_multi: the same for many phenotypes in one call; pgh_glm_sparse: the linear fit over a sparse-resident
 // dataset, from its entries (glm_sparse.hip); pgh_burden_sparse: gene-set burden fits over such a dataset
-// (burden_sparse.hip).
+// (burden_sparse.hip); pgh_glm_score_sparse: the logistic score test over such a dataset, from its entries
+// (glm_score_sparse.hip).
 #include "api_internal.hpp"
 #include "glm.hpp"
 #include "glm_math.hpp"
@@ -582,6 +583,125 @@ int GlmSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_beg
 	return PGH_OK;
 }
 
+// The covariates-only logistic fit of pgh_glm_score_sparse: Newton steps from beta = 0, each one evaluation on the
+// device (LaunchGlmScoreNull) and a (k + 1)-wide Cholesky step here.  On return r, w and hg on the device are those of
+// the last beta evaluated: the final one when the fit converged.  *status: PGH_GLM_OK, SINGULAR_MATRIX (a pivot failed
+// at the first step, where every w is 1/4: collinear covariates) or NO_CONVERGENCE.  With fit == false (too few
+// samples for any row) only beta = 0 is evaluated, which stages r's NaN pattern for the entry kernel's counts.
+int GlmScoreNullFit(uint32_t n_out, const double *d_y, const double *d_z, uint32_t kp, uint32_t k, const uint32_t *d_sel,
+                    bool fit, double *d_r, double *d_w, double *d_part, double *d_hg, hipStream_t st, int *status,
+                    char *errbuf) {
+	constexpr int kMaxSteps = 25;
+	constexpr int M = PGH_GLM_MAX_COVAR + 1;
+	const int q1 = static_cast<int>(k) + 1, nh = q1 * (q1 + 1) / 2;
+	pgh::GlmScoreBeta beta {};
+	std::vector<double> hg(nh + q1);
+	double a[M * M], delta[M];
+	*status = PGH_GLM_OK;
+	bool final = !fit;
+	for (int step = 0;; step++) {
+		PGH_HIP(pgh::LaunchGlmScoreNull(n_out, d_y, d_z, kp, k, beta, d_sel, d_r, d_w, d_part, d_hg, st),
+		        "glm_score_sparse null kernel");
+		if (final) {
+			return PGH_OK; // what the device holds is the fitted model's
+		}
+		if (step == kMaxSteps) {
+			*status = PGH_GLM_NO_CONVERGENCE;
+			return PGH_OK;
+		}
+		PGH_HIP(hipMemcpyAsync(hg.data(), d_hg, 8ull * hg.size(), hipMemcpyDeviceToHost, st), "glm_score_sparse null copy");
+		PGH_HIP(hipStreamSynchronize(st), "glm_score_sparse null sync");
+		for (int ia = 0, e = 0; ia < q1; ia++) {
+			for (int ib = ia; ib < q1; ib++, e++) {
+				a[ib * M + ia] = hg[e];
+			}
+		}
+		if (!pgh::GlmCholesky(a, q1, M, 1e-10, nullptr)) {
+			*status = step == 0 ? PGH_GLM_SINGULAR_MATRIX : PGH_GLM_NO_CONVERGENCE;
+			return PGH_OK;
+		}
+		std::copy_n(hg.data() + nh, q1, delta);
+		pgh::GlmCholSolve(a, q1, M, delta);
+		double dmax = 0.0;
+		bool finite = true;
+		for (int j = 0; j < q1; j++) {
+			finite = finite && std::isfinite(delta[j]) && std::isfinite(beta.b[j] + delta[j]);
+			dmax = std::max(dmax, std::fabs(delta[j]));
+		}
+		if (!finite) {
+			*status = PGH_GLM_NO_CONVERGENCE;
+			return PGH_OK;
+		}
+		for (int j = 0; j < q1; j++) {
+			beta.b[j] += delta[j];
+		}
+		final = dmax <= 1e-10; // converged: one more evaluation, at the final beta
+	}
+}
+
+// pgh_glm_score_sparse on one sparse-resident dataset.  y and z are staged in output-sample order for the null fit,
+// which leaves r and w in raw-sample order (NaN r outside the subset: uploaded so, the fit writes the subset's
+// samples only); z is staged a second time in raw-sample order when there is a subset, as in GlmSparseOne.
+int GlmScoreSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                      const double *phenotype, uint32_t k, const double *covariates, pgh_glm_row *out, char *errbuf) {
+	PGH_ENTER(ds);
+	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct, n_raw = ds->sample_ct;
+	const uint32_t nv_all = v_end - v_begin;
+	const uint32_t kp = pgh::GlmPadCovar(k);
+	hipStream_t st = PghThreadStream();
+	const GlmStaged sg = GlmStage(ds, subset, phenotype, k, covariates, GlmCentre::kZ, true);
+	const uint32_t n_y = sg.n_y;
+
+	const uint32_t chunk = std::min(kGlmChunk, std::max(1u, nv_all));
+	const uint32_t l_begin = v_begin - ds->v_begin;
+	const uint32_t ns = kp + 6, ne = (k + 1) * (k + 2) / 2 + k + 1;
+	const uint64_t n = n_out, nr = n_raw, c = chunk;
+	double *d_y, *d_z, *d_zr, *d_r, *d_w, *d_part, *d_hg, *d_sums, *d_hgn;
+	pgh_glm_row *d_rows;
+	ScratchLayout lay;
+	lay.Add(&d_y, n);
+	lay.Add(&d_z, n * kp + 1); // one element of slack, here and in d_zr
+	lay.Add(&d_zr, nr * kp + 1, subset != nullptr);
+	lay.Add(&d_r, nr);
+	lay.Add(&d_w, nr);
+	lay.Add(&d_part, static_cast<uint64_t>(pgh::kGlmScoreNullParts) * ne);
+	lay.Add(&d_hg, ne);
+	lay.Add(&d_sums, c * ns);
+	lay.Add(&d_hgn, c * ne);
+	lay.Add(&d_rows, c);
+	void *scratch = nullptr;
+	PGH_HIP(PghThreadScratch(lay.total, st, &scratch), "glm_score_sparse scratch");
+	lay.Bind(scratch);
+	if (!subset) {
+		d_zr = d_z;
+	}
+
+	HostSourceFence fence(st); // sg feeds asynchronous uploads
+	int rc = GlmUpload(sg, d_y, d_z, d_r, d_zr, st, "glm_score_sparse", "phenotype", errbuf);
+	if (rc != PGH_OK) {
+		return rc;
+	}
+	if (subset) {
+		PGH_HIP(hipMemsetAsync(d_w, 0, 8ull * nr, st), "glm_score_sparse weight clear");
+	}
+	int null_status = PGH_GLM_OK;
+	rc = GlmScoreNullFit(n_out, d_y, d_z, kp, k, subset ? subset->d_sel : nullptr, n_y >= k + 3, d_r, d_w, d_part, d_hg, st,
+	                     &null_status, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
+	}
+	for (uint32_t c0 = 0; c0 < nv_all; c0 += chunk) {
+		const uint32_t nv = std::min(chunk, nv_all - c0);
+		PGH_HIP(pgh::LaunchGlmScoreSparse(ds->Sparse(), l_begin + c0, nv, d_r, d_w, d_zr, kp, k, n_y, d_hg, d_sums, d_hgn, st),
+		        "glm_score_sparse entry kernel");
+		PGH_HIP(pgh::LaunchGlmScoreSolve(nv, d_sums, kp, k, d_hgn, null_status, d_rows, st), "glm_score_sparse solve kernel");
+		PGH_HIP(hipMemcpyAsync(out + c0, d_rows, sizeof(pgh_glm_row) * nv, hipMemcpyDeviceToHost, st),
+		        "glm_score_sparse rows copy");
+		PGH_HIP(hipStreamSynchronize(st), "glm_score_sparse sync");
+	}
+	return PGH_OK;
+}
+
 constexpr uint64_t kBurdenScratchBytes = 1ull << 30;
 const char *const kBurdenScratchEnv = "PGH_BURDEN_SCRATCH_BYTES";
 
@@ -752,6 +872,39 @@ extern "C" int pgh_glm_sparse(const pgh_dataset *ds, const pgh_subset *subset, u
 		return rc;
 	}
 	return GlmSparseOne(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, out, errbuf);
+}
+
+extern "C" int pgh_glm_score_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                                    const double *phenotype, uint32_t n_covar, const double *covariates,
+                                    pgh_glm_row *out, char *errbuf) {
+	PGH_ONE_DEVICE(ds);
+	PGH_SPARSE_ROWS(ds);
+	const int rc = GlmCheckCommon(ds, subset, v_begin, v_end, 1, phenotype, n_covar, covariates, PGH_GLM_LOGISTIC, out,
+	                              errbuf);
+	if (rc != PGH_OK) {
+		return rc;
+	}
+	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct;
+	uint32_t cases = 0, controls = 0;
+	for (uint32_t i = 0; i < n_out; i++) {
+		if (std::isnan(phenotype[i])) {
+			continue;
+		}
+		if (phenotype[i] != 0.0 && phenotype[i] != 1.0) {
+			SetErr(errbuf, "phenotype must be 0 or 1 (NaN = missing), got " + std::to_string(phenotype[i]) + " at sample " +
+			                   std::to_string(i));
+			return PGH_ERR_ARG;
+		}
+		(phenotype[i] != 0.0 ? cases : controls)++;
+	}
+	if (!cases || !controls) {
+		SetErr(errbuf, "no cases or no controls among the samples with a phenotype");
+		return PGH_ERR_ARG;
+	}
+	if (v_end == v_begin) {
+		return PGH_OK;
+	}
+	return GlmScoreSparseOne(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, out, errbuf);
 }
 
 extern "C" int pgh_burden_sparse(const pgh_dataset *ds, const pgh_subset *subset, const double *phenotype,

@@ -199,19 +199,6 @@ __device__ inline void SetRowNull(pgh_glm_row &r) {
 	r.pad[0] = r.pad[1] = 0;
 }
 
-// CONST_ALLELE where the reference uses its two-pass variance sum (x - mean)^2 < 1e-20 (the multivariate linear and
-// the logistic fits).  Calls and dosages (value / 16384) lie on the 2^-14 grid in [0, 2], so n, sum x and sum x^2
-// are exact sums (sum x^2 while n < 2^23; for calls always), and a used set that is not constant has a variance sum
-// of at least 2^-28 (1 - 1/n) > 1e-20.  The rule is therefore "every used x is equal", which is n sum x^2 == (sum x)^2
-// (Cauchy-Schwarz: > otherwise).  Both products are compared exactly, each as an fma two-product (hi + lo).  The
-// one-pass sum x^2 - (sum x)^2 / n is not enough: for a constant dosage it can round to a positive number (2.3e-13 for
-// 20,001 samples at 4915 / 16384).
-__device__ inline bool GlmConstant(double n, double sx, double sxx) {
-	const double a = n * sxx, a_lo = fma(n, sxx, -a);
-	const double b = sx * sx, b_lo = fma(sx, sx, -b);
-	return a < b || (a == b && a_lo <= b_lo);
-}
-
 // FLAGGED (pgh_burden_sparse): x is not on the dosage grid, so CONST_ALLELE is decided by the caller (x_const[v] != 0)
 // and the correction Gram is zero (corr is not read).  FLAGGED == false is the kernel of pgh_glm and pgh_glm_sparse.
 template <bool FLAGGED>

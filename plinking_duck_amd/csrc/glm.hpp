@@ -113,6 +113,31 @@ hipError_t LaunchGlmSparse(const SparseView &sv, uint32_t v_first, uint32_t nv, 
                            uint32_t kp, uint32_t k, uint32_t n_y, const double *gram, double *sums, double *corr,
                            hipStream_t stream);
 
+// ---- pgh_glm_score_sparse (glm_score_sparse.hip): the logistic score test from a sparse row's entries ----
+// The null model y ~ Zt = [1, z_1..z_k] and its packed sums hg: H = sum_S w Zt Zt' ((k+1)(k+2)/2 entries, row-major
+// upper) followed by g_S = sum_S Zt r (k + 1 entries), S being the samples with a phenotype.
+struct GlmScoreBeta {
+	double b[PGH_GLM_MAX_COVAR + 1];
+};
+// Partial sums per entry of hg: a fixed shape, so hg is a function of y, z and beta alone.
+constexpr uint32_t kGlmScoreNullParts = 64;
+// One Newton evaluation at beta.  y: n_out doubles (NaN = missing), z: n_out x kp doubles, output-sample order.
+// Leaves r = y - mu (NaN without a phenotype) and w = mu (1 - mu) at r_raw / w_raw[sel ? sel[i] : i] (the raw samples
+// outside `sel` are not written), and hg.  part: kGlmScoreNullParts x (entries of hg) doubles of scratch.
+hipError_t LaunchGlmScoreNull(uint32_t n_out, const double *y, const double *z, uint32_t kp, uint32_t k,
+                              const GlmScoreBeta &beta, const uint32_t *sel, double *r_raw, double *w_raw, double *part,
+                              double *hg, hipStream_t stream);
+// For the rows v_first + i (i < nv) of `sv`, sparse or held in the dense form: sums[i][kp + 6] = {n, sum x, sum x^2,
+// U0, A, c_0 .. c_kp} and hgn[i] = H_N then g_N in hg's layout (the sums of the file's header comment).
+// r, w: sv.sample_ct doubles in RAW sample order, NaN r = no phenotype or outside the subset; z: sv.sample_ct x kp
+// doubles, raw sample-major.  n_y: the samples with a phenotype.
+hipError_t LaunchGlmScoreSparse(const SparseView &sv, uint32_t v_first, uint32_t nv, const double *r, const double *w,
+                                const double *z, uint32_t kp, uint32_t k, uint32_t n_y, const double *hg, double *sums,
+                                double *hgn, hipStream_t stream);
+// The rows from the sums.  null_status: PGH_GLM_OK, or the errcode that every row not decided by its own counts gets.
+hipError_t LaunchGlmScoreSolve(uint32_t nv, const double *sums, uint32_t kp, uint32_t k, const double *hgn,
+                               int null_status, pgh_glm_row *rows, hipStream_t stream);
+
 // ---- pgh_burden_sparse (burden_sparse.hip): the linear fit's sums of a weighted burden per variant set ----
 // What the kernel leaves per set beside its sums row.
 struct BurdenAux {

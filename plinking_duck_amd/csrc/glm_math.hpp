@@ -1,5 +1,6 @@
 // glm_math.hpp -- the small dense arithmetic of plink_glm, shared by the host and the device (glm.hip, api_glm.cpp):
-// two-sided p-values of a t or z statistic and an in-place Cholesky factor of a symmetric p x p matrix.
+// two-sided p-values of a t or z statistic, an in-place Cholesky factor of a symmetric p x p matrix and the exact
+// CONST_ALLELE test.
 // Written from the textbook definitions; every value is FP64.
 #pragma once
 
@@ -144,6 +145,19 @@ PGH_GLM_HD void GlmCholInverse(const double *l, int n, int ld, double *inv, doub
 			inv[i * ld + c] = col[i];
 		}
 	}
+}
+
+// CONST_ALLELE where the reference uses its two-pass variance sum (x - mean)^2 < 1e-20 (the multivariate linear and
+// the logistic fits).  Calls and dosages (value / 16384) lie on the 2^-14 grid in [0, 2], so n, sum x and sum x^2
+// are exact sums (sum x^2 while n < 2^23; for calls always), and a used set that is not constant has a variance sum
+// of at least 2^-28 (1 - 1/n) > 1e-20.  The rule is therefore "every used x is equal", which is n sum x^2 == (sum x)^2
+// (Cauchy-Schwarz: > otherwise).  Both products are compared exactly, each as an fma two-product (hi + lo).  The
+// one-pass sum x^2 - (sum x)^2 / n is not enough: for a constant dosage it can round to a positive number (2.3e-13 for
+// 20,001 samples at 4915 / 16384).
+PGH_GLM_HD bool GlmConstant(double n, double sx, double sxx) {
+	const double a = n * sxx, a_lo = fma(n, sxx, -a);
+	const double b = sx * sx, b_lo = fma(sx, sx, -b);
+	return a < b || (a == b && a_lo <= b_lo);
 }
 
 #undef PGH_GLM_HD
