@@ -223,26 +223,11 @@ hipError_t LaunchBurdenSparse(const SparseView &sv, uint32_t n_sets, const uint6
 		return hipSuccess;
 	}
 	const uint64_t per_group = BurdenScratchPerGroup(sv.sample_ct), mark_off = per_group / 9 * 8;
-#define PGH_BURDEN(KP_)                                                                                                \
-	case KP_:                                                                                                          \
-		BurdenSparseKernel<KP_><<<n_groups, kBlock, 0, stream>>>(sv, n_sets, set_off, set_vidx, weight, y, z, n_y,     \
-		                                                         static_cast<uint8_t *>(scratch), per_group, mark_off, \
-		                                                         counter, sums, aux, x_const);                         \
-		break;
-	switch (kp) {
-		PGH_BURDEN(0)
-		PGH_BURDEN(1)
-		PGH_BURDEN(2)
-		PGH_BURDEN(4)
-		PGH_BURDEN(8)
-		PGH_BURDEN(12)
-		PGH_BURDEN(16)
-		PGH_BURDEN(20)
-	default:
-		return hipErrorInvalidValue;
-	}
-#undef PGH_BURDEN
-	return hipGetLastError();
+	return GlmForWidth(kp, [&](auto width) {
+		BurdenSparseKernel<decltype(width)::value><<<n_groups, kBlock, 0, stream>>>(
+		    sv, n_sets, set_off, set_vidx, weight, y, z, n_y, static_cast<uint8_t *>(scratch), per_group, mark_off, counter,
+		    sums, aux, x_const);
+	});
 }
 
 } // namespace pgh

@@ -4,7 +4,8 @@
 // {n, sum x, sum x^2, sum x y, sum x z_j} for a tile of T variants (each sample's y and z are loaded once for the
 // tile); the covariate block [1, z, y]' [1, z, y] is one Gram per call, and a variant with missing calls subtracts
 // the Gram of those samples (a compacted list per sample chunk: sparse when calls are rarely missing, any count
-// works).  The solve is a Cholesky of the augmented [1, z, x, y] matrix per variant.
+// works; the ranking of the list and the barriers around its walk are TeamRank's, glm_team.hpp).  The solve is a
+// Cholesky of the augmented [1, z, x, y] matrix per variant.
 // Logistic / Firth: rounds of an accumulation launch (one workgroup per variant still in play) and a per-variant
 // update launch (one thread per variant).
 //
@@ -13,6 +14,7 @@
 #include "device_utils.hpp"
 #include "glm.hpp"
 #include "glm_math.hpp"
+#include "glm_team.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -133,18 +135,11 @@ __global__ void __launch_bounds__(kBlock) GlmGramKernel(GlmX g, int per_variant,
 		return;
 	}
 	extern __shared__ double list[]; // kBlock rows of q doubles (sized at launch)
-	__shared__ uint32_t wave_ct[kWaves];
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	// entry owned by this thread
 	int ea = -1, eb = -1;
 	if (threadIdx.x < ne) {
-		int t = threadIdx.x, a = 0;
-		while (t >= static_cast<int>(q) - a) {
-			t -= q - a;
-			a++;
-		}
-		ea = a;
-		eb = a + t;
+		PackedUpper(threadIdx.x, q, &ea, &eb);
 	}
 	double acc = 0.0;
 	for (uint32_t c0 = 0; c0 < n_out; c0 += kBlock) {
@@ -155,18 +150,10 @@ __global__ void __launch_bounds__(kBlock) GlmGramKernel(GlmX g, int per_variant,
 			yi = y[i];
 			take = yi == yi && (!per_variant || GlmValue(g, v, i) == -9.0);
 		}
-		const uint64_t bal = __ballot(take);
-		if (lane == 0) {
-			wave_ct[wave] = static_cast<uint32_t>(__popcll(bal));
-		}
-		__syncthreads();
-		uint32_t base = 0, total = 0;
-		for (int w = 0; w < kWaves; w++) {
-			base += w < wave ? wave_ct[w] : 0u;
-			total += wave_ct[w];
-		}
+		// the ordered-list step (TeamRank in glm_team.hpp)
+		uint32_t total;
+		const uint32_t pos = TeamRank<kBlock>(take, lane, wave, &total);
 		if (take) {
-			const uint32_t pos = base + static_cast<uint32_t>(__popcll(bal & ((1ull << lane) - 1ull)));
 			double *r = list + pos * q;
 			r[0] = 1.0;
 			for (uint32_t j = 0; j < k; j++) {
@@ -815,17 +802,10 @@ __global__ void __launch_bounds__(kBlock) GlmMultiCorrKernel(GlmX g, const doubl
 	extern __shared__ double lz[]; // kBlock list rows [1, z_1..z_k] (sized at launch)
 	__shared__ uint32_t lidx[kBlock];
 	__shared__ double ysub[kYSub * kGlmMultiPb];
-	__shared__ uint32_t wave_ct[kWaves];
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	int ea = -1, eb = -1;
 	if (threadIdx.x < nes) {
-		int t = threadIdx.x, a = 0;
-		while (t >= static_cast<int>(qs) - a) {
-			t -= qs - a;
-			a++;
-		}
-		ea = a;
-		eb = a + t;
+		PackedUpper(threadIdx.x, qs, &ea, &eb);
 	}
 	double acc_s = 0.0;
 	double acc_p[kCorrRegs];
@@ -840,18 +820,10 @@ __global__ void __launch_bounds__(kBlock) GlmMultiCorrKernel(GlmX g, const doubl
 			const double yi = ypat[i];
 			take = yi == yi && GlmValue(g, v, i) == -9.0;
 		}
-		const uint64_t bal = __ballot(take);
-		if (lane == 0) {
-			wave_ct[wave] = static_cast<uint32_t>(__popcll(bal));
-		}
-		__syncthreads();
-		uint32_t base = 0, total = 0;
-		for (int w = 0; w < kWaves; w++) {
-			base += w < wave ? wave_ct[w] : 0u;
-			total += wave_ct[w];
-		}
+		// the ordered-list step (TeamRank in glm_team.hpp)
+		uint32_t total;
+		const uint32_t pos = TeamRank<kBlock>(take, lane, wave, &total);
 		if (take) {
-			const uint32_t pos = base + static_cast<uint32_t>(__popcll(bal & ((1ull << lane) - 1ull)));
 			double *r = lz + pos * qs;
 			r[0] = 1.0;
 			for (uint32_t j = 0; j < k; j++) {
@@ -990,8 +962,7 @@ uint32_t Blocks(uint32_t n, uint32_t per) {
 } // namespace
 
 uint32_t GlmPadCovar(uint32_t k) {
-	static const uint32_t widths[] = {0, 1, 2, 4, 8, 12, 16, 20};
-	for (uint32_t w : widths) {
+	for (uint32_t w : kGlmWidths) {
 		if (k <= w) {
 			return w;
 		}
@@ -1004,24 +975,10 @@ hipError_t LaunchGlmSums(const GlmX &g, uint32_t nv, const double *y, const doub
 	if (nv == 0) {
 		return hipSuccess;
 	}
-#define PGH_SUMS(KP_, T_)                                                                                              \
-	case KP_:                                                                                                          \
-		GlmSumsKernel<KP_, T_><<<Blocks(nv, T_), kBlock, 0, stream>>>(g, nv, y, z, sums);                              \
-		break;
-	switch (kp) {
-		PGH_SUMS(0, 8)
-		PGH_SUMS(1, 8)
-		PGH_SUMS(2, 8)
-		PGH_SUMS(4, 4)
-		PGH_SUMS(8, 4)
-		PGH_SUMS(12, 2)
-		PGH_SUMS(16, 2)
-		PGH_SUMS(20, 2)
-	default:
-		return hipErrorInvalidValue;
-	}
-#undef PGH_SUMS
-	return hipGetLastError();
+	return GlmForWidth(kp, [&](auto width) {
+		constexpr int KP = decltype(width)::value, T = GlmSumsTile(KP);
+		GlmSumsKernel<KP, T><<<Blocks(nv, T), kBlock, 0, stream>>>(g, nv, y, z, sums);
+	});
 }
 
 hipError_t LaunchGlmGram(const GlmX *g, uint32_t nv, const double *sums, uint32_t sums_stride, uint32_t n_y,
@@ -1067,30 +1024,16 @@ hipError_t LaunchGlmIrlsAcc(int mode, const GlmX &g, const uint32_t *list, uint3
 	if (n == 0) {
 		return hipSuccess;
 	}
-#define PGH_IRLS_MODE(KP_)                                                                                             \
-	case KP_:                                                                                                          \
-		if (mode == 0) {                                                                                               \
-			GlmIrlsAccKernel<KP_, 0><<<n, kBlock, 0, stream>>>(g, list, y, z, st, beta, hinv0, acc);                   \
-		} else if (mode == 1) {                                                                                        \
-			GlmIrlsAccKernel<KP_, 1><<<n, kBlock, 0, stream>>>(g, list, y, z, st, beta, hinv0, acc);                   \
-		} else {                                                                                                       \
-			GlmIrlsAccKernel<KP_, 2><<<n, kBlock, 0, stream>>>(g, list, y, z, st, beta, hinv0, acc);                   \
-		}                                                                                                              \
-		break;
-	switch (kp) {
-		PGH_IRLS_MODE(0)
-		PGH_IRLS_MODE(1)
-		PGH_IRLS_MODE(2)
-		PGH_IRLS_MODE(4)
-		PGH_IRLS_MODE(8)
-		PGH_IRLS_MODE(12)
-		PGH_IRLS_MODE(16)
-		PGH_IRLS_MODE(20)
-	default:
-		return hipErrorInvalidValue;
-	}
-#undef PGH_IRLS_MODE
-	return hipGetLastError();
+	return GlmForWidth(kp, [&](auto width) {
+		constexpr int KP = decltype(width)::value;
+		if (mode == 0) {
+			GlmIrlsAccKernel<KP, 0><<<n, kBlock, 0, stream>>>(g, list, y, z, st, beta, hinv0, acc);
+		} else if (mode == 1) {
+			GlmIrlsAccKernel<KP, 1><<<n, kBlock, 0, stream>>>(g, list, y, z, st, beta, hinv0, acc);
+		} else {
+			GlmIrlsAccKernel<KP, 2><<<n, kBlock, 0, stream>>>(g, list, y, z, st, beta, hinv0, acc);
+		}
+	});
 }
 
 hipError_t LaunchGlmNewtonUpdate(uint32_t nv, uint32_t kp, uint32_t k, const double *acc, GlmState *st, double *beta,
@@ -1154,24 +1097,9 @@ hipError_t LaunchGlmMultiWhole(uint32_t n_out, const double *yb, uint32_t pb, co
 	if (k > kp) {
 		return hipErrorInvalidValue;
 	}
-#define PGH_WHOLE(KP_)                                                                                                 \
-	case KP_:                                                                                                          \
-		GlmMultiWholeKernel<KP_><<<pb, kBlock, 0, stream>>>(n_out, yb, z, k, whole);                                   \
-		break;
-	switch (kp) {
-		PGH_WHOLE(0)
-		PGH_WHOLE(1)
-		PGH_WHOLE(2)
-		PGH_WHOLE(4)
-		PGH_WHOLE(8)
-		PGH_WHOLE(12)
-		PGH_WHOLE(16)
-		PGH_WHOLE(20)
-	default:
-		return hipErrorInvalidValue;
-	}
-#undef PGH_WHOLE
-	return hipGetLastError();
+	return GlmForWidth(kp, [&](auto width) {
+		GlmMultiWholeKernel<decltype(width)::value><<<pb, kBlock, 0, stream>>>(n_out, yb, z, k, whole);
+	});
 }
 
 hipError_t LaunchGlmMultiCorr(const GlmX &g, uint32_t nv, const double *sums, uint32_t n_y, const double *ypat,

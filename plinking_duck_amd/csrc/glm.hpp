@@ -9,6 +9,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <iterator>
+#include <type_traits>
+#include <utility>
 
 namespace pgh {
 
@@ -33,8 +36,25 @@ struct GlmState {
 };
 enum : int32_t { kGlmActive = 0, kGlmConverged = 1, kGlmFailed = 2, kGlmUnfinished = 3, kGlmDecided = 16 };
 
+// The covariate widths KP that the kernels templated on a width are instantiated for.
+constexpr uint32_t kGlmWidths[] = {0, 1, 2, 4, 8, 12, 16, 20};
 //! Padded covariate count of the kernels: the smallest instantiated width >= k (k <= 20).
 uint32_t GlmPadCovar(uint32_t k);
+// Variants per workgroup of GlmSumsKernel at the width KP.
+constexpr int GlmSumsTile(int kp) {
+	return kp <= 2 ? 8 : kp <= 8 ? 4 : 2;
+}
+// Calls launch(std::integral_constant<int, KP>()) with KP == kp, which enqueues the kernels of that width, and returns
+// hipGetLastError(); hipErrorInvalidValue if kp is not an instantiated width.
+template <class Launch, size_t... I>
+hipError_t GlmForWidth(uint32_t kp, Launch &&launch, std::index_sequence<I...>) {
+	const bool known = ((kp == kGlmWidths[I] && (launch(std::integral_constant<int, kGlmWidths[I]>()), true)) || ...);
+	return known ? hipGetLastError() : hipErrorInvalidValue;
+}
+template <class Launch>
+hipError_t GlmForWidth(uint32_t kp, Launch &&launch) {
+	return GlmForWidth(kp, launch, std::make_index_sequence<std::size(kGlmWidths)>());
+}
 //! Accumulators of one variant in the Newton / Firth rounds: packed upper Hessian, a vector, a scalar, a flag.
 inline uint32_t GlmIrlsEntries(uint32_t kp) {
 	const uint32_t pp = kp + 2;

@@ -1,0 +1,291 @@
+// glm_team.hpp -- the device code the GLM kernels share: a team's barrier, the ordered-list step (rank, write, walk),
+// the team reduction, the packed-upper decode, and the walk of a sparse row's entries that GlmSparseKernel
+// (glm_sparse.hip) and GlmScoreSparseKernel (glm_score_sparse.hip) instantiate with their arithmetic.
+//
+// A team is one wave (TEAM == 64) or the whole 256-thread workgroup (TEAM == 256).  Everything here is called by
+// every thread of the team under team-uniform control flow: each function that says so holds a barrier.
+#pragma once
+
+#include "device_utils.hpp"
+#include "glm.hpp"
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace pgh {
+
+namespace {
+
+constexpr int kTeamBlock = 256;
+constexpr int kTeamWaves = kTeamBlock / 64;
+// (k + 2)(k + 3) / 2 at k = PGH_GLM_MAX_COVAR: the most entries the owners of one list share
+constexpr int kTeamMaxOwned = 253;
+
+// Orders a team's LDS writes before its LDS reads.  A wave's LDS instructions complete in issue order, so a team of
+// one wave only has to keep the compiler from moving them.
+template <int TEAM>
+__device__ __forceinline__ void TeamSync() {
+	if constexpr (TEAM == kTeamBlock) {
+		__syncthreads();
+	} else {
+		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+		__builtin_amdgcn_wave_barrier();
+		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+	}
+}
+
+// Entry e of the packed row-major upper triangle of order q -> (a, b), a <= b < q.  e < q (q + 1) / 2.
+__device__ __forceinline__ void PackedUpper(int e, int q, int *a, int *b) {
+	int row = 0;
+	while (e >= q - row) {
+		e -= q - row;
+		row++;
+	}
+	*a = row;
+	*b = row + e;
+}
+
+// The ordered-list step, part one.  Returns how many threads before this one in thread order have `take` set, and in
+// *total how many of the team have: the takers' ranks are 0 .. *total - 1 in thread order, and *total is the same on
+// every thread, so code under `if (*total)` is team-uniform and may hold a barrier.
+//
+// How a caller uses it, once per step of its loop over the samples or entries:
+//   rank = TeamRank(take, ..., &total);  if (take) write list row `rank`;  TeamSync;  every owner walks rows
+//   0 .. total - 1 in order;  TeamSync.
+// The first TeamSync puts the rows before their readers.  The second keeps the next step from rewriting the list under
+// a thread that still walks it; it also stands between this call's reads of wave_ct and the next call's writes, which
+// is why a caller that skips the walk when total == 0 still runs the second one.
+template <int TEAM>
+__device__ __forceinline__ uint32_t TeamRank(bool take, int lane, int wave, uint32_t *total) {
+	const uint64_t bal = __ballot(take);
+	uint32_t before = 0;
+	*total = static_cast<uint32_t>(__popcll(bal));
+	if constexpr (TEAM == kTeamBlock) {
+		__shared__ uint32_t wave_ct[kTeamWaves];
+		if (lane == 0) {
+			wave_ct[wave] = *total;
+		}
+		__syncthreads();
+		*total = 0;
+		for (int w = 0; w < kTeamWaves; w++) {
+			before += w < wave ? wave_ct[w] : 0u;
+			*total += wave_ct[w];
+		}
+	}
+	return before + static_cast<uint32_t>(__popcll(bal & ((1ull << lane) - 1ull)));
+}
+
+// Team totals of N doubles and four integer counts, on every thread: a butterfly per wave, then (TEAM == 256) the
+// waves' partials added in the order 0..3 from LDS.  One barrier; the LDS it uses is not written again.
+template <int TEAM, int N>
+__device__ __forceinline__ void TeamSums(double (&v)[N], long long (&c)[4], int lane, int wave) {
+#pragma unroll
+	for (int j = 0; j < N; j++) {
+		v[j] = WaveSum(v[j]);
+	}
+#pragma unroll
+	for (int j = 0; j < 4; j++) {
+		c[j] = WaveSum(c[j]);
+	}
+	if constexpr (TEAM == kTeamBlock) {
+		__shared__ double part[kTeamWaves][N];
+		__shared__ long long ipart[kTeamWaves][4];
+		if (lane == 0) {
+#pragma unroll
+			for (int j = 0; j < N; j++) {
+				part[wave][j] = v[j];
+			}
+#pragma unroll
+			for (int j = 0; j < 4; j++) {
+				ipart[wave][j] = c[j];
+			}
+		}
+		__syncthreads();
+#pragma unroll
+		for (int j = 0; j < N; j++) {
+			v[j] = part[0][j];
+		}
+#pragma unroll
+		for (int j = 0; j < 4; j++) {
+			c[j] = ipart[0][j];
+		}
+		for (int w = 1; w < kTeamWaves; w++) {
+#pragma unroll
+			for (int j = 0; j < N; j++) {
+				v[j] += part[w][j];
+			}
+#pragma unroll
+			for (int j = 0; j < 4; j++) {
+				c[j] += ipart[w][j];
+			}
+		}
+	}
+}
+
+// The rows of a sparse-resident dataset (SparseView's arrays) that one launch of an entry kernel covers.
+struct SparseRows {
+	const int32_t *row_of;
+	const uint64_t *off;
+	const uint32_t *entries;
+	const uint8_t *pool; // read only by a Model that walks dense-form rows
+	uint64_t pitch;
+	uint32_t sample_ct, v_first, nv;
+};
+
+// The walk of one row by one team.  TEAM == 64: a wave per row, four rows per workgroup, the sparse rows of at most
+// kGlmSparseLong entries.  TEAM == 256: a workgroup per row, the longer sparse rows and (Model::kWalksDense) the rows
+// held in the dense form, walked from their pool row, one sample per lane per step, as base-0 rows whose entries are
+// the samples with a code other than 0.  The two launches cover the same rows and each returns from the other's.
+//
+// A row is a base code b and the entries that differ from it.  Of the entries that are used (sample below sample_ct,
+// m.Load says its staged value is a number), M are those with code 3 and C the others.  The walk leaves
+//   n = n_y - |M|, sum x = b n + sum_C (x - b), sum x^2 = b^2 n + sum_C (x^2 - b^2)   (b == 3: n = |C|, sums over C)
+// in sums[i][0..2], integers until they are stored; the Model's NL lane sums over C, one fma chain per lane and then
+// TeamSums; and per entry of the Model's packed set the sum of m.Term over the list set (M, or C when b == 3) in entry
+// order, by the one thread that owns the entry.  m.Epilogue stores them.  z: the kp = KP doubles of a sample's
+// covariates at z[s * KP], raw-sample order.  lds: 256 list rows [1, z_1..z_k, Model's tail] of q = k + 1 + Model::kTail
+// doubles.
+//
+// A Model supplies
+//   kNS, kNL, kTail, kWalksDense;  double *sums (rows of kNS);
+//   Sample: what Load(s, &v) reads of sample s (false: the sample is not used);
+//   Add(dd, v, zi, ls): a called entry's d = x - b joins the lane sums;  Tail(v, row + k + 1): the list row past z;
+//   Own, OwnedEntry(e, k), Term(list, row, own): an owner's entry (own.a < 0: there is no entry e) and its term of the
+//   list row that starts at list[row];
+//   Zero(i, tid, k) unless kWalksDense: the result row of a dense-form row, by a wave;
+//   Epilogue<TEAM>(i, tid, k, base3, bx, ls, own, acc): the rest of sums[i] and the owned sums; thread tid owns the
+//   entries tid + t * TEAM, acc[t] is the sum of entry own[t].
+template <class Model, int KP, int TEAM>
+__device__ __forceinline__ void TeamWalkSparseRow(const SparseRows &rows, const double *__restrict__ z, uint32_t k,
+                                                  uint32_t n_y, const Model &m, double *lds) {
+	constexpr int NOWN = (kTeamMaxOwned + TEAM - 1) / TEAM; // entries a thread owns
+	constexpr int TEAMS = kTeamBlock / TEAM;
+	const uint32_t q = k + 1 + Model::kTail;
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const int tid = TEAM == kTeamBlock ? static_cast<int>(threadIdx.x) : lane;
+	const uint32_t i = blockIdx.x * TEAMS + (TEAM == kTeamBlock ? 0 : wave);
+	if (i >= rows.nv) {
+		return; // (the whole team)
+	}
+	const uint32_t r = rows.v_first + i;
+	const int32_t ro = rows.row_of[r];
+	const bool dense = ro >= 0;
+	double *s_out = m.sums + static_cast<uint64_t>(i) * Model::kNS;
+	uint64_t e0 = 0, e1 = rows.sample_ct; // a dense-form row: its samples
+	if (dense) {
+		if constexpr (!Model::kWalksDense) {
+			if (TEAM == 64) {
+				m.Zero(i, tid, k); // its result row comes from the dense kernels
+			}
+			return;
+		} else if (TEAM != kTeamBlock) {
+			return; // the workgroup launch's row
+		}
+	} else {
+		e0 = rows.off[r];
+		e1 = rows.off[r + 1];
+		if ((e1 - e0 > kGlmSparseLong) != (TEAM == kTeamBlock)) {
+			return; // the other launch's row
+		}
+	}
+	const uint8_t *prow = Model::kWalksDense && dense ? rows.pool + static_cast<uint64_t>(ro) * rows.pitch : nullptr;
+	const bool base3 = ro == -4;
+	const int bx = (dense || base3) ? 0 : -1 - ro;
+	double *list = lds + (TEAM == kTeamBlock ? 0 : static_cast<uint32_t>(wave) * 64u * q);
+
+	// the entries this thread owns: e = tid + t * TEAM
+	typename Model::Own own[NOWN];
+	double acc[NOWN];
+#pragma unroll
+	for (int t = 0; t < NOWN; t++) {
+		own[t] = m.OwnedEntry(tid + t * TEAM, static_cast<int>(k));
+		acc[t] = 0.0;
+	}
+
+	double ls[Model::kNL];
+#pragma unroll
+	for (int j = 0; j < Model::kNL; j++) {
+		ls[j] = 0.0;
+	}
+	long long c_miss = 0, c_called = 0, sx = 0, sxx = 0; // |M|, |C|, sum_C (x - b), sum_C (x^2 - b^2)
+	for (uint64_t p0 = e0; p0 < e1; p0 += TEAM) {
+		const uint64_t p = p0 + tid;
+		bool used = false;
+		uint32_t code = 0, s = 0;
+		typename Model::Sample v {};
+		if (p < e1) {
+			bool entry;
+			if (Model::kWalksDense && dense) {
+				s = static_cast<uint32_t>(p);
+				code = (prow[s >> 2] >> (2 * (s & 3u))) & 3u;
+				entry = code != 0u;
+			} else {
+				const uint32_t x = rows.entries[p];
+				s = x >> 2;
+				code = x & 3u;
+				entry = s < rows.sample_ct;
+			}
+			if (entry) {
+				used = m.Load(s, &v);
+			}
+		}
+		double zi[KP > 0 ? KP : 1];
+		if (used) {
+#pragma unroll
+			for (int j = 0; j < KP; j++) {
+				zi[j] = z[static_cast<uint64_t>(s) * KP + j];
+			}
+			if (code != 3u) {
+				const int d = static_cast<int>(code) - bx;
+				c_called++;
+				sx += d;
+				sxx += static_cast<int>(code * code) - bx * bx;
+				m.Add(static_cast<double>(d), v, zi, ls);
+			} else {
+				c_miss++;
+			}
+		}
+		// the list set of this step, in entry order (base 3: the called entries, which are all of them)
+		const bool take = used && (base3 || code == 3u);
+		uint32_t total;
+		const uint32_t rank = TeamRank<TEAM>(take, lane, wave, &total);
+		if (total) { // (the whole team agrees)
+			if (take) {
+				double *row = list + rank * q;
+				row[0] = 1.0;
+#pragma unroll
+				for (int j = 0; j < KP; j++) {
+					if (j < static_cast<int>(k)) {
+						row[1 + j] = zi[j];
+					}
+				}
+				m.Tail(v, row + k + 1);
+			}
+			TeamSync<TEAM>();
+#pragma unroll
+			for (int t = 0; t < NOWN; t++) {
+				if (own[t].a >= 0) {
+					for (uint32_t l = 0; l < total; l++) {
+						acc[t] += m.Term(list, l * q, own[t]);
+					}
+				}
+			}
+		}
+		TeamSync<TEAM>(); // the list and TeamRank's counts are rewritten by the next step
+	}
+
+	long long ct[4] = {c_miss, c_called, sx, sxx};
+	TeamSums<TEAM>(ls, ct, lane, wave);
+	m.template Epilogue<TEAM>(i, tid, k, base3, bx, ls, own, acc);
+	const long long n = base3 ? ct[1] : static_cast<long long>(n_y) - ct[0];
+	if (tid == 0) {
+		s_out[0] = static_cast<double>(n);
+		s_out[1] = static_cast<double>(bx * n + ct[2]);
+		s_out[2] = static_cast<double>(bx * bx * n + ct[3]);
+	}
+}
+
+} // namespace
+
+} // namespace pgh

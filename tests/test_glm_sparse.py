@@ -179,6 +179,26 @@ def test_long_rows_take_the_workgroup_path(gpu_lib, tmp_path):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("kp", [1, 2, 4, 8, 12, 16, 20])
+def test_every_instantiated_width(gpu_lib, rare_files, kp):
+    """k = kp and kp - 1 for every width GlmPadCovar returns (kp = 1 covers the width 0)."""
+    f = rare_files[4099]
+    idx = sorted(set(range(5, M_R, 55)) | set(HET_ROWS))[:12]
+    assert len(idx) == 12
+    sp = f.sparse(max_minor=f.n)
+    assert sp.sparse_info().dense_variant_ct == 0
+    for k in (kp, kp - 1):
+        rng = np.random.default_rng(3000 + k)
+        Z = _covariates(rng, k, f.n)
+        y = _oracle()._pheno(rng, f.n, "linear", Z)
+        zc = Z if k else None
+        got = sp.glm_sparse(y, zc)
+        _close(got, f.dense.glm(y, zc, model="linear"), ctx=k)
+        _oracle().check_rows(_rows(got, idx), f.x[idx], y, Z, "linear", rel=1e-9)
+    sp.close()
+
+
+@pytest.mark.gpu
 def test_sample_subset(gpu_lib, rare_files):
     f = rare_files[4099]
     rng = np.random.default_rng(12)

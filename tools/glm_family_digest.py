@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """One SHA-256 per case over the result bytes of the GLM family (pgh_glm, pgh_glm_multi, pgh_glm_sparse,
-pgh_burden_sparse), pgh_score_sparse, and the plink_ld pair sums and sparse counts that share their wave sums: the
-paths a change to the family's host staging, scratch layout or chunk loops can touch.  Two builds of the library
+pgh_glm_score_sparse, pgh_burden_sparse), pgh_score_sparse, and the plink_ld pair sums and sparse counts that share
+their wave sums: the paths a change to the family's kernels, host staging, scratch layout or chunk loops can touch.  Two builds of the library
 compute the same rows bit for bit exactly when their outputs of this tool are equal line for line; PGENHIP_LIB names
 the build (plinking_duck_amd/lib.py).  A case that differs between two runs of ONE build is not deterministic from
 run to run and its line says nothing.
@@ -145,6 +145,9 @@ for v, rate in ((7, 0.01), (8, 0.3)):  # het-majority rows: rare_matrix draws no
     rare[v, hit] = rng.integers(0, 4, hit.sum(), dtype=np.uint8)
 rare[9] = 0  # a row past kGlmSparseLong entries
 rare[9, rng.permutation(N_R)[:1500]] = rng.integers(1, 4, 1500, dtype=np.uint8)
+rare[10] = 3  # a missing-majority row past kGlmSparseLong called entries: every one of them joins the list
+rare[10, rng.permutation(N_R)[:1300]] = rng.integers(0, 3, 1300, dtype=np.uint8)
+assert np.bincount(rare[10], minlength=4).argmax() == 3 and (rare[10] != 3).sum() > 1024
 minor = N_R - np.array([np.bincount(r, minlength=4).max() for r in rare])
 assert (minor > 1024).any() and ((minor > 0) & (minor <= 1024)).any()  # both sides of kGlmSparseLong
 rare_path = os.path.join(out_dir, "rare.pgen")
@@ -153,6 +156,8 @@ keep_r = rng.random(N_R) < 0.7
 n_keep_r = int(keep_r.sum())
 Zr, Zrs = covar(rng, 3, N_R), covar(rng, 3, n_keep_r)
 yr, yrs = pheno(rng, N_R, Zr), pheno(rng, n_keep_r, Zrs)
+yb, ybs = pheno(rng, N_R, Zr, "logistic"), pheno(rng, n_keep_r, Zrs, "logistic")
+WIDTHS = (1, 2, 4, 8, 12, 16, 20)  # the instantiated covariate widths past 0; k = kp - 1 at kp = 1 covers the width 0
 set_off = np.concatenate([[0], np.cumsum(rng.integers(0, 12, 40))]).astype(np.uint64)
 set_vidx = rng.integers(0, M_R, int(set_off[-1])).astype(np.uint32)
 set_w = rng.normal(size=len(set_vidx))
@@ -168,6 +173,13 @@ for max_minor, form in ((N_R, "entries only"), (1, "with dense-form rows")):
     sub = sp.subset(keep_r)
     emit(f"glm_sparse {form}", sp.glm_sparse(yr, Zr), sp.glm_sparse(yr, None))
     emit(f"glm_sparse {form}, subset", sp.glm_sparse(yrs, Zrs, subset=sub, v_begin=3, v_end=M_R - 2))
+    emit(f"glm_score_sparse {form}", sp.glm_score_sparse(yb, Zr), sp.glm_score_sparse(yb, None))
+    emit(f"glm_score_sparse {form}, subset", sp.glm_score_sparse(ybs, Zrs, subset=sub, v_begin=3, v_end=M_R - 2))
+    if max_minor == N_R:
+        for k in sorted({k for kp in WIDTHS for k in (kp, kp - 1)}):
+            Zk = covar(rng, k, N_R)
+            emit(f"glm_sparse {form}, k={k}", sp.glm_sparse(pheno(rng, N_R, Zk), Zk))
+            emit(f"glm_score_sparse {form}, k={k}", sp.glm_score_sparse(pheno(rng, N_R, Zk, "logistic"), Zk))
     emit(f"burden_sparse {form}, weighted", sp.burden_sparse(yr, set_off, set_vidx, weights=set_w, covariates=Zr))
     emit(f"burden_sparse {form}, unweighted", sp.burden_sparse(yr, set_off, set_vidx, covariates=Zr))
     emit(f"burden_sparse {form}, subset", sp.burden_sparse(yrs, set_off, set_vidx, weights=set_w, covariates=Zrs,
@@ -182,11 +194,12 @@ for max_minor, form in ((N_R, "entries only"), (1, "with dense-form rows")):
     sub.close()
     sp.close()
 
-# carrier lists across a chunk boundary of pgh_glm_sparse (16384 variants)
+# carrier lists across a chunk boundary of pgh_glm_sparse and pgh_glm_score_sparse (16384 variants)
 M_C, N_C = 17000, 311
 prefix = os.path.join(out_dir, "carriers")
 write_carrier_pfile(prefix, M_C, N_C, carrier_rows(M_C, N_C, 0.02, 5))
 sp = L.Dataset.open(prefix + ".pgen", sparse=True)
 Zc = covar(rng, 2, N_C)
 emit("glm_sparse across a chunk", sp.glm_sparse(pheno(rng, N_C, Zc), Zc))
+emit("glm_score_sparse across a chunk", sp.glm_score_sparse(pheno(rng, N_C, Zc, "logistic"), Zc))
 sp.close()
