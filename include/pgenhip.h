@@ -144,7 +144,7 @@ void pgh_close(pgh_dataset *ds);
  * choice.  Hardcalls only (dosage and phase tracks are stepped over; pgh_info still reports them), one device,
  * fewer than 2^30 samples (PGH_ERR_ARG otherwise).  Served by pgh_get_info, pgh_close, pgh_counts_range(_dev),
  * pgh_sample_counts(_dev), pgh_copy_rows_to_host, pgh_subset_* and the entry points made for this form:
- * pgh_glm_sparse, pgh_glm_score_sparse, pgh_burden_sparse and pgh_score_sparse; every other entry point that reads rows (pgh_score,
+ * pgh_glm_sparse, pgh_glm_score_sparse(_spa), pgh_burden_sparse and pgh_score_sparse; every other entry point that reads rows (pgh_score,
  * pgh_score_dev and the score plans among them) returns PGH_ERR_ARG, and pgh_device_rows returns NULL. */
 typedef struct pgh_sparse_info {
 	uint32_t sparse_variant_ct; /* variants held as base + entries                                  */
@@ -582,6 +582,47 @@ int pgh_glm_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_b
 int pgh_glm_score_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                          const double *phenotype, uint32_t n_covar, const double *covariates,
                          pgh_glm_row *out, char *errbuf);
+/* pgh_glm_score_sparse with a SADDLEPOINT p-value beside the normal one, for the rows the normal tail serves badly:
+ * rare variants under an unbalanced case / control ratio (the "fast SPA" of Dey et al. 2017: the exact cumulant
+ * generating function over the row's entries, a normal term for every other sample).  Arguments, argument checks and
+ * error codes are pgh_glm_score_sparse's.  In addition spa_cutoff must be at least 0.1 (+infinity: never apply it;
+ * NaN or a smaller value is PGH_ERR_ARG, "spa_cutoff must be at least 0.1"), and p_spa and spa_state, one element per
+ * variant, must not be NULL.  On any error the outputs are untouched.
+ *
+ * out[i] is pgh_glm_score_sparse's row for the same arguments bit for bit; its p stays the normal p-value.
+ * spa_state[i]: 0 = not applied (the row is not fitted, or |stat| <= spa_cutoff), 1 = applied, 2 = attempted and
+ * failed.  p_spa[i]: NaN when the row is not fitted, out[i].p bit for bit in state 0 (fitted) and in state 2, the
+ * saddlepoint p in state 1.
+ *
+ * Definition, in pgh_glm_score_sparse's notation (S, N, Zt, w, r, d = x - b, t = H_N^-1 c in the d parameterisation,
+ * U, V).  mu_i = the null model's fitted mean, recovered from the staged residual: mu = r > 0 ? 1 - r : -r.
+ * gt_i = d_i - Zt_i t for i in N (d_i = 0 for a sample that is not an entry).  E = the row's used called entries: the
+ * samples of N that the row holds as entries.  A row held in the dense form counts as a base-0 row, so its E is its
+ * called samples with a code other than 0; a missing-majority row (b = 3) has E = N.  V_E = sum_E w gt^2; V_rest = 0
+ * by rule when b = 3, otherwise max(V - V_E, 0).
+ *   K(s)   = sum_E [ln(1 - mu + mu e^(gt s)) - s mu gt] + V_rest s^2 / 2
+ *   K'(s)  = sum_E gt (pi - mu) + V_rest s         pi = mu / (mu + (1 - mu) e^(-gt s))
+ *   K''(s) = sum_E gt^2 pi (1 - pi) + V_rest       K'(0) = 0, K''(0) = V
+ * evaluated with one exp of -|gt s| per entry (log1p / expm1 of it for K), so that nothing overflows or cancels for
+ * large |gt s|.  For each of q+ = |U| and q- = -|U|, s^ is the root of K'(s^) = q, found by a safeguarded Newton
+ * iteration: K' is increasing, the root has the sign of q; the bracket starts as [0, open), the first point is the
+ * Newton step from 0, |q| / V; while the far side is open a step may not exceed 1/sqrt(V), doubling each time the
+ * limit is used; once it is closed a Newton step that leaves the bracket is replaced by its midpoint.  The root is
+ * taken when |delta s| sqrt(V) <= 1e-12 (or the bracket is that narrow, or |delta s| <= 2^-50 |s|: far out the
+ * first bound is below the spacing of s), after at most 64 evaluations of K', K''.
+ *   omega = sign(s^) sqrt(2 (s^ q - K(s^)))   nu = s^ sqrt(K''(s^))   tail = Phibar(|omega + ln(nu / omega) / omega|)
+ *   p_spa = tail(q+) + tail(q-)
+ * State 2: for either tail no root within the 64 evaluations, or 2 (s^ q - K) <= 0, or nu / omega <= 0, or anything
+ * not finite.  With V_rest = 0 and q outside the support of the score there is no root, and the cap is the outcome.
+ *
+ * p_spa depends on the form a row is held in, because E does: datasets opened with another max_minor agree to
+ * rounding only for the rows whose E is the same set, and within the quality of the approximation otherwise.  A row's
+ * (out, p_spa, spa_state) is a function of its variant's entries, the phenotype, the covariates, the subset and
+ * spa_cutoff only: not of v_begin, the chunk, the window the dataset was opened with or the rows around it, and the
+ * same call returns the same bytes every time. */
+int pgh_glm_score_sparse_spa(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                             const double *phenotype, uint32_t n_covar, const double *covariates, double spa_cutoff,
+                             pgh_glm_row *out, double *p_spa, uint8_t *spa_state, char *errbuf);
 /* Gene-set BURDEN tests over a SPARSE-RESIDENT dataset (pgh_open_sparse), from the variants' entries: per set, the
  * variants are collapsed into one weighted burden per sample and the phenotype is regressed on it (linear).
  *

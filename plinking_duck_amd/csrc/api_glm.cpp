@@ -642,8 +642,18 @@ int GlmScoreNullFit(uint32_t n_out, const double *d_y, const double *d_z, uint32
 // pgh_glm_score_sparse on one sparse-resident dataset.  y and z are staged in output-sample order for the null fit,
 // which leaves r and w in raw-sample order (NaN r outside the subset: uploaded so, the fit writes the subset's
 // samples only); z is staged a second time in raw-sample order when there is a subset, as in GlmSparseOne.
+// spa != null (pgh_glm_score_sparse_spa): after a chunk's rows, GlmScoreSpaKernel replaces the p-value of the rows
+// beyond the cutoff; the workgroup form's stashes are cut from the same scratch block, within kSpaStashBytes.
+struct GlmScoreSpaArgs {
+	double cutoff;
+	double *p_spa;
+	uint8_t *state;
+};
+constexpr uint64_t kSpaStashBytes = 256ull << 20;
+
 int GlmScoreSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
-                      const double *phenotype, uint32_t k, const double *covariates, pgh_glm_row *out, char *errbuf) {
+                      const double *phenotype, uint32_t k, const double *covariates, pgh_glm_row *out, char *errbuf,
+                      const GlmScoreSpaArgs *spa = nullptr) {
 	PGH_ENTER(ds);
 	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct, n_raw = ds->sample_ct;
 	const uint32_t nv_all = v_end - v_begin;
@@ -669,6 +679,24 @@ int GlmScoreSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t 
 	lay.Add(&d_sums, c * ns);
 	lay.Add(&d_hgn, c * ne);
 	lay.Add(&d_rows, c);
+	// the saddlepoint path: [t, U, V], p_spa and the state per chunk variant, and a stash per workgroup of the
+	// workgroup form, at most four workgroups per compute unit
+	pgh::GlmScoreSpaOut so;
+	uint8_t *d_stash = nullptr;
+	uint32_t n_groups = 0;
+	if (spa) {
+		int device = 0, cus = 0;
+		PGH_HIP(hipGetDevice(&device), "glm_score_sparse_spa device");
+		PGH_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device),
+		        "glm_score_sparse_spa device attribute");
+		const uint64_t per_group = pgh::GlmScoreSpaStashPerGroup(n_raw);
+		n_groups = static_cast<uint32_t>(std::min<uint64_t>(std::min<uint64_t>(chunk, 4ull * static_cast<uint32_t>(std::max(cus, 1))),
+		                                                    std::max<uint64_t>(1, kSpaStashBytes / per_group)));
+		lay.Add(&so.t, c * (kp + 3));
+		lay.Add(&so.p_spa, c);
+		lay.Add(&so.state, c);
+		lay.Add(&d_stash, per_group * n_groups);
+	}
 	void *scratch = nullptr;
 	PGH_HIP(PghThreadScratch(lay.total, st, &scratch), "glm_score_sparse scratch");
 	lay.Bind(scratch);
@@ -694,9 +722,19 @@ int GlmScoreSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t 
 		const uint32_t nv = std::min(chunk, nv_all - c0);
 		PGH_HIP(pgh::LaunchGlmScoreSparse(ds->Sparse(), l_begin + c0, nv, d_r, d_w, d_zr, kp, k, n_y, d_hg, d_sums, d_hgn, st),
 		        "glm_score_sparse entry kernel");
-		PGH_HIP(pgh::LaunchGlmScoreSolve(nv, d_sums, kp, k, d_hgn, null_status, d_rows, st), "glm_score_sparse solve kernel");
+		PGH_HIP(pgh::LaunchGlmScoreSolve(nv, d_sums, kp, k, d_hgn, null_status, d_rows, st, so),
+		        "glm_score_sparse solve kernel");
 		PGH_HIP(hipMemcpyAsync(out + c0, d_rows, sizeof(pgh_glm_row) * nv, hipMemcpyDeviceToHost, st),
 		        "glm_score_sparse rows copy");
+		if (spa) {
+			PGH_HIP(pgh::LaunchGlmScoreSpa(ds->Sparse(), l_begin + c0, nv, d_r, d_w, d_zr, kp, d_rows, so.t, spa->cutoff,
+			                               n_groups, d_stash, so.p_spa, so.state, st),
+			        "glm_score_sparse_spa kernel");
+			PGH_HIP(hipMemcpyAsync(spa->p_spa + c0, so.p_spa, 8ull * nv, hipMemcpyDeviceToHost, st),
+			        "glm_score_sparse_spa p copy");
+			PGH_HIP(hipMemcpyAsync(spa->state + c0, so.state, nv, hipMemcpyDeviceToHost, st),
+			        "glm_score_sparse_spa state copy");
+		}
 		PGH_HIP(hipStreamSynchronize(st), "glm_score_sparse sync");
 	}
 	return PGH_OK;
@@ -874,9 +912,12 @@ extern "C" int pgh_glm_sparse(const pgh_dataset *ds, const pgh_subset *subset, u
 	return GlmSparseOne(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, out, errbuf);
 }
 
-extern "C" int pgh_glm_score_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
-                                    const double *phenotype, uint32_t n_covar, const double *covariates,
-                                    pgh_glm_row *out, char *errbuf) {
+namespace {
+
+// pgh_glm_score_sparse and pgh_glm_score_sparse_spa (spa != null) after the latter's own argument checks.
+int GlmScoreSparseEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                        const double *phenotype, uint32_t n_covar, const double *covariates, pgh_glm_row *out,
+                        const GlmScoreSpaArgs *spa, char *errbuf) {
 	PGH_ONE_DEVICE(ds);
 	PGH_SPARSE_ROWS(ds);
 	const int rc = GlmCheckCommon(ds, subset, v_begin, v_end, 1, phenotype, n_covar, covariates, PGH_GLM_LOGISTIC, out,
@@ -904,7 +945,31 @@ extern "C" int pgh_glm_score_sparse(const pgh_dataset *ds, const pgh_subset *sub
 	if (v_end == v_begin) {
 		return PGH_OK;
 	}
-	return GlmScoreSparseOne(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, out, errbuf);
+	return GlmScoreSparseOne(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, out, errbuf, spa);
+}
+
+} // namespace
+
+extern "C" int pgh_glm_score_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                                    const double *phenotype, uint32_t n_covar, const double *covariates,
+                                    pgh_glm_row *out, char *errbuf) {
+	return GlmScoreSparseEntry(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, out, nullptr, errbuf);
+}
+
+extern "C" int pgh_glm_score_sparse_spa(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin,
+                                        uint32_t v_end, const double *phenotype, uint32_t n_covar,
+                                        const double *covariates, double spa_cutoff, pgh_glm_row *out, double *p_spa,
+                                        uint8_t *spa_state, char *errbuf) {
+	if (!(spa_cutoff >= 0.1)) { // (NaN too)
+		SetErr(errbuf, "spa_cutoff must be at least 0.1");
+		return PGH_ERR_ARG;
+	}
+	if (!p_spa || !spa_state) {
+		SetErr(errbuf, "null p_spa or spa_state");
+		return PGH_ERR_ARG;
+	}
+	const GlmScoreSpaArgs spa = {spa_cutoff, p_spa, spa_state};
+	return GlmScoreSparseEntry(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, out, &spa, errbuf);
 }
 
 extern "C" int pgh_burden_sparse(const pgh_dataset *ds, const pgh_subset *subset, const double *phenotype,

@@ -154,9 +154,31 @@ hipError_t LaunchGlmScoreNull(uint32_t n_out, const double *y, const double *z, 
 hipError_t LaunchGlmScoreSparse(const SparseView &sv, uint32_t v_first, uint32_t nv, const double *r, const double *w,
                                 const double *z, uint32_t kp, uint32_t k, uint32_t n_y, const double *hg, double *sums,
                                 double *hgn, hipStream_t stream);
+// What the solve kernel leaves for pgh_glm_score_sparse_spa (all null: nothing, pgh_glm_score_sparse's launch).
+// t[i][kp + 3] = {H_N^-1 c (kp + 1 doubles, zero past k), U, V} for the fitted rows; p_spa[i] = rows[i].p (NaN when the
+// row is not fitted) and state[i] = 0 for every row.
+struct GlmScoreSpaOut {
+	double *t = nullptr, *p_spa = nullptr;
+	uint8_t *state = nullptr;
+};
 // The rows from the sums.  null_status: PGH_GLM_OK, or the errcode that every row not decided by its own counts gets.
 hipError_t LaunchGlmScoreSolve(uint32_t nv, const double *sums, uint32_t kp, uint32_t k, const double *hgn,
-                               int null_status, pgh_glm_row *rows, hipStream_t stream);
+                               int null_status, pgh_glm_row *rows, hipStream_t stream,
+                               const GlmScoreSpaOut &spa = GlmScoreSpaOut());
+
+// ---- pgh_glm_score_sparse_spa (glm_score_spa.hip): saddlepoint p-values of the score test's rows ----
+// Bytes of the private stash one workgroup of the workgroup form needs for `sample_ct` samples (a pair of doubles each).
+inline uint64_t GlmScoreSpaStashPerGroup(uint32_t sample_ct) {
+	return 16ull * (sample_ct ? sample_ct : 1u);
+}
+// For the rows v_first + i (i < nv) of `sv` that are fitted with |stat| > cutoff: p_spa[i] and state[i] = 1, or
+// state[i] = 2 with p_spa[i] left as it is; the other rows are not touched.  r, w, z: LaunchGlmScoreSparse's; rows, t:
+// LaunchGlmScoreSolve's.  stash: n_groups x GlmScoreSpaStashPerGroup bytes, whatever they hold.  Nothing in the
+// output depends on n_groups (>= 1).
+hipError_t LaunchGlmScoreSpa(const SparseView &sv, uint32_t v_first, uint32_t nv, const double *r, const double *w,
+                             const double *z, uint32_t kp, const pgh_glm_row *rows, const double *t,
+                             double cutoff, uint32_t n_groups, void *stash, double *p_spa, uint8_t *state,
+                             hipStream_t stream);
 
 // ---- pgh_burden_sparse (burden_sparse.hip): the linear fit's sums of a weighted burden per variant set ----
 // What the kernel leaves per set beside its sums row.

@@ -1,0 +1,293 @@
+// glm_score_spa.hip -- pgh_glm_score_sparse_spa: the saddlepoint p-value of the logistic score test of a sparse row,
+// from the row's entries (the launch wrapper is in glm.hpp, the contract in include/pgenhip.h).
+//
+// GlmScoreSolveKernel (glm_score_sparse.hip) has left per variant its row, [t = H_N^-1 c, U, V], and p_spa = p with
+// state 0.  A team (a wave, or the workgroup for rows of more than kGlmSparseLong entries and for dense-form rows, the
+// split of the entry kernel) takes a row that is fitted with |stat| > cutoff:
+//   phase A  one walk of the row's entries.  A used called entry (the set E) gathers r, w and its z row and becomes
+//            the pair (g, mu): g = d - Zt t, mu = r > 0 ? 1 - r : -r.  The pairs go to the team's stash in entry order
+//            (TeamRank), V_E = sum_E w g^2 is a lane chain and TeamSums.
+//   phase B  u+ and u- (the roots are s = +u+ and s = -u-, both u > 0) by the safeguarded Newton iteration of the
+//            contract.  One evaluation is one pass of the team over the stash, both tails in the same pass: an exp per
+//            pair and tail, four fma chains per lane, TeamSums.  Every thread then holds the same four sums and takes
+//            the same step, so the control flow is team-uniform.  A last pass gives K and K'' at the two roots.
+// The stash of a wave is 1,024 pairs of LDS; a workgroup's is sample_ct pairs of global scratch of its own, and the
+// workgroup form runs as a bounded grid of workgroups that stride over the rows.  No atomics; nothing depends on which
+// workgroup takes a row, on the grid, on the chunk or on where the range starts.
+#include "glm.hpp"
+#include "glm_team.hpp"
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+namespace pgh {
+
+namespace {
+
+constexpr int kBlock = kTeamBlock;
+constexpr int kSpaMaxEval = 64;        // evaluations of K', K'' per row (both tails in one)
+constexpr double kSpaStop = 1e-12;     // |delta s| sqrt(V) at which a root is taken
+constexpr double kSpaUlps = 0x1p-50;   // ... or |delta s| / |s|
+constexpr uint32_t kSpaWaveStash = kGlmSparseLong; // pairs per wave
+
+// pi = mu e^x / (1 - mu + mu e^x) and 1 - pi from one exp of a non-positive argument.
+__device__ __forceinline__ void SpaPi(double x, double mu, double *pi, double *qi) {
+	const double a = exp(-fabs(x)), nu = 1.0 - mu;
+	const double np = x > 0.0 ? mu : mu * a, nq = x > 0.0 ? nu * a : nu;
+	const double inv = 1.0 / (np + nq);
+	*pi = np * inv;
+	*qi = nq * inv;
+}
+
+// ln(1 - mu + mu e^x) - mu x
+__device__ __forceinline__ double SpaK(double x, double mu) {
+	const double m = x > 0.0 ? 1.0 - mu : mu;
+	return (x > 0.0 ? x : 0.0) + log1p(m * expm1(-fabs(x))) - mu * x;
+}
+
+// One tail's iteration for the root u > 0 of F(u) = |U|, F increasing, F(0) = 0.
+struct SpaRoot {
+	double u, lo, hi, grow;
+	bool done;
+};
+
+// F and F' at r->u are known: the bracket, then the next u.  Returns false when a value is not finite.
+__device__ __forceinline__ bool SpaStep(SpaRoot *r, double f, double fp, double q, double tol) {
+	if (r->done) {
+		return true;
+	}
+	if (!(fabs(f) < INFINITY) || !(fabs(fp) < INFINITY)) {
+		return false;
+	}
+	if (f < q) {
+		r->lo = r->u;
+	} else {
+		r->hi = r->u;
+	}
+	double un = r->u + (q - f) / fp;
+	if (r->hi == INFINITY) {
+		if (!(un <= r->u + r->grow)) { // (a NaN step too)
+			un = r->u + r->grow;
+			r->grow *= 2.0;
+		}
+	} else if (!(un >= r->lo && un <= r->hi)) {
+		un = 0.5 * (r->lo + r->hi);
+	}
+	// (far out, where a step of kSpaStop / sqrt(V) is below the spacing of s, a step of a few ulps is as good)
+	r->done = fabs(un - r->u) <= fmax(tol, kSpaUlps * r->u) || r->hi - r->lo <= tol;
+	r->u = un;
+	return true;
+}
+
+// Phi-bar(|omega + ln(nu / omega) / omega|) of one tail; NaN when the formula cannot be evaluated.
+__device__ __forceinline__ double SpaTail(double u, double q, double kk, double k2) {
+	const double rad = 2.0 * (u * q - kk);
+	if (!(rad > 0.0) || !(k2 > 0.0)) {
+		return NAN;
+	}
+	const double om = sqrt(rad), ratio = u * sqrt(k2) / om;
+	if (!(ratio > 0.0) || !(ratio < INFINITY)) {
+		return NAN;
+	}
+	return 0.5 * erfc(fabs(om + log(ratio) / om) * 0.70710678118654752440);
+}
+
+// One row by one team.  st: the team's stash of at least `cap` pairs (LDS or global).
+template <int KP, int TEAM, class Stash>
+__device__ __forceinline__ void SpaRow(const SparseRows &rows, uint32_t i, const double *__restrict__ rr,
+                                       const double *__restrict__ ww, const double *__restrict__ z,
+                                       const pgh_glm_row *__restrict__ out, const double *__restrict__ tv,
+                                       double cutoff, Stash st, uint32_t cap,
+                                       double *__restrict__ p_spa, uint8_t *__restrict__ state) {
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const int tid = TEAM == kTeamBlock ? static_cast<int>(threadIdx.x) : lane;
+	const uint32_t r = rows.v_first + i;
+	const int32_t ro = rows.row_of[r];
+	const bool dense = ro >= 0;
+	uint64_t e0 = 0, e1 = rows.sample_ct;
+	if (dense) {
+		if (TEAM != kTeamBlock) {
+			return;
+		}
+	} else {
+		e0 = rows.off[r];
+		e1 = rows.off[r + 1];
+		if ((e1 - e0 > kGlmSparseLong) != (TEAM == kTeamBlock)) {
+			return;
+		}
+	}
+	if (out[i].errcode != PGH_GLM_OK || !(fabs(out[i].stat) > cutoff)) {
+		return;
+	}
+	const uint8_t *prow = dense ? rows.pool + static_cast<uint64_t>(ro) * rows.pitch : nullptr;
+	const bool base3 = ro == -4;
+	const int bx = (dense || base3) ? 0 : -1 - ro;
+	double t[KP + 1];
+#pragma unroll
+	for (int j = 0; j <= KP; j++) {
+		t[j] = tv[static_cast<uint64_t>(i) * (KP + 3) + j];
+		// the row is the same for the whole workgroup, which would make t, and below U, V and the state of the
+		// iteration, scalar registers, more than there are: keep them in vector registers
+		asm volatile("" : "+v"(t[j]));
+	}
+	double q = fabs(tv[static_cast<uint64_t>(i) * (KP + 3) + KP + 1]), v = tv[static_cast<uint64_t>(i) * (KP + 3) + KP + 2];
+	asm volatile("" : "+v"(q), "+v"(v));
+
+	// phase A
+	uint32_t count = 0;
+	double sums[4] = {0.0, 0.0, 0.0, 0.0};
+	long long none[4] = {0, 0, 0, 0};
+	for (uint64_t p0 = e0; p0 < e1; p0 += TEAM) {
+		const uint64_t p = p0 + tid;
+		bool take = false;
+		double g = 0.0, mu = 0.0;
+		if (p < e1) {
+			uint32_t code, s;
+			bool entry;
+			if (dense) {
+				s = static_cast<uint32_t>(p);
+				code = (prow[s >> 2] >> (2 * (s & 3u))) & 3u;
+				entry = code != 0u;
+			} else {
+				const uint32_t x = rows.entries[p];
+				s = x >> 2;
+				code = x & 3u;
+				entry = s < rows.sample_ct;
+			}
+			if (entry && code != 3u) {
+				const double ri = rr[s];
+				if (ri == ri) {
+					take = true;
+					g = static_cast<double>(static_cast<int>(code) - bx) - t[0];
+#pragma unroll
+					for (int j = 0; j < KP; j++) {
+						g = fma(-z[static_cast<uint64_t>(s) * KP + j], t[1 + j], g);
+					}
+					mu = ri > 0.0 ? 1.0 - ri : -ri;
+					sums[0] = fma(ww[s] * g, g, sums[0]);
+				}
+			}
+		}
+		uint32_t total;
+		const uint32_t at = count + TeamRank<TEAM>(take, lane, wave, &total);
+		if (take && at < cap) {
+			st[at] = make_double2(g, mu);
+		}
+		count += total;
+		TeamSync<TEAM>(); // TeamRank's counts are rewritten by the next step
+	}
+	TeamSums<TEAM>(sums, none, lane, wave);
+	TeamSync<TEAM>(); // the pairs before their readers, and TeamSums' LDS before it is written again
+	bool ok = count <= cap;
+	const double v_rest = base3 ? 0.0 : fmax(v - sums[0], 0.0);
+
+	// phase B
+	const double tol = kSpaStop / sqrt(v);
+	SpaRoot ra = {q / v, 0.0, INFINITY, 1.0 / sqrt(v), false}, rb = ra;
+	asm volatile("" : "+v"(ra.lo), "+v"(ra.hi), "+v"(rb.lo), "+v"(rb.hi));
+	for (int ev = 0; ok && ev < kSpaMaxEval && !(ra.done && rb.done); ev++) {
+		sums[0] = sums[1] = sums[2] = sums[3] = 0.0;
+		for (uint32_t j = tid; j < count; j += TEAM) {
+			const double2 e = st[j];
+			const double gg = e.x * e.x;
+			double pi, qi;
+			SpaPi(e.x * ra.u, e.y, &pi, &qi);
+			sums[0] = fma(e.x, pi - e.y, sums[0]);
+			sums[1] = fma(gg, pi * qi, sums[1]);
+			SpaPi(-e.x * rb.u, e.y, &pi, &qi);
+			sums[2] = fma(e.x, pi - e.y, sums[2]);
+			sums[3] = fma(gg, pi * qi, sums[3]);
+		}
+		TeamSums<TEAM>(sums, none, lane, wave);
+		TeamSync<TEAM>();
+		ok = SpaStep(&ra, fma(v_rest, ra.u, sums[0]), sums[1] + v_rest, q, tol) &&
+		     SpaStep(&rb, fma(v_rest, rb.u, -sums[2]), sums[3] + v_rest, q, tol);
+	}
+	ok = ok && ra.done && rb.done;
+	double p = NAN;
+	if (ok) { // (the whole team agrees)
+		// K and K'' at the two roots, a tail at a time (one copy of the code; this pass runs once per row)
+		p = 0.0;
+#pragma nounroll
+		for (int h = 0; h < 2; h++) {
+			const double u = h ? rb.u : ra.u, su = h ? -u : u;
+			sums[0] = sums[1] = sums[2] = sums[3] = 0.0;
+			for (uint32_t j = tid; j < count; j += TEAM) {
+				const double2 e = st[j];
+				double pi, qi;
+				SpaPi(e.x * su, e.y, &pi, &qi);
+				sums[0] += SpaK(e.x * su, e.y);
+				sums[1] = fma(e.x * e.x, pi * qi, sums[1]);
+			}
+			TeamSums<TEAM>(sums, none, lane, wave);
+			TeamSync<TEAM>();
+			p += SpaTail(u, q, fma(0.5 * v_rest * u, u, sums[0]), sums[1] + v_rest);
+		}
+		ok = fabs(p) < INFINITY;
+	}
+	if (tid == 0) {
+		if (ok) {
+			p_spa[i] = p;
+		}
+		state[i] = ok ? 1 : 2;
+	}
+}
+
+template <int KP, int TEAM>
+__global__ void __launch_bounds__(kBlock) GlmScoreSpaKernel(const int32_t *__restrict__ row_of,
+                                                            const uint64_t *__restrict__ off,
+                                                            const uint32_t *__restrict__ entries,
+                                                            const uint8_t *__restrict__ pool, uint64_t pitch,
+                                                            uint32_t sample_ct, uint32_t v_first, uint32_t nv,
+                                                            const double *__restrict__ rr,
+                                                            const double *__restrict__ ww,
+                                                            const double *__restrict__ z,
+                                                            const pgh_glm_row *__restrict__ out,
+                                                            const double *__restrict__ tv, double cutoff,
+                                                            double2 *__restrict__ stash, double *__restrict__ p_spa,
+                                                            uint8_t *__restrict__ state) {
+	const SparseRows rows = {row_of, off, entries, pool, pitch, sample_ct, v_first, nv};
+	if constexpr (TEAM == kTeamBlock) {
+		// a bounded grid: workgroup b takes the rows b, b + gridDim.x, ... with its own sample_ct pairs of `stash`
+		double2 *st = stash + static_cast<uint64_t>(blockIdx.x) * sample_ct;
+		// (only thread 0's stores use them: held in vector registers, the loop's scalar registers all fit)
+		asm volatile("" : "+v"(p_spa), "+v"(state));
+		for (uint32_t i = blockIdx.x; i < nv; i += gridDim.x) {
+			SpaRow<KP, TEAM>(rows, i, rr, ww, z, out, tv, cutoff, st, sample_ct, p_spa, state);
+			__syncthreads(); // the next row rewrites the stash
+		}
+	} else {
+		__shared__ double2 lds[kTeamWaves * kSpaWaveStash];
+		const uint32_t i = blockIdx.x * kTeamWaves + (threadIdx.x >> 6);
+		if (i < nv) {
+			SpaRow<KP, TEAM>(rows, i, rr, ww, z, out, tv, cutoff, lds + (threadIdx.x >> 6) * kSpaWaveStash,
+			                 kSpaWaveStash, p_spa, state);
+		}
+	}
+}
+
+} // namespace
+
+hipError_t LaunchGlmScoreSpa(const SparseView &sv, uint32_t v_first, uint32_t nv, const double *r, const double *w,
+                             const double *z, uint32_t kp, const pgh_glm_row *rows, const double *t,
+                             double cutoff, uint32_t n_groups, void *stash, double *p_spa, uint8_t *state,
+                             hipStream_t stream) {
+	if (nv == 0) {
+		return hipSuccess;
+	}
+	if (n_groups == 0) {
+		return hipErrorInvalidValue;
+	}
+	return GlmForWidth(kp, [&](auto width) {
+		constexpr int KP = decltype(width)::value;
+		GlmScoreSpaKernel<KP, 64><<<(nv + kTeamWaves - 1) / kTeamWaves, kBlock, 0, stream>>>(
+		    sv.row_of, sv.off, sv.entries, sv.pool, sv.pitch, sv.sample_ct, v_first, nv, r, w, z, rows, t, cutoff,
+		    nullptr, p_spa, state);
+		GlmScoreSpaKernel<KP, kBlock><<<n_groups < nv ? n_groups : nv, kBlock, 0, stream>>>(
+		    sv.row_of, sv.off, sv.entries, sv.pool, sv.pitch, sv.sample_ct, v_first, nv, r, w, z, rows, t, cutoff,
+		    static_cast<double2 *>(stash), p_spa, state);
+	});
+}
+
+} // namespace pgh

@@ -218,11 +218,18 @@ __global__ void __launch_bounds__(kBlock) GlmScoreSparseKernel(const int32_t *__
 // the row of a variant: one thread per variant
 // ---------------------------------------------------------------------------
 
+// spa.t != null (pgh_glm_score_sparse_spa): a fitted row also leaves t = H_N^-1 c (kp + 1 doubles, zero past k), U and
+// V (kp + 3 doubles in all), and every row p_spa = its p (NaN when it is not fitted) and state 0, for GlmScoreSpaKernel to replace.
 __global__ void GlmScoreSolveKernel(uint32_t nv, const double *__restrict__ sums, uint32_t kp, uint32_t k,
-                                    const double *__restrict__ hgn, int null_status, pgh_glm_row *__restrict__ rows) {
+                                    const double *__restrict__ hgn, int null_status, pgh_glm_row *__restrict__ rows,
+                                    GlmScoreSpaOut spa) {
 	const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
 	if (v >= nv) {
 		return;
+	}
+	if (spa.t) {
+		spa.p_spa[v] = NAN;
+		spa.state[v] = 0;
 	}
 	const int q1 = static_cast<int>(k) + 1, nh = q1 * (q1 + 1) / 2;
 	const double *s = sums + static_cast<uint64_t>(v) * (kp + 6);
@@ -284,6 +291,23 @@ __global__ void GlmScoreSolveKernel(uint32_t nv, const double *__restrict__ sums
 	r.stat = u / lxx;
 	r.p = GlmPFromZ(r.stat);
 	rows[v] = r;
+	if (spa.t) {
+		// t = L^-T (L^-1 c): one back substitution with the factor
+		double *t = spa.t + static_cast<uint64_t>(v) * (kp + 3);
+		for (int j = static_cast<int>(kp); j >= q1; j--) {
+			t[j] = 0.0;
+		}
+		for (int j = q1 - 1; j >= 0; j--) {
+			double x = a[xi * kMaxQ + j];
+			for (int m = j + 1; m < q1; m++) {
+				x -= a[m * kMaxQ + j] * t[m];
+			}
+			t[j] = x / a[j * kMaxQ + j];
+		}
+		t[kp + 1] = u;
+		t[kp + 2] = lxx * lxx;
+		spa.p_spa[v] = r.p;
+	}
 }
 
 uint32_t Blocks(uint32_t n, uint32_t per) {
@@ -326,11 +350,11 @@ hipError_t LaunchGlmScoreSparse(const SparseView &sv, uint32_t v_first, uint32_t
 }
 
 hipError_t LaunchGlmScoreSolve(uint32_t nv, const double *sums, uint32_t kp, uint32_t k, const double *hgn,
-                               int null_status, pgh_glm_row *rows, hipStream_t stream) {
+                               int null_status, pgh_glm_row *rows, hipStream_t stream, const GlmScoreSpaOut &spa) {
 	if (nv == 0) {
 		return hipSuccess;
 	}
-	GlmScoreSolveKernel<<<Blocks(nv, 64), 64, 0, stream>>>(nv, sums, kp, k, hgn, null_status, rows);
+	GlmScoreSolveKernel<<<Blocks(nv, 64), 64, 0, stream>>>(nv, sums, kp, k, hgn, null_status, rows, spa);
 	return hipGetLastError();
 }
 

@@ -77,7 +77,9 @@ __device__ __forceinline__ uint32_t TeamRank(bool take, int lane, int wave, uint
 }
 
 // Team totals of N doubles and four integer counts, on every thread: a butterfly per wave, then (TEAM == 256) the
-// waves' partials added in the order 0..3 from LDS.  One barrier; the LDS it uses is not written again.
+// waves' partials added in the order 0..3 from LDS.  One barrier, between the partials' writes and their reads: a
+// caller that calls it again (GlmScoreSpaKernel does, once per evaluation) puts a TeamSync between the calls, or the
+// next call's writes race this call's reads.
 template <int TEAM, int N>
 __device__ __forceinline__ void TeamSums(double (&v)[N], long long (&c)[4], int lane, int wave) {
 #pragma unroll

@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = [
     "pgh_reader_unpack_start", "pgh_reader_unpack_wait", "pgh_get_2bit", "pgh_get_counts", "pgh_get_missingness", "pgh_get_int8", "pgh_get_dosage_f64", "pgh_get_phased",
     "pgh_tally_start", "pgh_tally_request", "pgh_tally_wait", "pgh_tally_counts", "pgh_tally_hwe_lnp",
     "pgh_tally_sample_missing", "pgh_tally_destroy", "pgh_tally_passes_started", "pgh_host_alloc", "pgh_host_free", "pgh_trim_device_cache",
-    "pgh_reader_error", "pgh_open_sparse", "pgh_get_sparse_info", "pgh_sparse_opens_started", "pgh_glm", "pgh_glm_multi", "pgh_glm_sparse", "pgh_glm_score_sparse", "pgh_burden_sparse", "pgh_score_sparse", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
+    "pgh_reader_error", "pgh_open_sparse", "pgh_get_sparse_info", "pgh_sparse_opens_started", "pgh_glm", "pgh_glm_multi", "pgh_glm_sparse", "pgh_glm_score_sparse", "pgh_glm_score_sparse_spa", "pgh_burden_sparse", "pgh_score_sparse", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
     "pgh_king_counts", "pgh_king_table", "pgh_king_kinship",
     "pgh_ld_window_sums", "pgh_ld_prune", "pgh_ld_exceeds", "pgh_ld_scores", "pgh_ld_r2",
     "pgh_grm", "pgh_grm_standardize",
@@ -232,6 +232,7 @@ def _load():
         "pgh_glm_multi": (C.c_int, [vp, vp, u32, u32, u32, vp, u32, vp, C.c_int, C.c_int, vp, cp]),
         "pgh_glm_sparse": (C.c_int, [vp, vp, u32, u32, vp, u32, vp, vp, cp]),
         "pgh_glm_score_sparse": (C.c_int, [vp, vp, u32, u32, vp, u32, vp, vp, cp]),
+        "pgh_glm_score_sparse_spa": (C.c_int, [vp, vp, u32, u32, vp, u32, vp, C.c_double, vp, vp, vp, cp]),
         "pgh_burden_sparse": (C.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, cp]),
         "pgh_score_sparse": (C.c_int, [vp, vp, u32, vp, vp, vp, u32, C.c_int, vp, vp, vp, cp]),
         "pgh_glm_p_from_t": (C.c_double, [C.c_double, C.c_double]),
@@ -929,11 +930,8 @@ class Dataset:
             "firth": rows["firth"].astype(bool),
         }
 
-    def glm_score_sparse(self, phenotype, covariates=None, v_begin: int | None = None, v_end: int | None = None,
-                         subset: Subset | None = None) -> dict:
-        """pgh_glm_score_sparse: the logistic score test of every variant of a sparse-resident dataset
-        (Dataset.open(..., sparse=True)), from each variant's entries.  phenotype: 0.0 / 1.0 per output sample, NaN =
-        missing (apply glm_model() first for 1/2 coding).  Returns glm()'s dict (firth is False everywhere)."""
+    def _score_sparse_args(self, phenotype, covariates, v_begin, v_end, subset):
+        """(v0, v1, y, z) of the score-test calls, after their shape checks."""
         v0 = self.v_begin if v_begin is None else v_begin
         v1 = self.v_end if v_end is None else v_end
         n_out = subset.size if subset else self.n_samples
@@ -946,16 +944,45 @@ class Dataset:
             z = np.ascontiguousarray(np.atleast_2d(np.asarray(covariates, dtype=np.float64)))
             if z.shape[1] != n_out:
                 raise ValueError(f"covariates must be n_covar x {n_out}, got shape {z.shape}")
-        rows = np.zeros(max(0, v1 - v0), dtype=GLM_ROW_DTYPE)
-        eb = _errbuf()
-        _check(_lib.pgh_glm_score_sparse(self._h, subset._h if subset else None, v0, v1, _ptr(y), z.shape[0],
-                                         _ptr(z) if z.size else None, _ptr(rows), eb), eb)
+        return v0, v1, y, z
+
+    @staticmethod
+    def _glm_rows_dict(rows) -> dict:
         return {
             "beta": rows["beta"].copy(), "se": rows["se"].copy(), "stat": rows["stat"].copy(), "p": rows["p"].copy(),
             "a1_freq": rows["a1_freq"].copy(), "obs_ct": rows["obs_ct"].astype(np.int64),
             "errcode": np.array([GLM_ERRCODES[c] for c in rows["errcode"]], dtype=object),
             "firth": rows["firth"].astype(bool),
         }
+
+    def glm_score_sparse(self, phenotype, covariates=None, v_begin: int | None = None, v_end: int | None = None,
+                         subset: Subset | None = None) -> dict:
+        """pgh_glm_score_sparse: the logistic score test of every variant of a sparse-resident dataset
+        (Dataset.open(..., sparse=True)), from each variant's entries.  phenotype: 0.0 / 1.0 per output sample, NaN =
+        missing (apply glm_model() first for 1/2 coding).  Returns glm()'s dict (firth is False everywhere)."""
+        v0, v1, y, z = Dataset._score_sparse_args(self, phenotype, covariates, v_begin, v_end, subset)
+        rows = np.zeros(max(0, v1 - v0), dtype=GLM_ROW_DTYPE)
+        eb = _errbuf()
+        _check(_lib.pgh_glm_score_sparse(self._h, subset._h if subset else None, v0, v1, _ptr(y), z.shape[0],
+                                         _ptr(z) if z.size else None, _ptr(rows), eb), eb)
+        return Dataset._glm_rows_dict(rows)
+
+    def glm_score_sparse_spa(self, phenotype, covariates=None, cutoff: float = 2.0, v_begin: int | None = None,
+                             v_end: int | None = None, subset: Subset | None = None) -> dict:
+        """pgh_glm_score_sparse_spa: glm_score_sparse() plus a saddlepoint p-value for the rows with |stat| > cutoff
+        (cutoff >= 0.1; inf = never).  Returns glm_score_sparse()'s dict (p stays the normal p-value) and p_spa
+        (float64: NaN for a row that is not fitted, p where the saddlepoint was not applied or failed) and spa_state
+        (uint8: 0 = not applied, 1 = applied, 2 = attempted and failed)."""
+        v0, v1, y, z = Dataset._score_sparse_args(self, phenotype, covariates, v_begin, v_end, subset)
+        nv = max(0, v1 - v0)
+        rows = np.zeros(nv, dtype=GLM_ROW_DTYPE)
+        p_spa = np.zeros(nv, dtype=np.float64)
+        state = np.zeros(nv, dtype=np.uint8)
+        eb = _errbuf()
+        _check(_lib.pgh_glm_score_sparse_spa(self._h, subset._h if subset else None, v0, v1, _ptr(y), z.shape[0],
+                                             _ptr(z) if z.size else None, float(cutoff), _ptr(rows), _ptr(p_spa),
+                                             _ptr(state), eb), eb)
+        return dict(Dataset._glm_rows_dict(rows), p_spa=p_spa, spa_state=state)
 
     def burden_sparse(self, phenotype, set_off, set_vidx, weights=None, covariates=None,
                       subset: Subset | None = None) -> np.ndarray:
