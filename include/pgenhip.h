@@ -194,7 +194,20 @@ const pgh_dataset *pgh_shard(const pgh_dataset *ds, uint32_t k);
 /* ---- sample subsets ------------------------------------------------------ */
 
 /* Replaces BuildSampleSubset / PgrSetSampleSubsetIndex (src/plink_common.cpp:1222-1250,
- * src/plink_freq.cpp:393-397).  sample_include: ceil(N/64) words, bit s = sample s kept. */
+ * src/plink_freq.cpp:393-397).  sample_include: ceil(N/64) words, bit s = sample s kept.  Bits at and above N are
+ * ignored (the subset clears them in its own copy): all-ones words mean every sample.
+ *
+ * The empty subset (no bit below N set, pgh_subset_size() == 0) is accepted, and every entry point that takes it
+ * answers one of three ways, never with PGH_ERR_DEVICE:
+ *   - per-variant integer products are zeros: pgh_counts_range(_dev), the tally pass (its HWE ln p is that of zero
+ *     counts), pgh_dosage_sums(_dev), pgh_ld_pairs(_dev), the reader's pgh_get_counts;
+ *   - per-sample products are zero-length, PGH_OK with nothing written: pgh_unpack_range, pgh_unpack_samples,
+ *     pgh_dosage_unpack(_samples), the reader's per-sample calls, pgh_sample_counts, pgh_missing_per_sample,
+ *     pgh_tally_sample_missing, pgh_score, pgh_score_counts, pgh_score_sparse.  A score plan made for it scores
+ *     nothing: pgh_score_run_dev zeroes its (raw-sample) outputs;
+ *   - everything that fits or compares samples returns PGH_ERR_ARG, "the sample subset is empty ...", before any
+ *     launch: pgh_glm, pgh_glm_multi, pgh_glm_sparse, pgh_glm_score_sparse(_spa), pgh_burden_sparse, pgh_pca,
+ *     pgh_pca_sharded, pgh_king_counts, pgh_king_table, pgh_grm, pgh_ld_window_sums, pgh_ld_prune, pgh_ld_scores. */
 int pgh_subset_create(const pgh_dataset *ds, const uint64_t *sample_include, pgh_subset **out, char *errbuf);
 uint32_t pgh_subset_size(const pgh_subset *ss);
 void pgh_subset_destroy(pgh_subset *ss);

@@ -699,6 +699,11 @@ static int ScorePlanCreate(const pgh_dataset *ds, const pgh_subset *subset, uint
 		}
 		local[i] = vidx[i] - ds->v_begin;
 	}
+	if (subset && subset->n_out == 0) {
+		// nobody is kept: no counts to build tables from (their means would be 0 / 0).  The plan scores nothing, so a
+		// run zeroes its outputs and pgh_score compacts them to zero-length results.
+		n_scored = 0;
+	}
 	// Variants that carry dosage tracks are scored by their own kernel (dosage.hip); they go to the back
 	// of the list so each kernel sees one contiguous run.  Per-sample sums do not depend on the order.
 	std::vector<uint32_t> order(n_scored);
@@ -1705,6 +1710,9 @@ extern "C" int pgh_pca_sharded(const pgh_dataset *ds, const pgh_subset *subset, 
 	PGH_ONE_DEVICE(ds);
 	PGH_ENTER(ds);
 	int rc = CheckSubset(ds, subset, errbuf);
+	if (rc == PGH_OK) {
+		rc = RefuseEmptySubset(subset, errbuf);
+	}
 	if (rc != PGH_OK) {
 		return rc;
 	}

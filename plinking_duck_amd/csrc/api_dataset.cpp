@@ -1533,6 +1533,9 @@ extern "C" int pgh_subset_create(const pgh_dataset *ds, const uint64_t *sample_i
 	ss->device = ds->device;
 	const uint32_t N = ds->sample_ct;
 	ss->include.assign(sample_include, sample_include + (N + 63) / 64);
+	if (N % 64) {
+		ss->include.back() &= (1ull << (N % 64)) - 1; // bits >= N are ignored: the bit walkers never see them
+	}
 	std::vector<uint8_t> mask2(ds->pitch, 0);
 	for (uint32_t s = 0; s < N; s++) {
 		if ((ss->include[s >> 6] >> (s & 63)) & 1ull) {

@@ -471,6 +471,9 @@ int GlmCheckCommon(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_b
 		return PGH_ERR_ARG;
 	}
 	rc = CheckSubset(ds, subset, errbuf);
+	if (rc == PGH_OK) {
+		rc = RefuseEmptySubset(subset, errbuf);
+	}
 	if (rc != PGH_OK) {
 		return rc;
 	}

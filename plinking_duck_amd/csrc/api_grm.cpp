@@ -60,6 +60,9 @@ extern "C" int pgh_grm(const pgh_dataset *ds, const pgh_subset *subset, uint32_t
 	PGH_DENSE_ROWS(ds);
 	PGH_ENTER(ds);
 	int rc = CheckSubset(ds, subset, errbuf);
+	if (rc == PGH_OK) {
+		rc = RefuseEmptySubset(subset, errbuf);
+	}
 	if (rc != PGH_OK) {
 		return rc;
 	}

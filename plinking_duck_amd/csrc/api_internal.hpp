@@ -419,6 +419,16 @@ struct HostSourceFence {
 	return PGH_OK;
 }
 
+// The calls that fit or compare samples refuse a subset that keeps nobody (pgenhip.h, pgh_subset_create): no launch
+// sized by n_out, no division by it.
+[[maybe_unused]] int RefuseEmptySubset(const pgh_subset *ss, char *errbuf) {
+	if (ss && ss->n_out == 0) {
+		SetErr(errbuf, "the sample subset is empty: this call needs at least one sample");
+		return PGH_ERR_ARG;
+	}
+	return PGH_OK;
+}
+
 // Shard k's slice of [v_begin, v_end) over a group: fn(shard, the subset's part for it or nullptr, lo, hi) when the
 // shard holds some of the range, PGH_OK when it holds none.
 template <class Fn>

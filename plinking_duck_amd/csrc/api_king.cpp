@@ -86,6 +86,9 @@ extern "C" int pgh_king_counts(const pgh_dataset *ds, const pgh_subset *subset, 
 	PGH_DENSE_ROWS(ds);
 	PGH_ENTER(ds);
 	int rc = CheckSubset(ds, subset, errbuf);
+	if (rc == PGH_OK) {
+		rc = RefuseEmptySubset(subset, errbuf);
+	}
 	if (rc != PGH_OK) {
 		return rc;
 	}
@@ -138,6 +141,9 @@ extern "C" int pgh_king_table(const pgh_dataset *ds, const pgh_subset *subset, u
 	PGH_DENSE_ROWS(ds);
 	PGH_ENTER(ds);
 	int rc = CheckSubset(ds, subset, errbuf);
+	if (rc == PGH_OK) {
+		rc = RefuseEmptySubset(subset, errbuf);
+	}
 	if (rc != PGH_OK) {
 		return rc;
 	}

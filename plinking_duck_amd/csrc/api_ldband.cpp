@@ -138,6 +138,9 @@ extern "C" int pgh_ld_window_sums(const pgh_dataset *ds, const pgh_subset *subse
 	PGH_DENSE_ROWS(ds);
 	PGH_ENTER(ds);
 	int rc = CheckSubset(ds, subset, errbuf);
+	if (rc == PGH_OK) {
+		rc = RefuseEmptySubset(subset, errbuf);
+	}
 	if (rc != PGH_OK) {
 		return rc;
 	}
@@ -203,6 +206,9 @@ extern "C" int pgh_ld_prune(const pgh_dataset *ds, const pgh_subset *subset, uin
 	PGH_DENSE_ROWS(ds);
 	PGH_ENTER(ds);
 	int rc = CheckSubset(ds, subset, errbuf);
+	if (rc == PGH_OK) {
+		rc = RefuseEmptySubset(subset, errbuf);
+	}
 	if (rc != PGH_OK) {
 		return rc;
 	}
@@ -349,6 +355,9 @@ extern "C" int pgh_ld_scores(const pgh_dataset *ds, const pgh_subset *subset, ui
 	PGH_DENSE_ROWS(ds);
 	PGH_ENTER(ds);
 	int rc = CheckSubset(ds, subset, errbuf);
+	if (rc == PGH_OK) {
+		rc = RefuseEmptySubset(subset, errbuf);
+	}
 	if (rc != PGH_OK) {
 		return rc;
 	}

@@ -591,6 +591,9 @@ int SubsetCreate(const pgh_dataset *g, const uint64_t *sample_include, pgh_subse
 	ss->ds = g;
 	const uint32_t N = g->sample_ct;
 	ss->include.assign(sample_include, sample_include + (N + 63) / 64);
+	if (N % 64) {
+		ss->include.back() &= (1ull << (N % 64)) - 1; // bits >= N are ignored
+	}
 	for (uint32_t s = 0; s < N; s++) {
 		if ((ss->include[s >> 6] >> (s & 63)) & 1ull) {
 			ss->sel.push_back(s);
@@ -817,7 +820,7 @@ int SampleCounts(const pgh_dataset *g, const pgh_subset *ss, uint32_t variant_be
 	} else {
 		rc = CheckRange(g, variant_begin, variant_begin + n_var, errbuf);
 	}
-	if (rc != PGH_OK) {
+	if (rc != PGH_OK || n_out == 0) { // an empty subset: nothing to write (a shard would refuse its null buffer)
 		return rc;
 	}
 	std::vector<std::vector<uint32_t>> part(g->shards.size());
@@ -1026,6 +1029,9 @@ int Pca(const pgh_dataset *g, const pgh_subset *ss, uint32_t n_var, const uint32
         const double *inv_stdev, uint32_t n_pcs, const double *g1_init, double *eigenvalues, double *eigenvectors,
         char *errbuf) {
 	int rc = CheckGroupSubset(g, ss, errbuf);
+	if (rc == PGH_OK) {
+		rc = RefuseEmptySubset(ss, errbuf);
+	}
 	if (rc != PGH_OK) {
 		return rc;
 	}

@@ -536,7 +536,7 @@ extern "C" int pgh_score_sparse(const pgh_dataset *ds, const pgh_subset *subset,
 		}
 	}
 	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct;
-	if (n_scored == 0) { // pgh_score's answer for an empty list
+	if (n_scored == 0 || n_out == 0) { // pgh_score's answer for an empty list; nothing to write for an empty subset
 		std::fill_n(score_sum, static_cast<size_t>(n_out) * n_cols, 0.0);
 		if (dosage_sum) {
 			std::fill_n(dosage_sum, n_out, 0.0);
