@@ -2,10 +2,13 @@
 // pgh_glm_multi: the same for many phenotypes in one call; pgh_glm_sparse: the linear fit over a sparse-resident
 // dataset, from its entries (glm_sparse.hip); pgh_burden_sparse: gene-set burden fits over such a dataset
 // (burden_sparse.hip); pgh_glm_score_sparse: the logistic score test over such a dataset, from its entries
-// (glm_score_sparse.hip).
+// (glm_score_sparse.hip); pgh_skat_sparse: SKAT and burden score tests of variant sets under that test's null model
+// (skat_sparse.hip, skat_math.hpp, linalg.cpp).
 #include "api_internal.hpp"
 #include "glm.hpp"
 #include "glm_math.hpp"
+#include "linalg.hpp"
+#include "skat_math.hpp"
 
 #include <unordered_map>
 
@@ -748,8 +751,8 @@ const char *const kBurdenScratchEnv = "PGH_BURDEN_SCRATCH_BYTES";
 
 // The byte budget of the workgroups' private vectors (read at every call; the result does not depend on it: it only
 // bounds how many sets are in flight, and anything below one vector still gives one workgroup).
-uint64_t BurdenScratchBytes() {
-	const char *s = std::getenv(kBurdenScratchEnv);
+uint64_t EnvBytes(const char *name, uint64_t fallback) {
+	const char *s = std::getenv(name);
 	if (s && *s) {
 		char *end = nullptr;
 		const unsigned long long v = std::strtoull(s, &end, 10);
@@ -757,7 +760,10 @@ uint64_t BurdenScratchBytes() {
 			return v;
 		}
 	}
-	return kBurdenScratchBytes;
+	return fallback;
+}
+uint64_t BurdenScratchBytes() {
+	return EnvBytes(kBurdenScratchEnv, kBurdenScratchBytes);
 }
 
 // pgh_burden_sparse on one sparse-resident dataset, after the argument checks.  n_memb = set_off[n_sets].
@@ -857,6 +863,260 @@ int BurdenSparseOne(const pgh_dataset *ds, const pgh_subset *subset, const doubl
 	return PGH_OK;
 }
 
+
+constexpr uint64_t kSkatScratchBytes = 1ull << 30;
+const char *const kSkatScratchEnv = "PGH_SKAT_SCRATCH_BYTES";
+
+// One set's row and eigenvalues from the kernel's sums (LaunchSkatSparse's layout at `sums`), in FP64.  chol: the lower
+// Cholesky factor of H (stride M); yg = L^-1 g_S.  With Y_j = L^-1 c_j, c_j' H^-1 c_l = Y_j . Y_l and t_j' g_S =
+// Y_j . yg, so Phi is symmetric as it is computed.  omega: the set's weights, null = 1.0.  lambda (m doubles) is
+// written only for a decided row; work is the caller's, reused across the sets.
+struct SkatWork {
+	std::vector<double> y, u, phi, km, lam;
+};
+void SkatFinishSet(uint32_t m, uint32_t kp, uint32_t k, const double *sums, const double *omega, const double *chol,
+                   const double *yg, int null_status, uint32_t n_y, const pgh::SkatSetCounts &cnt, SkatWork &wk,
+                   pgh_skat_row *row, double *lambda) {
+	constexpr int M = PGH_GLM_MAX_COVAR + 1;
+	const double nan = std::nan("");
+	std::memset(row, 0, sizeof *row);
+	row->q = row->p_skat = row->beta = row->se = row->stat = row->p = row->lambda_sum = row->lambda_max = nan;
+	row->obs_ct = n_y;
+	row->n_carriers = cnt.n_carriers;
+	if (n_y < k + 3) {
+		row->errcode = PGH_GLM_TOO_FEW_SAMPLES;
+		return;
+	}
+	if (cnt.n_carriers == 0 || cnt.n_nonzero == 0) {
+		row->errcode = PGH_GLM_CONST_ALLELE;
+		return;
+	}
+	if (null_status != PGH_GLM_OK) {
+		row->errcode = static_cast<uint8_t>(null_status);
+		return;
+	}
+	const uint32_t q1 = k + 1, nc = kp + 1;
+	const double *a = sums, *c = a + static_cast<uint64_t>(m) * (m + 1) / 2, *u0 = c + static_cast<uint64_t>(m) * nc;
+	wk.y.resize(static_cast<size_t>(m) * q1);
+	wk.u.resize(m);
+	wk.phi.resize(static_cast<size_t>(m) * m);
+	wk.km.resize(static_cast<size_t>(m) * m);
+	wk.lam.resize(m);
+	for (uint32_t j = 0; j < m; j++) {
+		double *yj = wk.y.data() + static_cast<size_t>(j) * q1;
+		double dot = 0.0;
+		for (uint32_t i = 0; i < q1; i++) {
+			double t = c[static_cast<uint64_t>(j) * nc + i];
+			for (uint32_t e = 0; e < i; e++) {
+				t -= chol[i * M + e] * yj[e];
+			}
+			yj[i] = t / chol[i * M + i];
+			dot += yj[i] * yg[i];
+		}
+		wk.u[j] = u0[j] - dot;
+	}
+	double q = 0.0, trace = 0.0, ub = 0.0, vb = 0.0, ab = 0.0;
+	bool finite = true;
+	for (uint32_t j = 0; j < m; j++) {
+		const double wj = omega ? omega[j] : 1.0;
+		const double *yj = wk.y.data() + static_cast<size_t>(j) * q1;
+		q += wj * wj * wk.u[j] * wk.u[j];
+		ub += wj * wk.u[j];
+		for (uint32_t l = j; l < m; l++) {
+			const double wl = omega ? omega[l] : 1.0;
+			const double *yl = wk.y.data() + static_cast<size_t>(l) * q1;
+			const double ajl = a[static_cast<uint64_t>(j) * m - static_cast<uint64_t>(j) * (j + 1) / 2 + l];
+			double dot = 0.0;
+			for (uint32_t i = 0; i < q1; i++) {
+				dot += yj[i] * yl[i];
+			}
+			const double phi = ajl - dot, kjl = wj * wl * phi;
+			wk.phi[static_cast<size_t>(j) * m + l] = wk.phi[static_cast<size_t>(l) * m + j] = phi;
+			wk.km[static_cast<size_t>(j) * m + l] = wk.km[static_cast<size_t>(l) * m + j] = kjl;
+			finite = finite && std::isfinite(kjl);
+			const double twice = l == j ? 1.0 : 2.0;
+			vb += twice * kjl;
+			ab += twice * wj * wl * ajl;
+			trace += l == j ? kjl : 0.0;
+		}
+	}
+	if (finite) {
+		pgh::SymmetricEigenvalues(wk.km.data(), m, wk.lam.data());
+	}
+	if (!finite || !std::isfinite(wk.lam[0]) || !(wk.lam[0] > 0.0)) {
+		row->errcode = PGH_GLM_ZERO_VARIANCE;
+		return;
+	}
+	row->errcode = PGH_GLM_OK;
+	uint32_t used = 0;
+	while (used < m && wk.lam[used] > 1e-10 * wk.lam[0]) { // (descending: the used eigenvalues come first)
+		used++;
+	}
+	row->q = q;
+	row->lambda_sum = trace;
+	row->lambda_max = wk.lam[0];
+	row->n_lambda = used;
+	row->p_skat = pgh::SkatPFromLambda(q, wk.lam.data(), used, &row->p_state);
+	if (vb > 1e-10 * ab) {
+		row->beta = ub / vb;
+		row->se = 1.0 / std::sqrt(vb);
+		row->stat = ub / std::sqrt(vb);
+		row->p = pgh::GlmPFromZ(row->stat);
+	}
+	std::copy_n(wk.lam.data(), m, lambda);
+}
+
+// pgh_skat_sparse on one sparse-resident dataset, after the argument checks.  The staging and the null fit are
+// GlmScoreSparseOne's; the sets are taken in chunks of consecutive sets whose sums fit the scratch budget, every chunk
+// one launch of LaunchSkatSparse and a host pass over its sets.  out and lambda_out are written only when every chunk
+// has been served.
+int SkatSparseOne(const pgh_dataset *ds, const pgh_subset *subset, const double *phenotype, uint32_t k,
+                  const double *covariates, uint32_t n_sets, const uint64_t *set_off, const uint32_t *set_vidx,
+                  const double *weight, pgh_skat_row *out, double *lambda_out, char *errbuf) {
+	PGH_ENTER(ds);
+	constexpr int M = PGH_GLM_MAX_COVAR + 1;
+	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct, n_raw = ds->sample_ct;
+	const uint32_t kp = pgh::GlmPadCovar(k);
+	const uint64_t n_memb = set_off[n_sets];
+	hipStream_t st = PghThreadStream();
+	const GlmStaged sg = GlmStage(ds, subset, phenotype, k, covariates, GlmCentre::kZ, true);
+	const uint32_t n_y = sg.n_y;
+
+	// the grid and the chunks: the workgroups' private vectors take at most half of the byte budget (one vector at
+	// least, eight workgroups per compute unit at most), a chunk's sums the rest (one set at least)
+	int device = 0, cus = 0;
+	PGH_HIP(hipGetDevice(&device), "skat_sparse device");
+	PGH_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device), "skat_sparse device attribute");
+	const uint64_t budget = EnvBytes(kSkatScratchEnv, kSkatScratchBytes);
+	const uint64_t per_group = pgh::BurdenScratchPerGroup(n_raw);
+	const uint32_t n_groups = static_cast<uint32_t>(std::min<uint64_t>(
+	    std::min<uint64_t>(n_sets, 8ull * static_cast<uint32_t>(std::max(cus, 1))),
+	    std::max<uint64_t>(1, budget / 2 / per_group)));
+	const uint64_t vec_bytes = per_group * n_groups;
+	uint64_t largest = 0;
+	for (uint32_t s = 0; s < n_sets; s++) {
+		largest = std::max(largest, pgh::SkatSetDoubles(set_off[s + 1] - set_off[s], kp));
+	}
+	const uint64_t chunk_doubles = std::max<uint64_t>(std::max<uint64_t>(largest, 1), (budget > vec_bytes ? budget - vec_bytes : 0) / 8);
+	// out_off[s]: where set s starts in its chunk's sums; chunk_first: the first set of every chunk, then n_sets
+	std::vector<uint64_t> out_off(n_sets);
+	std::vector<uint32_t> chunk_first;
+	uint64_t fill = 0, region = 0;
+	for (uint32_t s = 0; s < n_sets; s++) {
+		const uint64_t need = pgh::SkatSetDoubles(set_off[s + 1] - set_off[s], kp);
+		if (s == 0 || fill + need > chunk_doubles) {
+			chunk_first.push_back(s);
+			fill = 0;
+		}
+		out_off[s] = fill;
+		fill += need;
+		region = std::max(region, fill);
+	}
+	chunk_first.push_back(n_sets);
+	DevBuf vectors, sums;
+	PGH_HIP(vectors.Alloc(vec_bytes), "skat_sparse vectors");
+	PGH_HIP(sums.Alloc(8 * region), "skat_sparse sums");
+
+	const uint32_t ne = (k + 1) * (k + 2) / 2 + k + 1;
+	const uint64_t n = n_out, nr = n_raw, nsets = n_sets, ctr_bytes = 256;
+	double *d_y, *d_z, *d_zr, *d_r, *d_w, *d_part, *d_hg;
+	uint64_t *d_off, *d_out_off;
+	uint32_t *d_vidx, *d_ctr;
+	pgh::SkatSetCounts *d_counts;
+	ScratchLayout lay;
+	lay.Add(&d_y, n);
+	lay.Add(&d_z, n * kp + 1); // one element of slack, here and in d_zr, d_vidx
+	lay.Add(&d_zr, nr * kp + 1, subset != nullptr);
+	lay.Add(&d_r, nr);
+	lay.Add(&d_w, nr);
+	lay.Add(&d_part, static_cast<uint64_t>(pgh::kGlmScoreNullParts) * ne);
+	lay.Add(&d_hg, ne);
+	lay.Add(&d_off, nsets + 1);
+	lay.Add(&d_out_off, nsets);
+	lay.Add(&d_vidx, n_memb + 1);
+	lay.Add(&d_ctr, ctr_bytes / 4);
+	lay.Add(&d_counts, nsets);
+	void *scratch = nullptr;
+	PGH_HIP(PghThreadScratch(lay.total, st, &scratch), "skat_sparse scratch");
+	lay.Bind(scratch);
+	if (!subset) {
+		d_zr = d_z;
+	}
+
+	std::vector<pgh_skat_row> rows(n_sets);
+	std::vector<double> lam(std::max<uint64_t>(n_memb, 1), std::nan("")), hsums(std::max<uint64_t>(region, 1)), hg(ne);
+	std::vector<pgh::SkatSetCounts> counts(n_sets);
+	HostSourceFence fence(st); // sg's vectors, out_off and the caller's set arrays feed asynchronous uploads
+	int rc = GlmUpload(sg, d_y, d_z, d_r, d_zr, st, "skat_sparse", "phenotype", errbuf);
+	if (rc != PGH_OK) {
+		return rc;
+	}
+	if (subset) {
+		PGH_HIP(hipMemsetAsync(d_w, 0, 8ull * nr, st), "skat_sparse weight clear");
+	}
+	PGH_HIP(hipMemcpyAsync(d_off, set_off, 8ull * (n_sets + 1ull), hipMemcpyHostToDevice, st), "skat_sparse set upload");
+	PGH_HIP(hipMemcpyAsync(d_out_off, out_off.data(), 8ull * n_sets, hipMemcpyHostToDevice, st), "skat_sparse offset upload");
+	if (n_memb) {
+		PGH_HIP(hipMemcpyAsync(d_vidx, set_vidx, 4ull * n_memb, hipMemcpyHostToDevice, st), "skat_sparse member upload");
+	}
+	// zeroed at every call: nothing is assumed of what an earlier call, or another user of the block, left there
+	PGH_HIP(hipMemsetAsync(vectors.p, 0, vec_bytes, st), "skat_sparse vectors clear");
+	int null_status = PGH_GLM_OK;
+	rc = GlmScoreNullFit(n_out, d_y, d_z, kp, k, subset ? subset->d_sel : nullptr, n_y >= k + 3, d_r, d_w, d_part, d_hg, st,
+	                     &null_status, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
+	}
+	// the Cholesky factor of the final H and L^-1 g_S
+	double chol[M * M] = {}, yg[M] = {};
+	const bool fitted = n_y >= k + 3 && null_status == PGH_GLM_OK;
+	if (fitted) {
+		PGH_HIP(hipMemcpyAsync(hg.data(), d_hg, 8ull * ne, hipMemcpyDeviceToHost, st), "skat_sparse null copy");
+		PGH_HIP(hipStreamSynchronize(st), "skat_sparse null sync");
+		const uint32_t q1 = k + 1, nh = q1 * (q1 + 1) / 2;
+		for (uint32_t ia = 0, e = 0; ia < q1; ia++) {
+			for (uint32_t ib = ia; ib < q1; ib++, e++) {
+				chol[ib * M + ia] = hg[e];
+			}
+		}
+		if (!pgh::GlmCholesky(chol, static_cast<int>(q1), M, 1e-10, nullptr)) {
+			null_status = PGH_GLM_SINGULAR_MATRIX; // (the fit factored this H up to its last step of at most 1e-10)
+		}
+		for (uint32_t i = 0; i < q1 && null_status == PGH_GLM_OK; i++) {
+			double t = hg[nh + i];
+			for (uint32_t e = 0; e < i; e++) {
+				t -= chol[i * M + e] * yg[e];
+			}
+			yg[i] = t / chol[i * M + i];
+		}
+	}
+	SkatWork wk;
+	for (size_t ci = 0; ci + 1 < chunk_first.size(); ci++) {
+		const uint32_t s0 = chunk_first[ci], ns = chunk_first[ci + 1] - s0;
+		const uint64_t used = out_off[s0 + ns - 1] + pgh::SkatSetDoubles(set_off[s0 + ns] - set_off[s0 + ns - 1], kp);
+		PGH_HIP(hipMemsetAsync(d_ctr, 0, ctr_bytes, st), "skat_sparse counter clear");
+		PGH_HIP(pgh::LaunchSkatSparse(ds->Sparse(), ns, d_off + s0, d_vidx, d_r, d_w, d_zr, kp, k, std::min(n_groups, ns),
+		                              vectors.p, d_ctr, d_out_off + s0, sums.As<double>(), d_counts + s0, st),
+		        "skat_sparse set kernel");
+		if (used) {
+			PGH_HIP(hipMemcpyAsync(hsums.data(), sums.p, 8ull * used, hipMemcpyDeviceToHost, st), "skat_sparse sums copy");
+		}
+		PGH_HIP(hipMemcpyAsync(counts.data() + s0, d_counts + s0, sizeof(pgh::SkatSetCounts) * ns, hipMemcpyDeviceToHost, st),
+		        "skat_sparse counts copy");
+		PGH_HIP(hipStreamSynchronize(st), "skat_sparse sync");
+		for (uint32_t s = s0; s < s0 + ns; s++) {
+			const uint64_t m0 = set_off[s];
+			SkatFinishSet(static_cast<uint32_t>(set_off[s + 1] - m0), kp, k, hsums.data() + out_off[s], weight ? weight + m0 : nullptr,
+			              chol, yg, null_status, n_y, counts[s], wk, &rows[s], lam.data() + m0);
+		}
+	}
+	std::copy(rows.begin(), rows.end(), out);
+	if (lambda_out) {
+		std::copy_n(lam.data(), n_memb, lambda_out);
+	}
+	return PGH_OK;
+}
+
 } // namespace
 
 extern "C" double pgh_glm_p_from_t(double t, double df) {
@@ -917,18 +1177,8 @@ extern "C" int pgh_glm_sparse(const pgh_dataset *ds, const pgh_subset *subset, u
 
 namespace {
 
-// pgh_glm_score_sparse and pgh_glm_score_sparse_spa (spa != null) after the latter's own argument checks.
-int GlmScoreSparseEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
-                        const double *phenotype, uint32_t n_covar, const double *covariates, pgh_glm_row *out,
-                        const GlmScoreSpaArgs *spa, char *errbuf) {
-	PGH_ONE_DEVICE(ds);
-	PGH_SPARSE_ROWS(ds);
-	const int rc = GlmCheckCommon(ds, subset, v_begin, v_end, 1, phenotype, n_covar, covariates, PGH_GLM_LOGISTIC, out,
-	                              errbuf);
-	if (rc != PGH_OK) {
-		return rc;
-	}
-	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct;
+// The score tests' phenotype: every value 0, 1 or NaN, with a case and a control.
+int GlmCheckBinary(const double *phenotype, uint32_t n_out, char *errbuf) {
 	uint32_t cases = 0, controls = 0;
 	for (uint32_t i = 0; i < n_out; i++) {
 		if (std::isnan(phenotype[i])) {
@@ -944,6 +1194,68 @@ int GlmScoreSparseEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_
 	if (!cases || !controls) {
 		SetErr(errbuf, "no cases or no controls among the samples with a phenotype");
 		return PGH_ERR_ARG;
+	}
+	return PGH_OK;
+}
+
+// The set arguments that pgh_burden_sparse and pgh_skat_sparse share (out: the caller's rows).
+int GlmCheckSets(const pgh_dataset *ds, uint32_t n_sets, const uint64_t *set_off, const uint32_t *set_vidx,
+                 const double *weight, const void *out, char *errbuf) {
+	if (n_sets == 0) {
+		SetErr(errbuf, "at least one set is needed");
+		return PGH_ERR_ARG;
+	}
+	if (!set_off || !out) {
+		SetErr(errbuf, "null argument");
+		return PGH_ERR_ARG;
+	}
+	if (set_off[0] != 0) {
+		SetErr(errbuf, "set_off[0] must be 0, got " + std::to_string(set_off[0]));
+		return PGH_ERR_ARG;
+	}
+	for (uint32_t s = 0; s < n_sets; s++) {
+		if (set_off[s + 1] < set_off[s]) {
+			SetErr(errbuf, "set_off decreases at set " + std::to_string(s) + " (" + std::to_string(set_off[s]) + " -> " +
+			                   std::to_string(set_off[s + 1]) + ")");
+			return PGH_ERR_ARG;
+		}
+	}
+	const uint64_t n_memb = set_off[n_sets];
+	const uint32_t n_var = ds->v_end - ds->v_begin;
+	if (n_memb && !set_vidx) {
+		SetErr(errbuf, "null argument");
+		return PGH_ERR_ARG;
+	}
+	for (uint64_t m = 0; m < n_memb; m++) {
+		if (set_vidx[m] >= n_var) {
+			SetErr(errbuf, "set_vidx[" + std::to_string(m) + "] = " + std::to_string(set_vidx[m]) +
+			                   " is not below the dataset's variant count " + std::to_string(n_var));
+			return PGH_ERR_ARG;
+		}
+	}
+	for (uint64_t m = 0; weight && m < n_memb; m++) {
+		if (!std::isfinite(weight[m])) {
+			SetErr(errbuf, "weight " + std::to_string(m) + " is not finite");
+			return PGH_ERR_ARG;
+		}
+	}
+	return PGH_OK;
+}
+
+// pgh_glm_score_sparse and pgh_glm_score_sparse_spa (spa != null) after the latter's own argument checks.
+int GlmScoreSparseEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                        const double *phenotype, uint32_t n_covar, const double *covariates, pgh_glm_row *out,
+                        const GlmScoreSpaArgs *spa, char *errbuf) {
+	PGH_ONE_DEVICE(ds);
+	PGH_SPARSE_ROWS(ds);
+	const int rc = GlmCheckCommon(ds, subset, v_begin, v_end, 1, phenotype, n_covar, covariates, PGH_GLM_LOGISTIC, out,
+	                              errbuf);
+	if (rc != PGH_OK) {
+		return rc;
+	}
+	const int rc_y = GlmCheckBinary(phenotype, subset ? subset->n_out : ds->sample_ct, errbuf);
+	if (rc_y != PGH_OK) {
+		return rc_y;
 	}
 	if (v_end == v_begin) {
 		return PGH_OK;
@@ -986,43 +1298,50 @@ extern "C" int pgh_burden_sparse(const pgh_dataset *ds, const pgh_subset *subset
 	if (rc != PGH_OK) {
 		return rc;
 	}
-	if (n_sets == 0) {
-		SetErr(errbuf, "at least one set is needed");
-		return PGH_ERR_ARG;
-	}
-	if (!set_off || !out) {
-		SetErr(errbuf, "null argument");
-		return PGH_ERR_ARG;
-	}
-	if (set_off[0] != 0) {
-		SetErr(errbuf, "set_off[0] must be 0, got " + std::to_string(set_off[0]));
-		return PGH_ERR_ARG;
-	}
-	for (uint32_t s = 0; s < n_sets; s++) {
-		if (set_off[s + 1] < set_off[s]) {
-			SetErr(errbuf, "set_off decreases at set " + std::to_string(s) + " (" + std::to_string(set_off[s]) + " -> " +
-			                   std::to_string(set_off[s + 1]) + ")");
-			return PGH_ERR_ARG;
-		}
-	}
-	const uint64_t n_memb = set_off[n_sets];
-	const uint32_t n_var = ds->v_end - ds->v_begin;
-	if (n_memb && !set_vidx) {
-		SetErr(errbuf, "null argument");
-		return PGH_ERR_ARG;
-	}
-	for (uint64_t m = 0; m < n_memb; m++) {
-		if (set_vidx[m] >= n_var) {
-			SetErr(errbuf, "set_vidx[" + std::to_string(m) + "] = " + std::to_string(set_vidx[m]) +
-			                   " is not below the dataset's variant count " + std::to_string(n_var));
-			return PGH_ERR_ARG;
-		}
-	}
-	for (uint64_t m = 0; weight && m < n_memb; m++) {
-		if (!std::isfinite(weight[m])) {
-			SetErr(errbuf, "weight " + std::to_string(m) + " is not finite");
-			return PGH_ERR_ARG;
-		}
+	const int rc_sets = GlmCheckSets(ds, n_sets, set_off, set_vidx, weight, out, errbuf);
+	if (rc_sets != PGH_OK) {
+		return rc_sets;
 	}
 	return BurdenSparseOne(ds, subset, phenotype, n_covar, covariates, n_sets, set_off, set_vidx, weight, out, errbuf);
+}
+
+extern "C" int pgh_skat_sparse(const pgh_dataset *ds, const pgh_subset *subset, const double *phenotype, uint32_t n_covar,
+                               const double *covariates, uint32_t n_sets, const uint64_t *set_off,
+                               const uint32_t *set_vidx, const double *weight, pgh_skat_row *out, double *lambda_out,
+                               char *errbuf) {
+	PGH_ONE_DEVICE(ds);
+	PGH_SPARSE_ROWS(ds);
+	// the arguments pgh_glm_score_sparse has too, over the whole resident range (`out` is checked with the sets)
+	int rc = GlmCheckCommon(ds, subset, ds ? ds->v_begin : 0, ds ? ds->v_begin : 0, 1, phenotype, n_covar, covariates,
+	                        PGH_GLM_LOGISTIC, nullptr, errbuf);
+	if (rc == PGH_OK) {
+		rc = GlmCheckBinary(phenotype, subset ? subset->n_out : ds->sample_ct, errbuf);
+	}
+	if (rc == PGH_OK) {
+		rc = GlmCheckSets(ds, n_sets, set_off, set_vidx, weight, out, errbuf);
+	}
+	if (rc != PGH_OK) {
+		return rc;
+	}
+	for (uint32_t s = 0; s < n_sets; s++) {
+		if (set_off[s + 1] - set_off[s] > PGH_SKAT_MAX_SET) {
+			SetErr(errbuf, "set larger than PGH_SKAT_MAX_SET (" + std::to_string(PGH_SKAT_MAX_SET) + "): set " +
+			                   std::to_string(s) + " holds " + std::to_string(set_off[s + 1] - set_off[s]) + " memberships");
+			return PGH_ERR_ARG;
+		}
+	}
+	return SkatSparseOne(ds, subset, phenotype, n_covar, covariates, n_sets, set_off, set_vidx, weight, out, lambda_out,
+	                     errbuf);
+}
+
+extern "C" double pgh_skat_p_from_lambda(double q, const double *lambda, uint32_t n, uint8_t *state) {
+	return pgh::SkatPFromLambda(q, lambda, n, state);
+}
+
+extern "C" int pgh_symmetric_eigenvalues(const double *a, uint32_t n, double *out) {
+	if (!a || !out || n == 0) {
+		return PGH_ERR_ARG;
+	}
+	pgh::SymmetricEigenvalues(a, n, out);
+	return PGH_OK;
 }

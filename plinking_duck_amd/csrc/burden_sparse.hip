@@ -17,9 +17,10 @@
 // are reduced by a fixed butterfly and the waves in the order 0..3.  So a set's numbers do not depend on the other sets
 // of the call, on the workgroup that took it or on how many workgroups there are.  Entries whose staged y is NaN
 // (outside the subset, or no phenotype) are skipped in both passes.  A dense-form member is read from its pool row as
-// base 0 with one entry per sample whose code is 1 or 2, 16 samples per word per lane.
+// base 0 with one entry per sample whose code is 1 or 2, 16 samples per word per lane (WalkMember, set_walk.hpp).
 #include "device_utils.hpp"
 #include "glm.hpp"
+#include "set_walk.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -27,45 +28,8 @@ namespace pgh {
 
 namespace {
 
-constexpr int kBlock = 256;
+constexpr int kBlock = kSetBlock;
 constexpr int kWaves = kBlock / 64;
-
-// The entries of row v that count, at stride over the workgroup: f(sample, val(code) - val(base), y[sample]).
-template <class F>
-__device__ inline void WalkMember(const SparseView &sv, uint32_t v, int32_t ro, int vb, const double *__restrict__ y,
-                                  int tid, F &&f) {
-	if (ro < 0) {
-		const uint64_t e0 = sv.off[v], e1 = sv.off[v + 1];
-		for (uint64_t p = e0 + tid; p < e1; p += kBlock) {
-			const uint32_t x = sv.entries[p];
-			const uint32_t smp = x >> 2, code = x & 3u;
-			if (smp < sv.sample_ct) {
-				const double yi = y[smp];
-				if (yi == yi) {
-					f(smp, (code == 3u ? 0 : static_cast<int>(code)) - vb, yi);
-				}
-			}
-		}
-	} else {
-		const uint32_t *row = reinterpret_cast<const uint32_t *>(sv.pool + static_cast<uint64_t>(ro) * sv.pitch);
-		const uint32_t words = (sv.sample_ct + 15u) / 16u;
-		for (uint32_t wi = tid; wi < words; wi += kBlock) {
-			const uint32_t word = row[wi];
-			uint32_t hit = (word ^ (word >> 1)) & 0x55555555u; // the low bit of every slot that holds 1 or 2
-			while (hit) {
-				const int bit = __ffs(static_cast<int>(hit)) - 1;
-				hit &= hit - 1u;
-				const uint32_t smp = wi * 16u + static_cast<uint32_t>(bit >> 1);
-				if (smp < sv.sample_ct) {
-					const double yi = y[smp];
-					if (yi == yi) {
-						f(smp, static_cast<int>((word >> bit) & 3u), yi);
-					}
-				}
-			}
-		}
-	}
-}
 
 template <int KP>
 __global__ void __launch_bounds__(kBlock)

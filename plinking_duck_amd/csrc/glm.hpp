@@ -200,4 +200,23 @@ hipError_t LaunchBurdenSparse(const SparseView &sv, uint32_t n_sets, const uint6
                               uint32_t n_y, uint32_t n_groups, void *scratch, uint32_t *counter, double *sums,
                               BurdenAux *aux, uint8_t *x_const, hipStream_t stream);
 
+// ---- pgh_skat_sparse (skat_sparse.hip): the cross-product sums of a set's members under the score test's null model ----
+struct SkatSetCounts {
+	uint32_t n_carriers; // samples with a phenotype and an entry in some member
+	uint32_t n_nonzero;  // (membership, entry) pairs of such samples with d != 0
+};
+// Doubles of one set of m memberships in `out`: packed upper A (row-major), C (m x (kp + 1)), U0 (m).
+inline uint64_t SkatSetDoubles(uint64_t m, uint32_t kp) {
+	return m * (m + 1) / 2 + m * (kp + 1) + m;
+}
+// For the sets s < n_sets (CSR as for LaunchBurdenSparse; no set holds more than PGH_SKAT_MAX_SET memberships), at
+// out + out_off[s]: A_jl = sum_i w_i d_ij d_il (j <= l), c_j = sum_i w_i d_ij [1, z_i] and U0_j = sum_i d_ij r_i, the
+// sums of the file's header comment; and counts[s].  r, w, z: LaunchGlmScoreSparse's (raw-sample order, NaN r = not in
+// S).  scratch: n_groups x BurdenScratchPerGroup bytes, ALL ZERO on entry and on exit; counter: one uint32, zero on
+// entry.  Nothing in the output depends on n_groups (>= 1).
+hipError_t LaunchSkatSparse(const SparseView &sv, uint32_t n_sets, const uint64_t *set_off, const uint32_t *set_vidx,
+                            const double *r, const double *w, const double *z, uint32_t kp, uint32_t k,
+                            uint32_t n_groups, void *scratch, uint32_t *counter, const uint64_t *out_off, double *out,
+                            SkatSetCounts *counts, hipStream_t stream);
+
 } // namespace pgh

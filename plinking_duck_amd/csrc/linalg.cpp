@@ -76,12 +76,16 @@ namespace {
 // Householder tridiagonalisation + implicit-shift QL, for the larger matrices (plink_pca's final 220 x 220 Gram
 // matrix: ~6 n^3 contiguous flops instead of Jacobi's ~10 sweeps x 3 n^3).  qt holds the accumulated orthogonal
 // factor as ROWS (row j = j-th basis vector) so that both the reflector updates and the QL rotations run over
-// contiguous memory.  On return d = eigenvalues (unordered), row j of qt = eigenvector of d[j].
-bool TridiagonalEigen(std::vector<double> &a, size_t n, std::vector<double> &d, std::vector<double> &qt) {
+// contiguous memory.  On return d = eigenvalues (unordered), row j of qt = eigenvector of d[j].  vectors == false: qt is
+// left alone and only d is computed, by the same arithmetic.
+bool TridiagonalEigen(std::vector<double> &a, size_t n, std::vector<double> &d, std::vector<double> &qt,
+                      bool vectors = true) {
 	std::vector<double> e(n, 0.0), v(n), pv(n);
-	qt.assign(n * n, 0.0);
-	for (size_t i = 0; i < n; i++) {
-		qt[i * n + i] = 1.0;
+	if (vectors) {
+		qt.assign(n * n, 0.0);
+		for (size_t i = 0; i < n; i++) {
+			qt[i * n + i] = 1.0;
+		}
 	}
 	// A <- H_k A H_k for k = 0 .. n-3, H_k = I - beta v v^T zeroing column k below the subdiagonal (the matrix is
 	// kept full and symmetric: row k of the trailing block is read instead of column k)
@@ -124,6 +128,9 @@ bool TridiagonalEigen(std::vector<double> &a, size_t n, std::vector<double> &d, 
 		a[k * n + k + 1] = a[(k + 1) * n + k] = alpha;
 		for (size_t i = 1; i < m; i++) {
 			a[k * n + k + 1 + i] = a[(k + 1 + i) * n + k] = 0.0;
+		}
+		if (!vectors) {
+			continue;
 		}
 		// Q <- Q H_k: with the basis vectors as rows of qt, rows k+1 .. of qt mix: qt_rows -= beta v (v^T qt_rows)
 		std::fill(pv.begin(), pv.end(), 0.0);
@@ -188,6 +195,9 @@ bool TridiagonalEigen(std::vector<double> &a, size_t n, std::vector<double> &d, 
 				p = sn * r;
 				d[i + 1] = gg + p;
 				gg = cs * r - b;
+				if (!vectors) {
+					continue;
+				}
 				double *lo = &qt[i * n], *hi = &qt[(i + 1) * n];
 				for (size_t k = 0; k < n; k++) {
 					f = hi[k];
@@ -293,6 +303,26 @@ void SymmetricEigen(const std::vector<double> &g, size_t n, std::vector<double> 
 			v[i * n + k] = vt[order[k] * n + i];
 		}
 	}
+}
+
+bool SymmetricEigenvalues(const double *a, size_t n, double *out) {
+	for (size_t i = 0; i < n * n; i++) {
+		if (!std::isfinite(a[i])) { // neither iteration ends on such a matrix
+			std::fill(out, out + n, std::nan(""));
+			return false;
+		}
+	}
+	std::vector<double> work(a, a + n * n), d, unused;
+	if (TridiagonalEigen(work, n, d, unused, false)) {
+		std::sort(d.begin(), d.end(), [](double x, double y) { return x > y; });
+		std::copy(d.begin(), d.end(), out);
+		return true;
+	}
+	// (no convergence in 60 QL steps for some eigenvalue: Jacobi, which cannot fail)
+	std::vector<double> v;
+	SymmetricEigen(std::vector<double>(a, a + n * n), n, d, v);
+	std::copy(d.begin(), d.end(), out);
+	return false;
 }
 
 void ThinSvdInPlace(double *a, size_t m, size_t n, std::vector<double> &s) {

@@ -18,4 +18,9 @@ void ThinSvdInPlace(double *a, size_t m, size_t n, std::vector<double> &s);
 void SymmetricEigen(const std::vector<double> &g, size_t n, std::vector<double> &eigenvalues,
                     std::vector<double> &v);
 
+// The eigenvalues alone of the symmetric n x n matrix a (row-major), in descending order: Householder
+// tridiagonalisation and implicit QL, about 4/3 n^3 flops.  Returns false when the QL iteration did not converge and
+// the values come from SymmetricEigen instead, or when an entry is not finite (out is then all NaN).  Shared with pgh_skat_sparse (one matrix per variant set).
+bool SymmetricEigenvalues(const double *a, size_t n, double *out);
+
 } // namespace pgh

@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = [
     "pgh_reader_unpack_start", "pgh_reader_unpack_wait", "pgh_get_2bit", "pgh_get_counts", "pgh_get_missingness", "pgh_get_int8", "pgh_get_dosage_f64", "pgh_get_phased",
     "pgh_tally_start", "pgh_tally_request", "pgh_tally_wait", "pgh_tally_counts", "pgh_tally_hwe_lnp",
     "pgh_tally_sample_missing", "pgh_tally_destroy", "pgh_tally_passes_started", "pgh_host_alloc", "pgh_host_free", "pgh_trim_device_cache",
-    "pgh_reader_error", "pgh_open_sparse", "pgh_get_sparse_info", "pgh_sparse_opens_started", "pgh_glm", "pgh_glm_multi", "pgh_glm_sparse", "pgh_glm_score_sparse", "pgh_glm_score_sparse_spa", "pgh_burden_sparse", "pgh_score_sparse", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
+    "pgh_reader_error", "pgh_open_sparse", "pgh_get_sparse_info", "pgh_sparse_opens_started", "pgh_glm", "pgh_glm_multi", "pgh_glm_sparse", "pgh_glm_score_sparse", "pgh_glm_score_sparse_spa", "pgh_burden_sparse", "pgh_skat_sparse", "pgh_skat_p_from_lambda", "pgh_symmetric_eigenvalues", "pgh_score_sparse", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
     "pgh_king_counts", "pgh_king_table", "pgh_king_kinship",
     "pgh_ld_window_sums", "pgh_ld_prune", "pgh_ld_exceeds", "pgh_ld_scores", "pgh_ld_r2",
     "pgh_grm", "pgh_grm_standardize",
@@ -82,6 +82,15 @@ class PghBurdenRow(C.Structure):
     ]
 
 
+class PghSkatRow(C.Structure):
+    _fields_ = [
+        ("q", C.c_double), ("p_skat", C.c_double), ("beta", C.c_double), ("se", C.c_double), ("stat", C.c_double),
+        ("p", C.c_double), ("lambda_sum", C.c_double), ("lambda_max", C.c_double), ("obs_ct", C.c_uint32),
+        ("n_carriers", C.c_uint32), ("n_lambda", C.c_uint32), ("errcode", C.c_uint8), ("p_state", C.c_uint8),
+        ("pad", C.c_uint8 * 2),
+    ]
+
+
 # pgh_king_counts' planes, pgh_king_pair, and the kernel's tile of sample pairs (a test of tile edges names it)
 KING_NSNP, KING_HETHET, KING_IBS0, KING_HET1HOM2, KING_HET2HOM1, KING_PLANES = 0, 1, 2, 3, 4, 5
 KING_TILE = 128
@@ -107,6 +116,15 @@ GLM_ROW_DTYPE = np.dtype([("beta", "<f8"), ("se", "<f8"), ("stat", "<f8"), ("p",
 BURDEN_ROW_DTYPE = np.dtype([("beta", "<f8"), ("se", "<f8"), ("stat", "<f8"), ("p", "<f8"), ("mean", "<f8"),
                              ("obs_ct", "<u4"), ("n_nonzero", "<u4"), ("errcode", "u1"), ("pad", "u1", (7,))])
 BURDEN_SCRATCH_ENV = "PGH_BURDEN_SCRATCH_BYTES"
+# pgh_skat_row, the largest set, pgh_skat_row.p_state's values and the environment variable that bounds
+# pgh_skat_sparse's device scratch (results do not depend on it)
+SKAT_ROW_DTYPE = np.dtype([("q", "<f8"), ("p_skat", "<f8"), ("beta", "<f8"), ("se", "<f8"), ("stat", "<f8"),
+                           ("p", "<f8"), ("lambda_sum", "<f8"), ("lambda_max", "<f8"), ("obs_ct", "<u4"),
+                           ("n_carriers", "<u4"), ("n_lambda", "<u4"), ("errcode", "u1"), ("p_state", "u1"),
+                           ("pad", "u1", (2,))])
+SKAT_MAX_SET = 256
+SKAT_P_NONE, SKAT_P_EXACT, SKAT_P_SADDLEPOINT, SKAT_P_NEAR_MEAN, SKAT_P_FAILED = range(5)
+SKAT_SCRATCH_ENV = "PGH_SKAT_SCRATCH_BYTES"
 # pgh_score_sparse: weight columns per walk of the entries, the LDS bytes of a sample tile's accumulators (a tile holds
 # SCORE_SPARSE_ACC_BYTES // (8 * accumulators + 4) samples, rounded down to a multiple of 64) and the environment
 # variable that sets the row slices per tile (results do not depend on it)
@@ -234,6 +252,9 @@ def _load():
         "pgh_glm_score_sparse": (C.c_int, [vp, vp, u32, u32, vp, u32, vp, vp, cp]),
         "pgh_glm_score_sparse_spa": (C.c_int, [vp, vp, u32, u32, vp, u32, vp, C.c_double, vp, vp, vp, cp]),
         "pgh_burden_sparse": (C.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, cp]),
+        "pgh_skat_sparse": (C.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, cp]),
+        "pgh_skat_p_from_lambda": (C.c_double, [C.c_double, vp, u32, vp]),
+        "pgh_symmetric_eigenvalues": (C.c_int, [vp, u32, vp]),
         "pgh_score_sparse": (C.c_int, [vp, vp, u32, vp, vp, vp, u32, C.c_int, vp, vp, vp, cp]),
         "pgh_glm_p_from_t": (C.c_double, [C.c_double, C.c_double]),
         "pgh_glm_p_from_z": (C.c_double, [C.c_double]),
@@ -288,6 +309,29 @@ def glm_p_from_t(t: float, df: float) -> float:
 def glm_p_from_z(z: float) -> float:
     """Two-sided p of a standard normal z (ZstatToPvalue)."""
     return _lib.pgh_glm_p_from_z(float(z))
+
+
+def skat_p_from_lambda(q: float, lam, return_state: bool = False):
+    """pgh_skat_p_from_lambda: the upper tail of sum_k lam[k] chi^2_1 at q (exact for one eigenvalue, Kuonen's
+    saddlepoint approximation otherwise).  With return_state also the state, SKAT_P_*."""
+    a = np.ascontiguousarray(lam, dtype=np.float64)
+    if a.ndim != 1:
+        raise ValueError("lam must be a one-dimensional array of eigenvalues")
+    state = C.c_uint8(0)
+    p = _lib.pgh_skat_p_from_lambda(float(q), _ptr(a) if a.size else None, a.size, C.byref(state))
+    return (p, state.value) if return_state else p
+
+
+def symmetric_eigenvalues(a) -> np.ndarray:
+    """pgh_symmetric_eigenvalues: the eigenvalues of a symmetric matrix, descending."""
+    m = np.ascontiguousarray(a, dtype=np.float64)
+    if m.ndim != 2 or m.shape[0] != m.shape[1] or m.shape[0] == 0:
+        raise ValueError(f"a must be a square matrix, got shape {m.shape}")
+    out = np.zeros(m.shape[0], dtype=np.float64)
+    rc = _lib.pgh_symmetric_eigenvalues(_ptr(m), m.shape[0], _ptr(out))
+    if rc != PGH_OK:
+        raise PghArgError(rc, "pgh_symmetric_eigenvalues refused its arguments")
+    return out
 
 
 def king_kinship(hethet: int, ibs0: int, het1hom2: int, het2hom1: int) -> float:
@@ -984,23 +1028,10 @@ class Dataset:
                                              _ptr(state), eb), eb)
         return dict(Dataset._glm_rows_dict(rows), p_spa=p_spa, spa_state=state)
 
-    def burden_sparse(self, phenotype, set_off, set_vidx, weights=None, covariates=None,
-                      subset: Subset | None = None) -> np.ndarray:
-        """pgh_burden_sparse: per variant set, the linear fit of phenotype on the weighted burden of the set's variants
-        plus covariates, over a sparse-resident dataset.  The sets are in CSR form: set s is
-        set_vidx[set_off[s]:set_off[s + 1]], indices into the dataset's resident variants (0 = v_begin), any order,
-        repeats counted; weights: None (1.0) or one per membership.  Returns one BURDEN_ROW_DTYPE row per set
-        (errcode: an index into GLM_ERRCODES)."""
-        n_out = subset.size if subset else self.n_samples
-        y = np.ascontiguousarray(phenotype, dtype=np.float64)
-        if y.shape != (n_out,):
-            raise ValueError(f"phenotype must hold one value per output sample ({n_out}), got shape {y.shape}")
-        if covariates is None:
-            z = np.zeros((0, n_out), dtype=np.float64)
-        else:
-            z = np.ascontiguousarray(np.atleast_2d(np.asarray(covariates, dtype=np.float64)))
-            if z.shape[1] != n_out:
-                raise ValueError(f"covariates must be n_covar x {n_out}, got shape {z.shape}")
+    @staticmethod
+    def _set_args(set_off, set_vidx, weights):
+        """(set_off as uint64, set_vidx as uint32, weights as float64 or None) of the set calls, after their shape
+        checks."""
         off = np.asarray(set_off)
         vidx = np.asarray(set_vidx)
         for name, a in (("set_off", off), ("set_vidx", vidx)):
@@ -1021,12 +1052,52 @@ class Dataset:
             w = np.ascontiguousarray(weights, dtype=np.float64)
             if w.shape != vidx.shape:
                 raise ValueError(f"weights must hold one value per membership ({vidx.size}), got shape {w.shape}")
+        return off, vidx, w
+
+    def burden_sparse(self, phenotype, set_off, set_vidx, weights=None, covariates=None,
+                      subset: Subset | None = None) -> np.ndarray:
+        """pgh_burden_sparse: per variant set, the linear fit of phenotype on the weighted burden of the set's variants
+        plus covariates, over a sparse-resident dataset.  The sets are in CSR form: set s is
+        set_vidx[set_off[s]:set_off[s + 1]], indices into the dataset's resident variants (0 = v_begin), any order,
+        repeats counted; weights: None (1.0) or one per membership.  Returns one BURDEN_ROW_DTYPE row per set
+        (errcode: an index into GLM_ERRCODES)."""
+        n_out = subset.size if subset else self.n_samples
+        y = np.ascontiguousarray(phenotype, dtype=np.float64)
+        if y.shape != (n_out,):
+            raise ValueError(f"phenotype must hold one value per output sample ({n_out}), got shape {y.shape}")
+        if covariates is None:
+            z = np.zeros((0, n_out), dtype=np.float64)
+        else:
+            z = np.ascontiguousarray(np.atleast_2d(np.asarray(covariates, dtype=np.float64)))
+            if z.shape[1] != n_out:
+                raise ValueError(f"covariates must be n_covar x {n_out}, got shape {z.shape}")
+        off, vidx, w = Dataset._set_args(set_off, set_vidx, weights)
+        n_sets = off.size - 1
         rows = np.zeros(n_sets, dtype=BURDEN_ROW_DTYPE)
         eb = _errbuf()
         _check(_lib.pgh_burden_sparse(self._h, subset._h if subset else None, _ptr(y), z.shape[0],
                                       _ptr(z) if z.size else None, n_sets, _ptr(off), _ptr(vidx) if vidx.size else None,
                                       _ptr(w) if w is not None and w.size else None, _ptr(rows), eb), eb)
         return rows
+
+    def skat_sparse(self, phenotype, set_off, set_vidx, weights=None, covariates=None, subset: Subset | None = None,
+                    return_lambda: bool = False):
+        """pgh_skat_sparse: per variant set, the SKAT test and the burden score test of a 0 / 1 phenotype (NaN =
+        missing) under glm_score_sparse()'s null model, over a sparse-resident dataset.  The sets and weights are
+        burden_sparse()'s, at most SKAT_MAX_SET memberships a set.  Returns one SKAT_ROW_DTYPE row per set (errcode: an
+        index into GLM_ERRCODES; p_state: SKAT_P_*), and with return_lambda also the eigenvalues of every set, all
+        memberships of set s at set_off[s], descending (float64; NaN for a row that is not decided)."""
+        _, _, y, z = Dataset._score_sparse_args(self, phenotype, covariates, None, None, subset)
+        off, vidx, w = Dataset._set_args(set_off, set_vidx, weights)
+        n_sets = off.size - 1
+        rows = np.zeros(n_sets, dtype=SKAT_ROW_DTYPE)
+        lam = np.zeros(vidx.size, dtype=np.float64) if return_lambda else None
+        eb = _errbuf()
+        _check(_lib.pgh_skat_sparse(self._h, subset._h if subset else None, _ptr(y), z.shape[0],
+                                    _ptr(z) if z.size else None, n_sets, _ptr(off), _ptr(vidx) if vidx.size else None,
+                                    _ptr(w) if w is not None and w.size else None, _ptr(rows),
+                                    _ptr(lam) if lam is not None and lam.size else None, eb), eb)
+        return (rows, lam) if return_lambda else rows
 
     def score_sparse(self, vidx, weights, flip=None, mode: int = SCORE_MEAN_IMPUTE, subset: Subset | None = None,
                      dosage_sum: bool = True):
