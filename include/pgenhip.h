@@ -213,6 +213,52 @@ int pgh_subset_create(const pgh_dataset *ds, const uint64_t *sample_include, pgh
 uint32_t pgh_subset_size(const pgh_subset *ss);
 void pgh_subset_destroy(pgh_subset *ss);
 
+/* ---- variant ranges and variant lists -------------------------------------
+ * Index convention.  A variant index is GLOBAL: the variant's number in the file, whatever range the dataset holds
+ * (pgh_info.variant_begin / variant_end; for a shard group the union of its shards' ranges).  This goes for every
+ * v_begin / v_end, every variant_begin / n_var, every vidx, vidx_a / vidx_b and the reader's vidx.  The one exception
+ * is the set_vidx of pgh_burden_sparse and pgh_skat_sparse, which is DATASET-LOCAL: 0 names the first resident variant.
+ *
+ * Outside the resident range.  A range that is reversed or not inside [variant_begin, variant_end), and a list with
+ * an entry outside it, is PGH_ERR_ARG before anything is launched, with a message that says "outside the resident
+ * range" (the set tests: "is not below the dataset's variant count"); every output is untouched.
+ *
+ * The two forms.  Where an entry point takes (variant_begin, n_var, vidx), vidx == NULL means the n_var variants from
+ * variant_begin on, and vidx != NULL means the n_var listed variants (variant_begin is then ignored).  The list
+ * variant_begin, variant_begin + 1, .. gives what the range form gives, integer outputs bit for bit.  The same global
+ * variants give the same answer from every dataset that holds them -- the whole file, a window of it, a shard group --
+ * integer outputs bit for bit, floating outputs to rounding, and bit for bit where a row is stated to be a function of
+ * its variant (or its set) alone.
+ *
+ * Order, repeats and the empty list, per entry point ("call order" = the order of the list; output row or column i
+ * belongs to list entry i):
+ *   pgh_sample_counts             any order; a repeated variant counts each time; n_var == 0: PGH_OK, every count 0
+ *   pgh_dosage_sums / _unpack     any order; a repeated variant is a repeated output row; n_variants == 0: PGH_OK,
+ *                                 nothing written
+ *   pgh_unpack_samples,           any order; a repeated variant is a repeated output column; n_variants == 0: PGH_OK,
+ *   pgh_dosage_unpack_samples     nothing written
+ *   pgh_score, pgh_score_counts,  any order (the sums do not depend on it beyond rounding; allele_ct not at all); a
+ *   the score plan,               repeated variant is scored each time, with the weights, flip and counts of each of
+ *   pgh_score_sparse              its entries; n_scored == 0: PGH_OK, every sum and allele_ct 0
+ *   pgh_ld_pairs(_dev)            the pairs in any order, a variant with itself and a repeated pair included (a
+ *                                 repeated pair is a repeated output row); n_pairs == 0: PGH_OK, nothing written
+ *   pgh_pca, pgh_pca_sharded      any order; a repeated variant is a repeated row of X (with the center / inv_stdev of
+ *                                 each of its entries); fewer than (n_pcs + 1) 2 n_pcs variants, n_var == 0 included:
+ *                                 PGH_ERR_ARG ("too few variants ...").  pgh_pca_streamed alone wants ascending order.
+ *   pgh_king_counts / _table,     any order; a repeated variant counts each time (pgh_grm: with the freq of each of
+ *   pgh_grm                       its entries); n_var == 0: PGH_ERR_ARG ("n_var must be at least 1")
+ *   pgh_ld_window_sums            any order; a repeated variant is a repeated row and column of the rectangle;
+ *                                 n_var == 0: PGH_ERR_ARG (no rectangle fits: "variant rectangle ... is empty")
+ *   pgh_ld_prune, pgh_ld_scores   STRICTLY INCREASING, hence no repeats: anything else is PGH_ERR_ARG ("the variant
+ *                                 list must be strictly increasing"); n_var == 0: PGH_ERR_ARG ("n_var must be at
+ *                                 least 1")
+ *   pgh_burden_sparse,            set_vidx (dataset-local) in any order; a repeated variant counts each time (SKAT: a
+ *   pgh_skat_sparse               repeated row and column of Phi); an empty set is a row with PGH_GLM_CONST_ALLELE
+ * The range-only entry points (pgh_counts_range, pgh_missing_per_sample, pgh_unpack_range, pgh_glm, pgh_glm_multi,
+ * pgh_glm_sparse, pgh_glm_score_sparse(_spa)) accept v_begin == v_end inside the resident range: PGH_OK with no
+ * per-variant row written; pgh_missing_per_sample's per-sample counts are then 0.
+ * tests/test_variant_shapes.py pins every line of this section. */
+
 /* ---- batched device calls (the fast path of the table functions) -------- */
 
 /* PgrGetCounts over a variant range (src/plink_freq.cpp:482, plink_hardy.cpp:510,
@@ -315,7 +361,9 @@ int pgh_probe_unpack_shape_dev(const void *d_src, size_t n_vec, void *d_dst, voi
 
 /* plink_score phase 1 (src/plink_score.cpp:575-654) for n_scored variants and
  * n_cols weight columns (the reference has one; BASELINE config 4 uses 16).
- *   vidx[i]      variant index (ascending; src/plink_score.cpp:407-408)
+ *   vidx[i]      variant index, in any order, repeats allowed (see "variant ranges and variant lists" above; the
+ *                reference walks its score file in variant order, src/plink_score.cpp:407-408, and a file with
+ *                dosage tracks is scored in an order of the plan's own)
  *   weights      [n_scored][n_cols] doubles, row-major
  *   flip[i]      scored allele is REF (dosage 2 - alt)      (may be NULL)
  *   mode         PGH_SCORE_MEAN_IMPUTE | _NO_MEAN_IMPUTATION | _CENTER
@@ -694,7 +742,8 @@ int pgh_burden_sparse(const pgh_dataset *ds, const pgh_subset *subset, const dou
  * have not been compared with another program's output.
  *
  * Inputs.  phenotype, n_covar, covariates and subset are pgh_glm_score_sparse's (values 0 / 1 / NaN, at least one case
- * and one control).  n_sets, set_off, set_vidx and weight (omega, finite; NULL = 1.0) are pgh_burden_sparse's, with the
+ * and one control).  n_sets, set_off, set_vidx (dataset-local indices, any order, repeats counted, an empty set allowed)
+ * and weight (omega, finite; NULL = 1.0) are pgh_burden_sparse's, with the
  * same checks and the same PGH_ERR_ARG texts; in addition no set may hold more than PGH_SKAT_MAX_SET memberships
  * ("set larger than PGH_SKAT_MAX_SET").  A dataset that is not sparse-resident and a shard group are refused as there.
  * On any error every output is untouched.

@@ -78,15 +78,15 @@ def empty_tiles(mask, tile=SPARSE_TILE):
 
 # ---- the matrices ------------------------------------------------------------------------------------------------
 
-def hard_codes(n, seed=None):
-    """(M, n) hardcall codes (3 = missing), about 8 % missing: variants 0..89 carry LD (two haplotypes per sample whose
+def hard_codes(n, seed=None, m=M):
+    """(m, n) hardcall codes (3 = missing), about 8 % missing: variants 0..89 carry LD (two haplotypes per sample whose
     latent uniforms are redrawn with probability 0.1 per variant, as tests/test_ld_prune.py's ld_codes), variants 90..
     follow three populations drawn per sample (so every mask of 127 samples and more holds all three, and a PCA of it
     has two separated leading components).  Row 3 is all missing, row 4 monomorphic, and row 5's only non-reference
     calls sit in samples that the word_block mask [64, 192) drops."""
     rng = np.random.default_rng(1000 + n if seed is None else seed)
-    codes = np.zeros((M, n), dtype=np.uint8)
-    p = rng.uniform(0.05, 0.5, M)
+    codes = np.zeros((m, n), dtype=np.uint8)
+    p = rng.uniform(0.05, 0.5, m)
     u = rng.random(2 * n)
     for k in range(90):
         redraw = rng.random(2 * n) < 0.1
@@ -95,10 +95,10 @@ def hard_codes(n, seed=None):
         codes[k] = allele[:n] + allele[n:]
     pop = rng.integers(0, 3, n)
     levels = np.array([0.08, 0.5, 0.92])
-    for k in range(90, M):
+    for k in range(90, m):
         freq = levels[rng.permutation(3)] if k % 2 else np.array([0.1, 0.1, 0.9])[rng.permutation(3)]
         codes[k] = rng.binomial(2, freq[pop])
-    codes[rng.random((M, n)) < 0.08] = 3
+    codes[rng.random((m, n)) < 0.08] = 3
     codes[ROW_ALL_MISSING] = 3
     codes[ROW_MONO] = 0
     outside = np.ones(n, dtype=bool)
@@ -109,14 +109,14 @@ def hard_codes(n, seed=None):
     return codes
 
 
-def rare_codes(n, seed=None):
-    """(codes, y): pgen_writer.rare_matrix rows (every majority code, 0..many entries) with the two het-majority rows
+def rare_codes(n, seed=None, m=M):
+    """(codes, y): m pgen_writer.rare_matrix rows (every majority code, 0..many entries) with the two het-majority rows
     of the sparse tests, a 0/1 phenotype over the raw samples, and every fourth hom-ref-majority variant enriched for
     ALT calls among its cases (tests/glm_spa_oracle.py), so that score tests beyond the saddlepoint cutoff exist."""
     import glm_spa_oracle as S
 
     rng = np.random.default_rng(2000 + n if seed is None else seed)
-    codes = W.rare_matrix(M, n, rng)
+    codes = W.rare_matrix(m, n, rng)
     for v, rate in zip((7, 8), (0.01, 0.3)):
         hit = rng.random(n) < rate
         codes[v] = 1
@@ -151,7 +151,7 @@ def validity_ref(codes):
     """uint64[V][ceil(n / 64)]: bit k set = sample k called, zero padding."""
     v, n = codes.shape
     words = np.zeros((v, (n + 63) // 64), dtype=np.uint64)
-    if n:
+    if n and v:
         bits = np.packbits(codes != 3, axis=1, bitorder="little")
         words.view(np.uint8).reshape(v, -1)[:, :bits.shape[1]] = bits
     return words

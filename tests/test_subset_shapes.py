@@ -96,10 +96,20 @@ def test_the_catalogue_is_what_the_kernels_are_meant_to_see():
     assert np.flatnonzero(SS.shapes(SS.N_WIDE)["tile_edges"]).tolist() == [8191, 8192, 16383, 16384, 16450]
 
 
+# sha256 (first 16 hex digits) of hard_codes(n) and of rare_codes(n)'s codes + phenotype, taken before the generators
+# got their m= keyword: the default must go on giving these bytes
+MATRIX_DIGESTS = {SS.N_SMALL: ("01f3507bee0546b2", "1e90c5aacda0af4c"), SS.N_WIDE: ("1aa071641715fa01", "7c3fbf90b6e9ac83")}
+
+
 def test_the_matrices_hold_the_made_rows():
+    import hashlib
+
     for n in SS.SAMPLE_COUNTS:
         codes = SS.hard_codes(n)
         assert codes.shape == (SS.M, n) and codes.max() == 3
+        rare_bytes = b"".join(a.tobytes() for a in SS.rare_codes(n))
+        assert (hashlib.sha256(codes.tobytes()).hexdigest()[:16],
+                hashlib.sha256(rare_bytes).hexdigest()[:16]) == MATRIX_DIGESTS[n], n
         assert (codes[SS.ROW_ALL_MISSING] == 3).all() and (codes[SS.ROW_MONO] == 0).all()
         block = SS.shapes(n)["word_block"]
         assert (codes[SS.ROW_BLOCK][block] == 0).all() and (codes[SS.ROW_BLOCK][~block] != 0).sum() > 100
