@@ -179,46 +179,27 @@ extern "C" int pgh_sample_counts(const pgh_dataset *ds, const pgh_subset *subset
 	if (rc != PGH_OK) {
 		return rc;
 	}
-	std::vector<uint32_t> local;
-	if (vidx) {
-		local.resize(n_var);
-		for (uint32_t i = 0; i < n_var; i++) {
-			if (vidx[i] < ds->v_begin || vidx[i] >= ds->v_end) {
-				SetErr(errbuf, "variant index outside the resident range");
-				return PGH_ERR_ARG;
-			}
-			local[i] = vidx[i] - ds->v_begin;
-		}
-	} else {
-		rc = CheckRange(ds, variant_begin, variant_begin + n_var, errbuf);
-		if (rc != PGH_OK) {
-			return rc;
-		}
-	}
 	const uint32_t N = ds->sample_ct;
 	const uint32_t n_out = subset ? subset->n_out : N;
 	const uint32_t padded = (N + 63) / 64 * 64;
 	hipStream_t st = PghThreadStream();
-	DevBuf d_cls, d_list, d_scratch;
-	HostSourceFence fence(st); // `local` feeds an asynchronous upload
-	PGH_HIP(d_cls.Alloc(sizeof(uint32_t) * 3ull * padded), "hipMalloc(sample counts)");
-	if (vidx && n_var) {
-		PGH_HIP(d_list.Alloc(sizeof(uint32_t) * n_var), "hipMalloc(sample counts)");
-		PGH_HIP(hipMemcpyAsync(d_list.p, local.data(), sizeof(uint32_t) * n_var, hipMemcpyHostToDevice, st),
-		        "sample counts upload");
+	DevBuf d_cls, d_scratch;
+	VariantRows rows;
+	rc = rows.ResolveAndUpload(ds, variant_begin, n_var, vidx, 0, st, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
 	}
+	PGH_HIP(d_cls.Alloc(sizeof(uint32_t) * 3ull * padded), "hipMalloc(sample counts)");
 	// het, hom-alt and missing column tallies in one pass; hom-ref is what is left
 	if (ds->sparse) {
-		rc = pgh_sparse::SampleClasses(ds, vidx ? 0 : variant_begin - ds->v_begin, vidx ? d_list.As<uint32_t>() : nullptr,
-		                               vidx ? local.data() : nullptr, n_var, d_cls.As<uint32_t>(), padded, st, false,
-		                               errbuf);
+		rc = pgh_sparse::SampleClasses(ds, rows.first, rows.Device(), rows.local.data(), n_var, d_cls.As<uint32_t>(), padded, st,
+		                               false, errbuf);
 		if (rc != PGH_OK) {
 			return rc;
 		}
 	} else {
 		PGH_HIP(d_scratch.Alloc(pgh::ClassCounts3ScratchBytes(ds->record_bytes)), "hipMalloc(sample counts)");
-		PGH_HIP(pgh::LaunchClassCounts3(ds->View(), vidx ? 0 : variant_begin - ds->v_begin,
-		                                vidx ? d_list.As<uint32_t>() : nullptr, n_var, d_scratch.As<uint8_t>(),
+		PGH_HIP(pgh::LaunchClassCounts3(ds->View(), rows.first, rows.Device(), n_var, d_scratch.As<uint8_t>(),
 		                                d_cls.As<uint32_t>(), padded, st),
 		        "sample counts kernel");
 	}
@@ -344,26 +325,6 @@ extern "C" int pgh_unpack_range(const pgh_dataset *ds, const pgh_subset *subset,
 // dosage tracks
 // ---------------------------------------------------------------------------
 
-//! Local variant indices of [v_begin, v_begin + n) or of vidx[0..n) on the device; NULL when the run is contiguous.
-//! `local` is the upload's (pageable) source: the caller keeps it alive behind a HostSourceFence on `st`.
-static int UploadVariantList(const pgh_dataset *ds, uint32_t v_begin, uint32_t n, const uint32_t *vidx, DevBuf &d_list,
-                             hipStream_t st, std::vector<uint32_t> &local, char *errbuf) {
-	if (!vidx) {
-		return CheckRange(ds, v_begin, v_begin + n, errbuf);
-	}
-	local.resize(n);
-	for (uint32_t i = 0; i < n; i++) {
-		if (vidx[i] < ds->v_begin || vidx[i] >= ds->v_end) {
-			SetErr(errbuf, "variant index outside the resident range");
-			return PGH_ERR_ARG;
-		}
-		local[i] = vidx[i] - ds->v_begin;
-	}
-	PGH_HIP(d_list.Alloc(sizeof(uint32_t) * n), "hipMalloc(variant list)");
-	PGH_HIP(hipMemcpyAsync(d_list.p, local.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, st), "variant list upload");
-	return PGH_OK;
-}
-
 extern "C" int pgh_dosage_sums_dev(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                                    void *d_sums, void *stream, char *errbuf) {
 	PGH_DENSE_ROWS(ds);
@@ -403,16 +364,15 @@ extern "C" int pgh_dosage_sums(const pgh_dataset *ds, const pgh_subset *subset, 
 		return rc;
 	}
 	hipStream_t st = PghThreadStream();
-	DevBuf d_list, d_sums;
-	std::vector<uint32_t> local;
-	HostSourceFence fence(st); // `local` feeds an asynchronous upload
-	rc = UploadVariantList(ds, variant_begin, n_variants, vidx, d_list, st, local, errbuf);
+	DevBuf d_sums;
+	VariantRows rows;
+	rc = rows.ResolveAndUpload(ds, variant_begin, n_variants, vidx, 0, st, errbuf);
 	if (rc != PGH_OK) {
 		return rc;
 	}
 	PGH_HIP(d_sums.Alloc(24ull * n_variants), "hipMalloc(dosage sums)");
-	PGH_HIP(pgh::LaunchDosageSums(ds->View(), ds->Dosage(), vidx ? 0 : variant_begin - ds->v_begin, d_list.As<uint32_t>(),
-	                              n_variants, subset ? subset->d_include : nullptr, d_sums.As<uint64_t>(), st),
+	PGH_HIP(pgh::LaunchDosageSums(ds->View(), ds->Dosage(), rows.first, rows.Device(), n_variants,
+	                              subset ? subset->d_include : nullptr, d_sums.As<uint64_t>(), st),
 	        "dosage sums kernel");
 	PGH_HIP(hipMemcpyAsync(sums, d_sums.p, 24ull * n_variants, hipMemcpyDeviceToHost, st), "dosage sums copy");
 	PGH_HIP(hipStreamSynchronize(st), "dosage sums sync");
@@ -460,10 +420,9 @@ extern "C" int pgh_dosage_unpack(const pgh_dataset *ds, const pgh_subset *subset
 		return rc;
 	}
 	hipStream_t st = PghThreadStream();
-	DevBuf d_list, d_out;
-	std::vector<uint32_t> local;
-	HostSourceFence fence(st); // `local` feeds an asynchronous upload
-	rc = UploadVariantList(ds, variant_begin, n_variants, vidx, d_list, st, local, errbuf);
+	DevBuf d_out;
+	VariantRows rows;
+	rc = rows.ResolveAndUpload(ds, variant_begin, n_variants, vidx, 0, st, errbuf);
 	if (rc != PGH_OK) {
 		return rc;
 	}
@@ -472,8 +431,8 @@ extern "C" int pgh_dosage_unpack(const pgh_dataset *ds, const pgh_subset *subset
 	PGH_HIP(d_out.Alloc(8ull * chunk * n_out), "hipMalloc(dosage unpack)");
 	for (uint32_t r0 = 0; r0 < n_variants; r0 += chunk) {
 		const uint32_t cnt = std::min(chunk, n_variants - r0);
-		PGH_HIP(pgh::LaunchDosageUnpack(ds->View(), ds->Dosage(), vidx ? 0 : variant_begin - ds->v_begin + r0,
-		                                vidx ? d_list.As<uint32_t>() + r0 : nullptr, cnt, subset ? subset->d_sel : nullptr,
+		PGH_HIP(pgh::LaunchDosageUnpack(ds->View(), ds->Dosage(), rows.first + (vidx ? 0 : r0),
+		                                vidx ? rows.Device() + r0 : nullptr, cnt, subset ? subset->d_sel : nullptr,
 		                                n_out, d_out.As<double>(), n_out, st),
 		        "dosage unpack kernel");
 		PGH_HIP(hipMemcpyAsync(out + static_cast<uint64_t>(r0) * n_out, d_out.p, 8ull * cnt * n_out, hipMemcpyDeviceToHost, st),
@@ -499,10 +458,9 @@ static int UnpackSamples(const pgh_dataset *ds, const pgh_subset *subset, uint32
 		return rc;
 	}
 	hipStream_t st = PghThreadStream();
-	DevBuf d_list, d_out;
-	std::vector<uint32_t> local;
-	HostSourceFence fence(st); // `local` feeds an asynchronous upload
-	rc = UploadVariantList(ds, 0, n_variants, vidx, d_list, st, local, errbuf);
+	DevBuf d_out;
+	VariantRows rows;
+	rc = rows.ResolveAndUpload(ds, 0, n_variants, vidx, pgh::kVariantRowsListOnly, st, errbuf);
 	if (rc != PGH_OK) {
 		return rc;
 	}
@@ -512,7 +470,7 @@ static int UnpackSamples(const pgh_dataset *ds, const pgh_subset *subset, uint32
 	PGH_HIP(d_out.Alloc(row_bytes * chunk), "hipMalloc(sample-major unpack)");
 	for (uint32_t k0 = 0; k0 < n_out; k0 += chunk) {
 		const uint32_t cnt = std::min(chunk, n_out - k0);
-		PGH_HIP(launch(d_list.As<uint32_t>(), k0, cnt, d_out.As<T>(), st), "sample-major unpack kernel");
+		PGH_HIP(launch(rows.Device(), k0, cnt, d_out.As<T>(), st), "sample-major unpack kernel");
 		PGH_HIP(hipMemcpyAsync(out + static_cast<uint64_t>(k0) * n_variants, d_out.p, row_bytes * cnt, hipMemcpyDeviceToHost, st),
 		        "sample-major unpack copy");
 		PGH_HIP(hipStreamSynchronize(st), "sample-major unpack sync");
@@ -691,13 +649,10 @@ static int ScorePlanCreate(const pgh_dataset *ds, const pgh_subset *subset, uint
 	if (rc != PGH_OK) {
 		return rc;
 	}
-	std::vector<uint32_t> local(n_scored);
-	for (uint32_t i = 0; i < n_scored; i++) {
-		if (vidx[i] < ds->v_begin || vidx[i] >= ds->v_end) {
-			SetErr(errbuf, "scored variant index outside the resident range");
-			return PGH_ERR_ARG;
-		}
-		local[i] = vidx[i] - ds->v_begin;
+	VariantRows rows;
+	rc = rows.Resolve(ds, 0, n_scored, vidx, pgh::kVariantRowsListOnly, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
 	}
 	if (subset && subset->n_out == 0) {
 		// nobody is kept: no counts to build tables from (their means would be 0 / 0).  The plan scores nothing, so a
@@ -714,7 +669,7 @@ static int ScorePlanCreate(const pgh_dataset *ds, const pgh_subset *subset, uint
 		// samples: they meet where ~40 % of the samples are explicit.
 		n_hard = 0;
 		auto kind = [&](uint32_t i) { // 0 hardcalls, 1 sparse, 2 mostly explicit, 3 fully explicit
-			const int32_t r = ds->dos_row_of[local[i]];
+			const int32_t r = ds->dos_row_of[rows.local[i]];
 			if (r < 0) {
 				return 0;
 			}
@@ -753,7 +708,7 @@ static int ScorePlanCreate(const pgh_dataset *ds, const pgh_subset *subset, uint
 			std::memcpy(&p_counts[4ull * k], counts[order[k]], 16);
 		}
 		for (uint32_t k = 0; k < n_scored; k++) {
-			p_local[k] = local[order[k]];
+			p_local[k] = rows.local[order[k]];
 			std::memcpy(&p_weights[static_cast<size_t>(k) * n_cols], weights + static_cast<size_t>(order[k]) * n_cols,
 			            sizeof(double) * n_cols);
 			if (flip) {
@@ -761,7 +716,7 @@ static int ScorePlanCreate(const pgh_dataset *ds, const pgh_subset *subset, uint
 			}
 		}
 	}
-	const uint32_t *up_local = reorder ? p_local.data() : local.data();
+	const uint32_t *up_local = reorder ? p_local.data() : rows.local.data();
 	const double *up_weights = reorder ? p_weights.data() : weights;
 	// Non-finite weights: the fixed-point digits of the matrix-core contraction cannot hold them (llrint of a NaN or
 	// an infinity is undefined: round 2 returned finite garbage for such a column).  They are zeroed for the
@@ -1187,24 +1142,24 @@ struct PcaSource {
 
 struct ResidentPcaSource : PcaSource {
 	const pgh_dataset *ds;
-	std::vector<uint32_t> local;
-	ResidentPcaSource(const pgh_dataset *d, std::vector<uint32_t> rows) : ds(d), local(std::move(rows)) {
+	VariantRows rows; // of the call's effective variants (host list only: PcaRun uploads a block's rows itself)
+	explicit ResidentPcaSource(const pgh_dataset *d) : ds(d) {
 		sample_ct = d->sample_ct;
 	}
 	uint32_t Count() const override {
 		return 1;
 	}
 	uint32_t MaxRows() const override {
-		return static_cast<uint32_t>(local.size());
+		return static_cast<uint32_t>(rows.local.size());
 	}
 	bool Keep() const override {
 		return true;
 	}
 	int Acquire(uint32_t, PcaBlock &out, char *) override {
 		out.view = ds->View();
-		out.local = local.data();
+		out.local = rows.local.data();
 		out.row0 = 0;
-		out.rows = static_cast<uint32_t>(local.size());
+		out.rows = MaxRows();
 		return PGH_OK;
 	}
 	void Release(uint32_t) override {
@@ -1713,18 +1668,13 @@ extern "C" int pgh_pca_sharded(const pgh_dataset *ds, const pgh_subset *subset, 
 	if (rc == PGH_OK) {
 		rc = RefuseEmptySubset(subset, errbuf);
 	}
+	ResidentPcaSource src(ds);
+	if (rc == PGH_OK) {
+		rc = src.rows.Resolve(ds, 0, n_var, vidx, pgh::kVariantRowsListOnly, errbuf);
+	}
 	if (rc != PGH_OK) {
 		return rc;
 	}
-	std::vector<uint32_t> local(n_var);
-	for (uint32_t i = 0; i < n_var; i++) {
-		if (vidx[i] < ds->v_begin || vidx[i] >= ds->v_end) {
-			SetErr(errbuf, "effective variant index outside the resident range");
-			return PGH_ERR_ARG;
-		}
-		local[i] = vidx[i] - ds->v_begin;
-	}
-	ResidentPcaSource src(ds, std::move(local));
 	return PcaRun(src, subset, n_var, center, inv_stdev, n_var_total, n_pcs, g1_init, allreduce, allreduce_ctx, eigenvalues,
 	              eigenvectors, errbuf);
 }
@@ -1855,30 +1805,26 @@ extern "C" int pgh_ld_pairs_dev(const pgh_dataset *ds, const pgh_subset *subset,
 	PGH_ONE_DEVICE(ds);
 	PGH_ENTER(ds);
 	int rc = CheckSubset(ds, subset, errbuf);
-	if (rc != PGH_OK) {
+	if (rc != PGH_OK || n_pairs == 0) {
 		return rc;
-	}
-	if (n_pairs == 0) {
-		return PGH_OK;
 	}
 	// runs of pairs that share the anchor and step through consecutive partners become one
 	// task of up to four partners (the windowed scan produces exactly such runs)
 	std::vector<pgh::LdTask> tasks;
 	tasks.reserve(n_pairs / 2 + 1);
 	for (uint32_t p = 0; p < n_pairs; p++) {
-		const uint32_t a = vidx_a[p], b = vidx_b[p];
-		if (a < ds->v_begin || a >= ds->v_end || b < ds->v_begin || b >= ds->v_end) {
-			SetErr(errbuf, "variant index outside the resident range");
-			return PGH_ERR_ARG;
+		if (!VariantPairInside(ds, vidx_a[p], vidx_b[p])) {
+			return RefuseVariantPair(ds, p, vidx_a[p], vidx_b[p], errbuf);
 		}
+		const uint32_t a = vidx_a[p] - ds->v_begin, b = vidx_b[p] - ds->v_begin; // rows
 		if (!tasks.empty()) {
 			pgh::LdTask &last = tasks.back();
-			if (last.n_b < 4 && last.a_row == a - ds->v_begin && last.b_row + last.n_b == b - ds->v_begin) {
+			if (last.n_b < 4 && last.a_row == a && last.b_row + last.n_b == b) {
 				last.n_b++;
 				continue;
 			}
 		}
-		tasks.push_back(pgh::LdTask {a - ds->v_begin, b - ds->v_begin, 1u, p});
+		tasks.push_back(pgh::LdTask {a, b, 1u, p});
 	}
 	hipStream_t st = static_cast<hipStream_t>(stream);
 	// The task list goes up through this thread's own pair of buffers (device + PINNED host), reused from call

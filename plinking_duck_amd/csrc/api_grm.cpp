@@ -72,12 +72,9 @@ extern "C" int pgh_grm(const pgh_dataset *ds, const pgh_subset *subset, uint32_t
 	}
 	const bool meanimpute = (flags & PGH_GRM_MEANIMPUTE) != 0;
 	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct;
-	if (i_begin >= i_end || j_begin >= j_end || i_end > n_out || j_end > n_out) {
-		char msg[200];
-		std::snprintf(msg, sizeof msg, "sample rectangle [%u, %u) x [%u, %u) is empty, reversed or beyond the %u output samples",
-		              i_begin, i_end, j_begin, j_end, n_out);
-		SetErr(errbuf, msg);
-		return PGH_ERR_ARG;
+	rc = CheckSampleRect(i_begin, i_end, j_begin, j_end, n_out, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
 	}
 	if (n_var == 0) {
 		SetErr(errbuf, "n_var must be at least 1");
@@ -88,50 +85,29 @@ extern "C" int pgh_grm(const pgh_dataset *ds, const pgh_subset *subset, uint32_t
 		return PGH_ERR_ARG;
 	}
 	hipStream_t st = PghThreadStream();
-	std::vector<uint32_t> local(n_var);
 	std::vector<double> table;
-	HostSourceFence fence(st); // `local` and `table` feed asynchronous uploads
-	if (vidx) {
-		for (uint32_t i = 0; i < n_var; i++) {
-			if (vidx[i] < ds->v_begin || vidx[i] >= ds->v_end) {
-				SetErr(errbuf, "variant index outside the resident range");
-				return PGH_ERR_ARG;
-			}
-			local[i] = vidx[i] - ds->v_begin;
-		}
-	} else {
-		if (static_cast<uint64_t>(variant_begin) + n_var > ds->v_end) {
-			SetErr(errbuf, "variant range is outside the resident range");
-			return PGH_ERR_ARG;
-		}
-		rc = CheckRange(ds, variant_begin, variant_begin + n_var, errbuf);
-		if (rc != PGH_OK) {
-			return rc;
-		}
-		for (uint32_t i = 0; i < n_var; i++) {
-			local[i] = variant_begin - ds->v_begin + i;
-		}
-	}
+	HostSourceFence fence(st); // `table` feeds an asynchronous upload
 	const uint32_t ni = i_end - i_begin, nj = j_end - j_begin;
 	const uint64_t n_pairs = static_cast<uint64_t>(ni) * nj;
 
 	// ---- counts over the output samples, the tables, and the list of the variants that are used ----
-	DevBuf d_list;
-	PGH_HIP(d_list.Alloc(sizeof(uint32_t) * static_cast<size_t>(n_var)), "hipMalloc(grm variant list)");
-	PGH_HIP(hipMemcpyAsync(d_list.p, local.data(), sizeof(uint32_t) * static_cast<size_t>(n_var), hipMemcpyHostToDevice, st),
-	        "grm variant list upload");
+	VariantRows rows;
+	rc = rows.ResolveAndUpload(ds, variant_begin, n_var, vidx, pgh::kVariantRowsExpand, st, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
+	}
 	uint32_t n_used = 0;
 	{
 		std::vector<uint32_t> counts(static_cast<size_t>(n_var) * 4);
 		{
 			DevBuf d_counts;
 			PGH_HIP(d_counts.Alloc(counts.size() * sizeof(uint32_t)), "hipMalloc(grm counts)");
-			PGH_HIP(pgh::LaunchCounts(ds->View(), 0, d_list.As<uint32_t>(), n_var, subset ? subset->d_mask2 : nullptr, n_out,
+			PGH_HIP(pgh::LaunchCounts(ds->View(), 0, rows.Device(), n_var, subset ? subset->d_mask2 : nullptr, n_out,
 			                          d_counts.As<uint32_t>(), st),
 			        "counts kernel");
 			PGH_HIP(hipMemcpyAsync(counts.data(), d_counts.p, counts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st),
 			        "grm counts copy");
-			PGH_HIP(hipStreamSynchronize(st), "grm counts sync"); // also: the list upload is done with `local`
+			PGH_HIP(hipStreamSynchronize(st), "grm counts sync"); // also: the list upload is done with rows.local
 		}
 		table.reserve(4 * (static_cast<size_t>(n_var) + pgh::kGrmKStep));
 		for (uint32_t k = 0; k < n_var; k++) {
@@ -145,7 +121,7 @@ extern "C" int pgh_grm(const pgh_dataset *ds, const pgh_subset *subset, uint32_t
 				used = !std::isnan(pgh_grm_standardize(c[1], c[2], called, z));
 			}
 			if (used) {
-				local[n_used++] = local[k];
+				rows.local[n_used++] = rows.local[k];
 				table.insert(table.end(), {z[0], z[1], z[2], 0.0});
 			}
 		}
@@ -176,8 +152,10 @@ extern "C" int pgh_grm(const pgh_dataset *ds, const pgh_subset *subset, uint32_t
 	DevBuf d_xt, d_table;
 	PGH_HIP(d_xt.Alloc(pitch * (rows_i + rows_j)), "hipMalloc(grm sample-major matrix)");
 	PGH_HIP(d_table.Alloc(sizeof(double) * table.size()), "hipMalloc(grm tables)");
-	PGH_HIP(hipMemcpyAsync(d_list.p, local.data(), sizeof(uint32_t) * static_cast<size_t>(n_used), hipMemcpyHostToDevice, st),
-	        "grm variant list upload");
+	rc = rows.Upload(st, errbuf, n_used); // the used prefix of the list, into the same block
+	if (rc != PGH_OK) {
+		return rc;
+	}
 	PGH_HIP(hipMemcpyAsync(d_table.p, table.data(), sizeof(double) * table.size(), hipMemcpyHostToDevice, st),
 	        "grm tables upload");
 	pgh::GrmOperand op {};
@@ -189,10 +167,10 @@ extern "C" int pgh_grm(const pgh_dataset *ds, const pgh_subset *subset, uint32_t
 	op.sel = subset ? subset->d_sel : nullptr;
 	op.table = d_table.As<double>();
 	op.n_used = n_used;
-	PGH_HIP(pgh::LaunchTranspose2bitRange(ds->View(), d_list.As<uint32_t>(), n_used, lo_i, hi_i, d_xt.As<uint8_t>(), st),
+	PGH_HIP(pgh::LaunchTranspose2bitRange(ds->View(), rows.Device(), n_used, lo_i, hi_i, d_xt.As<uint8_t>(), st),
 	        "grm transpose kernel");
 	if (!one_range) {
-		PGH_HIP(pgh::LaunchTranspose2bitRange(ds->View(), d_list.As<uint32_t>(), n_used, lo_j, hi_j,
+		PGH_HIP(pgh::LaunchTranspose2bitRange(ds->View(), rows.Device(), n_used, lo_j, hi_j,
 		                                      d_xt.As<uint8_t>() + pitch * rows_i, st),
 		        "grm transpose kernel");
 	}

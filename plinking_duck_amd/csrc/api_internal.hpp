@@ -15,6 +15,7 @@
 #include "pgen_file.hpp"
 #include "sparse.hpp"
 #include "synth.hpp"
+#include "variant_rows.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -24,6 +25,7 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <chrono>
 #include <thread>
@@ -396,15 +398,78 @@ struct HostSourceFence {
 	}
 };
 
+// PGH_OK for an empty `why` (the text of a refusal, as variant_rows.hpp's checks return it); else PGH_ERR_ARG with it
+[[maybe_unused]] int RefuseArg(char *errbuf, const std::string &why) {
+	SetErr(why.empty() ? nullptr : errbuf, why);
+	return why.empty() ? PGH_OK : PGH_ERR_ARG;
+}
+
 [[maybe_unused]] int CheckRange(const pgh_dataset *ds, uint32_t v_begin, uint32_t v_end, char *errbuf) {
-	if (!ds) {
-		SetErr(errbuf, "null dataset");
-		return PGH_ERR_ARG;
+	return RefuseArg(errbuf, ds ? pgh::VariantRangeError(ds->v_begin, ds->v_end, v_begin, v_end) : "null dataset");
+}
+
+//! A list that is only checked against the dataset's range (a group's: the union of its shards), not translated.
+[[maybe_unused]] int CheckVariantList(const pgh_dataset *ds, uint32_t n, const uint32_t *vidx, char *errbuf) {
+	return RefuseArg(errbuf, pgh::VariantListError(ds->v_begin, ds->v_end, n, vidx, false));
+}
+
+//! Pair p of the pair calls, which check inside their one walk of the two lists (a pass of its own over a million
+//! pairs shows in the call's time): both variants inside the dataset's range?
+[[maybe_unused]] inline bool VariantPairInside(const pgh_dataset *ds, uint32_t va, uint32_t vb) {
+	return pgh::VariantInside(ds->v_begin, ds->v_end, va) && pgh::VariantInside(ds->v_begin, ds->v_end, vb);
+}
+[[maybe_unused]] int RefuseVariantPair(const pgh_dataset *ds, uint32_t p, uint32_t va, uint32_t vb, char *errbuf) {
+	const uint32_t bad = pgh::VariantInside(ds->v_begin, ds->v_end, va) ? vb : va;
+	return RefuseArg(errbuf, pgh::VariantOutsideError(ds->v_begin, ds->v_end, p, bad));
+}
+
+// A call's variants -- (variant_begin, n, vidx) as pgenhip.h's section "variant ranges and variant lists" has them --
+// as rows of the resident range; the rules themselves are variant_rows.hpp's.  Resolve checks and translates on the
+// host: a list becomes local[i] = vidx[i] - v_begin, a range its `first` row and, with pgh::kVariantRowsExpand, the
+// rows first + i.  Upload puts the first `count` entries of local on the device (again, into the same block, once the
+// caller has compacted local in place) and does nothing where local is empty: a range that was not expanded goes
+// on handing (first, null list) to its kernel.  local is the upload's pageable source, so the object is its own
+// HostSourceFence: it drains the upload's stream when it goes, on every exit path, if and only if an upload was
+// issued.  Declare it after the call's DevBufs, so that it goes first.
+struct VariantRows {
+	std::vector<uint32_t> local;
+	uint32_t first = 0; // the range's first row; 0 for a list
+	DevBuf d_list;
+	std::optional<HostSourceFence> fence; // on the upload's stream, once one was issued; the first member to go
+	int Resolve(const pgh_dataset *ds, uint32_t variant_begin, uint32_t n, const uint32_t *vidx, uint32_t flags,
+	            char *errbuf) {
+		return RefuseArg(errbuf,
+		                 pgh::ResolveVariantRows(ds->v_begin, ds->v_end, variant_begin, n, vidx, flags, first, local));
 	}
-	if (v_begin > v_end || v_begin < ds->v_begin || v_end > ds->v_end) {
-		char msg[160];
-		std::snprintf(msg, sizeof msg, "variant range [%u, %u) is outside the resident range [%u, %u)", v_begin, v_end,
-		              ds->v_begin, ds->v_end);
+	int Upload(hipStream_t s, char *errbuf, size_t count = SIZE_MAX) {
+		count = std::min(count, local.size());
+		if (count && !d_list.p) { // the first upload sizes the block and sets the fence: a later one is on the same stream
+			PGH_HIP(d_list.Alloc(sizeof(uint32_t) * count), "hipMalloc(variant list)");
+			fence.emplace(s);
+		}
+		if (count) {
+			PGH_HIP(hipMemcpyAsync(d_list.p, local.data(), sizeof(uint32_t) * count, hipMemcpyHostToDevice, s),
+			        "variant list upload");
+		}
+		return PGH_OK;
+	}
+	int ResolveAndUpload(const pgh_dataset *ds, uint32_t variant_begin, uint32_t n, const uint32_t *vidx, uint32_t flags,
+	                     hipStream_t s, char *errbuf) {
+		const int rc = Resolve(ds, variant_begin, n, vidx, flags, errbuf);
+		return rc == PGH_OK ? Upload(s, errbuf) : rc;
+	}
+	uint32_t *Device() { // null: the rows are first + i
+		return d_list.As<uint32_t>();
+	}
+};
+
+// the [i_begin, i_end) x [j_begin, j_end) block of output samples that pgh_king_counts and pgh_grm compute
+[[maybe_unused]] int CheckSampleRect(uint32_t i_begin, uint32_t i_end, uint32_t j_begin, uint32_t j_end, uint32_t n_out,
+                                     char *errbuf) {
+	if (i_begin >= i_end || j_begin >= j_end || i_end > n_out || j_end > n_out) {
+		char msg[200];
+		std::snprintf(msg, sizeof msg, "sample rectangle [%u, %u) x [%u, %u) is empty, reversed or beyond the %u output samples",
+		              i_begin, i_end, j_begin, j_end, n_out);
 		SetErr(errbuf, msg);
 		return PGH_ERR_ARG;
 	}

@@ -17,7 +17,7 @@ constexpr uint64_t kTableFirstCapacity = 1ull << 20; // records of the first dev
 
 // The call's operand: the sample-major 2-bit matrix of its variants, on `st`.
 struct KingCall {
-	DevBuf d_list, d_xt;
+	DevBuf d_xt;
 	pgh::KingOperand op {};
 };
 
@@ -31,36 +31,14 @@ int Prepare(const pgh_dataset *ds, const pgh_subset *subset, uint32_t variant_be
 		SetErr(errbuf, "n_var must not exceed 2^31 - 1 (the counts are accumulated in int32)");
 		return PGH_ERR_ARG;
 	}
-	std::vector<uint32_t> local(n_var);
-	HostSourceFence fence(st); // `local` feeds an asynchronous upload
-	if (vidx) {
-		for (uint32_t i = 0; i < n_var; i++) {
-			if (vidx[i] < ds->v_begin || vidx[i] >= ds->v_end) {
-				SetErr(errbuf, "variant index outside the resident range");
-				return PGH_ERR_ARG;
-			}
-			local[i] = vidx[i] - ds->v_begin;
-		}
-	} else {
-		if (static_cast<uint64_t>(variant_begin) + n_var > ds->v_end) {
-			SetErr(errbuf, "variant range is outside the resident range");
-			return PGH_ERR_ARG;
-		}
-		int rc = CheckRange(ds, variant_begin, variant_begin + n_var, errbuf);
-		if (rc != PGH_OK) {
-			return rc;
-		}
-		for (uint32_t i = 0; i < n_var; i++) {
-			local[i] = variant_begin - ds->v_begin + i;
-		}
+	VariantRows rows; // local: the list serves the transpose alone, and its drain is the one this function ends with
+	const int rc = rows.ResolveAndUpload(ds, variant_begin, n_var, vidx, pgh::kVariantRowsExpand, st, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
 	}
 	const uint64_t pitch = pgh::TransposedPitch(n_var);
-	PGH_HIP(call.d_list.Alloc(sizeof(uint32_t) * static_cast<size_t>(n_var)), "hipMalloc(king variant list)");
 	PGH_HIP(call.d_xt.Alloc(pitch * ds->sample_ct), "hipMalloc(king sample-major matrix)");
-	PGH_HIP(hipMemcpyAsync(call.d_list.p, local.data(), sizeof(uint32_t) * static_cast<size_t>(n_var),
-	                       hipMemcpyHostToDevice, st),
-	        "king variant list upload");
-	PGH_HIP(pgh::LaunchTranspose2bit(ds->View(), call.d_list.As<uint32_t>(), n_var, call.d_xt.As<uint8_t>(), st),
+	PGH_HIP(pgh::LaunchTranspose2bit(ds->View(), rows.Device(), n_var, call.d_xt.As<uint8_t>(), st),
 	        "king transpose kernel");
 	call.op.xt = call.d_xt.As<uint8_t>();
 	call.op.pitch = pitch;
@@ -93,12 +71,9 @@ extern "C" int pgh_king_counts(const pgh_dataset *ds, const pgh_subset *subset, 
 		return rc;
 	}
 	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct;
-	if (i_begin >= i_end || j_begin >= j_end || i_end > n_out || j_end > n_out) {
-		char msg[200];
-		std::snprintf(msg, sizeof msg, "sample rectangle [%u, %u) x [%u, %u) is empty, reversed or beyond the %u output samples",
-		              i_begin, i_end, j_begin, j_end, n_out);
-		SetErr(errbuf, msg);
-		return PGH_ERR_ARG;
+	rc = CheckSampleRect(i_begin, i_end, j_begin, j_end, n_out, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
 	}
 	hipStream_t st = PghThreadStream();
 	KingCall call;

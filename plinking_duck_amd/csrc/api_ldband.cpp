@@ -21,7 +21,7 @@ constexpr const char *kScoreChunkEnv = "PGH_LD_SCORE_CHUNK_TILES";
 
 // The call's operand: the local row of each of its variants, on `st`.
 struct LdCall {
-	DevBuf d_list;
+	VariantRows rows;
 	pgh::LdBandOperand op {};
 };
 
@@ -40,39 +40,13 @@ int Prepare(const pgh_dataset *ds, const pgh_subset *subset, uint32_t variant_be
 		SetErr(errbuf, "more than 2^29 - 1 samples (the sums are accumulated in int32)");
 		return PGH_ERR_ARG;
 	}
-	std::vector<uint32_t> local(n_var);
-	HostSourceFence fence(st); // `local` feeds an asynchronous upload
-	if (vidx) {
-		for (uint32_t i = 0; i < n_var; i++) {
-			if (vidx[i] < ds->v_begin || vidx[i] >= ds->v_end) {
-				SetErr(errbuf, "variant index outside the resident range");
-				return PGH_ERR_ARG;
-			}
-			if (increasing && i && vidx[i] <= vidx[i - 1]) {
-				SetErr(errbuf, "the variant list must be strictly increasing");
-				return PGH_ERR_ARG;
-			}
-			local[i] = vidx[i] - ds->v_begin;
-		}
-	} else {
-		if (static_cast<uint64_t>(variant_begin) + n_var > ds->v_end) {
-			SetErr(errbuf, "variant range is outside the resident range");
-			return PGH_ERR_ARG;
-		}
-		int rc = CheckRange(ds, variant_begin, variant_begin + n_var, errbuf);
-		if (rc != PGH_OK) {
-			return rc;
-		}
-		for (uint32_t i = 0; i < n_var; i++) {
-			local[i] = variant_begin - ds->v_begin + i;
-		}
+	const uint32_t flags = pgh::kVariantRowsExpand | (increasing ? pgh::kVariantRowsIncreasing : 0u);
+	const int rc = call.rows.ResolveAndUpload(ds, variant_begin, n_var, vidx, flags, st, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
 	}
-	PGH_HIP(call.d_list.Alloc(sizeof(uint32_t) * static_cast<size_t>(n_var)), "hipMalloc(ld band variant list)");
-	PGH_HIP(hipMemcpyAsync(call.d_list.p, local.data(), sizeof(uint32_t) * static_cast<size_t>(n_var),
-	                       hipMemcpyHostToDevice, st),
-	        "ld band variant list upload");
 	call.op.view = ds->View();
-	call.op.list = call.d_list.As<uint32_t>();
+	call.op.list = call.rows.Device();
 	call.op.n_var = n_var;
 	call.op.mask2 = subset ? subset->d_mask2 : nullptr;
 	return PGH_OK;

@@ -268,16 +268,31 @@ struct ListCut {
 int CutList(const pgh_dataset *g, uint32_t n, const uint32_t *vidx, ListCut &cut, char *errbuf) {
 	cut.pos.assign(g->shards.size(), {});
 	cut.idx.assign(g->shards.size(), {});
-	for (uint32_t i = 0; i < n; i++) {
-		if (vidx[i] < g->v_begin || vidx[i] >= g->v_end) {
-			SetErr(errbuf, "variant index outside the resident range");
-			return PGH_ERR_ARG;
-		}
+	const int rc = CheckVariantList(g, n, vidx, errbuf);
+	for (uint32_t i = 0; rc == PGH_OK && i < n; i++) {
 		const size_t k = ShardOf(g, vidx[i]);
 		cut.pos[k].push_back(i);
 		cut.idx[k].push_back(vidx[i]);
 	}
-	return PGH_OK;
+	return rc;
+}
+
+//! A call's (variant_begin, n, vidx) checked, cut by shard, and fn(k, begin, count, list, pos, eb) run on the thread of
+//! every shard that has a share: of a range its slice [begin, begin + count) (list and pos are null), of a list its
+//! `count` entries `list`, of which entry i stands at pos[i] in the caller's list.
+template <class Fn>
+int ForShardShares(const pgh_dataset *g, uint32_t variant_begin, uint32_t n, const uint32_t *vidx, char *errbuf, Fn fn) {
+	ListCut cut;
+	const int rc = vidx ? CutList(g, n, vidx, cut, errbuf) : CheckRange(g, variant_begin, variant_begin + n, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
+	}
+	return ForShards(g, errbuf, [&](size_t k, char *eb) {
+		const uint32_t lo = std::max(variant_begin, g->shards[k]->v_begin), hi = std::min(variant_begin + n, g->shards[k]->v_end);
+		const uint32_t begin = vidx ? 0 : lo, count = vidx ? static_cast<uint32_t>(cut.idx[k].size()) : lo < hi ? hi - lo : 0;
+		return count ? fn(k, begin, count, vidx ? cut.idx[k].data() : nullptr, vidx ? cut.pos[k].data() : nullptr, eb)
+		             : static_cast<int>(PGH_OK);
+	});
 }
 
 //! A reusable barrier for the K shard threads of one call.
@@ -663,36 +678,18 @@ int UnpackRange(const pgh_dataset *g, const pgh_subset *ss, uint32_t v_begin, ui
 template <class T, class Call>
 static int PerVariantRows(const pgh_dataset *g, uint32_t variant_begin, uint32_t n_variants, const uint32_t *vidx,
                           T *out, size_t row_elems, char *errbuf, Call call) {
-	if (!vidx) {
-		int rc = CheckRange(g, variant_begin, variant_begin + n_variants, errbuf);
-		if (rc != PGH_OK) {
-			return rc;
-		}
-		const uint32_t v_end = variant_begin + n_variants;
-		return ForShards(g, errbuf, [&](size_t k, char *eb) {
-			const pgh_dataset *s = g->shards[k];
-			const uint32_t lo = std::max(variant_begin, s->v_begin), hi = std::min(v_end, s->v_end);
-			return lo < hi ? call(k, lo, hi - lo, nullptr, out + static_cast<size_t>(lo - variant_begin) * row_elems, eb)
-			               : static_cast<int>(PGH_OK);
-		});
-	}
-	ListCut cut;
-	int rc = CutList(g, n_variants, vidx, cut, errbuf);
-	if (rc != PGH_OK) {
-		return rc;
-	}
-	return ForShards(g, errbuf, [&](size_t k, char *eb) {
-		const uint32_t n_k = static_cast<uint32_t>(cut.idx[k].size());
-		if (n_k == 0) {
-			return static_cast<int>(PGH_OK);
+	return ForShardShares(g, variant_begin, n_variants, vidx, errbuf,
+	                      [&](size_t k, uint32_t begin, uint32_t n_k, const uint32_t *list, const uint32_t *pos, char *eb) {
+		if (!list) { // a slice's rows are contiguous in `out`
+			return call(k, begin, n_k, nullptr, out + static_cast<size_t>(begin - variant_begin) * row_elems, eb);
 		}
 		std::vector<T> tmp(static_cast<size_t>(n_k) * row_elems);
-		int rck = call(k, 0, n_k, cut.idx[k].data(), tmp.data(), eb);
+		int rck = call(k, 0, n_k, list, tmp.data(), eb);
 		if (rck != PGH_OK) {
 			return rck;
 		}
 		for (uint32_t i = 0; i < n_k; i++) {
-			std::memcpy(out + static_cast<size_t>(cut.pos[k][i]) * row_elems, &tmp[static_cast<size_t>(i) * row_elems],
+			std::memcpy(out + static_cast<size_t>(pos[i]) * row_elems, &tmp[static_cast<size_t>(i) * row_elems],
 			            sizeof(T) * row_elems);
 		}
 		return static_cast<int>(PGH_OK);
@@ -814,33 +811,15 @@ int SampleCounts(const pgh_dataset *g, const pgh_subset *ss, uint32_t variant_be
 		return rc;
 	}
 	const size_t n_out = ss ? ss->n_out : g->sample_ct;
-	ListCut cut;
-	if (vidx) {
-		rc = CutList(g, n_var, vidx, cut, errbuf);
-	} else {
-		rc = CheckRange(g, variant_begin, variant_begin + n_var, errbuf);
-	}
-	if (rc != PGH_OK || n_out == 0) { // an empty subset: nothing to write (a shard would refuse its null buffer)
-		return rc;
-	}
 	std::vector<std::vector<uint32_t>> part(g->shards.size());
-	rc = ForShards(g, errbuf, [&](size_t k, char *eb) {
-		const pgh_dataset *s = g->shards[k];
-		uint32_t vb = 0, n_k = 0;
-		const uint32_t *list = nullptr;
-		if (vidx) {
-			n_k = static_cast<uint32_t>(cut.idx[k].size());
-			list = cut.idx[k].data();
-		} else {
-			const uint32_t lo = std::max(variant_begin, s->v_begin), hi = std::min(variant_begin + n_var, s->v_end);
-			vb = lo;
-			n_k = lo < hi ? hi - lo : 0;
-		}
-		if (n_k == 0) {
+	rc = ForShardShares(g, variant_begin, n_var, vidx, errbuf,
+	                    [&](size_t k, uint32_t begin, uint32_t n_k, const uint32_t *list, const uint32_t *, char *eb) {
+		if (n_out == 0) { // an empty subset: nothing to write (a shard would refuse its null buffer)
 			return static_cast<int>(PGH_OK);
 		}
 		part[k].resize(4 * n_out);
-		return pgh_sample_counts(s, PartOf(ss, k), vb, n_k, list, reinterpret_cast<uint32_t(*)[4]>(part[k].data()), eb);
+		return pgh_sample_counts(g->shards[k], PartOf(ss, k), begin, n_k, list,
+		                         reinterpret_cast<uint32_t(*)[4]>(part[k].data()), eb);
 	});
 	if (rc != PGH_OK) {
 		return rc;
@@ -1122,9 +1101,8 @@ int LdPairs(const pgh_dataset *g, const pgh_subset *ss, uint32_t n_pairs, const 
 	std::vector<uint32_t> x_pos, x_a, x_b;
 	for (uint32_t p = 0; p < n_pairs; p++) {
 		const uint32_t va = vidx_a[p], vb = vidx_b[p];
-		if (va < g->v_begin || va >= g->v_end || vb < g->v_begin || vb >= g->v_end) {
-			SetErr(errbuf, "variant index outside the resident range");
-			return PGH_ERR_ARG;
+		if (!VariantPairInside(g, va, vb)) {
+			return RefuseVariantPair(g, p, va, vb, errbuf);
 		}
 		const size_t ka = ShardOf(g, va), kb = ShardOf(g, vb);
 		if (ka == kb) {

@@ -390,19 +390,17 @@ uint32_t ScoreSparseSlices() {
 	return 0;
 }
 
-// pgh_score_sparse on one sparse-resident dataset, after the argument checks (n_scored >= 1).
-int ScoreSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t n_scored, const uint32_t *vidx,
+// pgh_score_sparse on one sparse-resident dataset, after the argument checks (n_scored >= 1); local: the rows scored.
+int ScoreSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t n_scored, const uint32_t *local,
                    const double *weights, const uint8_t *flip, uint32_t n_cols, int mode, double *score_sum,
                    double *dosage_sum, uint32_t *allele_ct, char *errbuf) {
 	PGH_ENTER(ds);
 	const uint32_t N = ds->sample_ct;
 	hipStream_t st = PghThreadStream();
-	std::vector<uint32_t> local(n_scored);
 	uint32_t l_min = UINT32_MAX, l_max = 0;
 	uint64_t dense_listed = 0;
 	for (uint32_t i = 0; i < n_scored; i++) {
-		const uint32_t l = vidx[i] - ds->v_begin;
-		local[i] = l;
+		const uint32_t l = local[i];
 		l_min = std::min(l_min, l);
 		l_max = std::max(l_max, l);
 		dense_listed += ds->sp_dense_before[l + 1] - ds->sp_dense_before[l];
@@ -444,7 +442,7 @@ int ScoreSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t n_s
 	std::vector<double> h_score(static_cast<size_t>(N) * n_cols), h_dos(track ? N : 0);
 	std::vector<uint32_t> h_ac(N);
 	HostSourceFence fence(st); // local and the caller's arrays feed asynchronous uploads, the three above take downloads
-	PGH_HIP(hipMemcpyAsync(d_vlist, local.data(), 4ull * n_scored, hipMemcpyHostToDevice, st), "score_sparse upload");
+	PGH_HIP(hipMemcpyAsync(d_vlist, local, 4ull * n_scored, hipMemcpyHostToDevice, st), "score_sparse upload");
 	PGH_HIP(hipMemcpyAsync(d_w, weights, 8ull * n_scored * n_cols, hipMemcpyHostToDevice, st), "score_sparse upload");
 	if (flip) {
 		PGH_HIP(hipMemcpyAsync(d_flip, flip, n_scored, hipMemcpyHostToDevice, st), "score_sparse upload");
@@ -517,15 +515,13 @@ extern "C" int pgh_score_sparse(const pgh_dataset *ds, const pgh_subset *subset,
 		SetErr(errbuf, "n_cols must be between 1 and 4096");
 		return PGH_ERR_ARG;
 	}
-	const int rc = CheckSubset(ds, subset, errbuf);
+	VariantRows rows; // host list only: it goes up with the call's other arrays, behind ScoreSparseOne's fence
+	int rc = CheckSubset(ds, subset, errbuf);
+	if (rc == PGH_OK) {
+		rc = rows.Resolve(ds, 0, n_scored, vidx, pgh::kVariantRowsListOnly, errbuf);
+	}
 	if (rc != PGH_OK) {
 		return rc;
-	}
-	for (uint32_t i = 0; i < n_scored; i++) {
-		if (vidx[i] < ds->v_begin || vidx[i] >= ds->v_end) {
-			SetErr(errbuf, "scored variant index outside the resident range");
-			return PGH_ERR_ARG;
-		}
 	}
 	const size_t total = static_cast<size_t>(n_scored) * n_cols;
 	for (size_t j = 0; j < total; j++) {
@@ -544,6 +540,6 @@ extern "C" int pgh_score_sparse(const pgh_dataset *ds, const pgh_subset *subset,
 		std::fill_n(allele_ct, n_out, 0u);
 		return PGH_OK;
 	}
-	return ScoreSparseOne(ds, subset, n_scored, vidx, weights, flip, n_cols, mode, score_sum, dosage_sum, allele_ct,
-	                      errbuf);
+	return ScoreSparseOne(ds, subset, n_scored, rows.local.data(), weights, flip, n_cols, mode, score_sum, dosage_sum,
+	                      allele_ct, errbuf);
 }
