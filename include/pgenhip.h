@@ -644,6 +644,36 @@ int pgh_glm_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_b
 int pgh_glm_score_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                          const double *phenotype, uint32_t n_covar, const double *covariates,
                          pgh_glm_row *out, char *errbuf);
+/* The logistic score test of every variant of [v_begin, v_end) of a DENSE-RESIDENT dataset (pgh_open) for n_pheno
+ * case/control phenotypes in one call: one null fit per phenotype, then one pass over the 2-bit rows per block of
+ * phenotypes, as an FP64 matrix product on the matrix cores.  phenotypes, covariates, subset, the range and the layout
+ * of `out` are pgh_glm_multi's: out[(v - v_begin) * n_pheno + p] is phenotype p's row for variant v.
+ *
+ * Row contract.  Each row is the row that pgh_glm_score_sparse's contract above defines, for that phenotype alone,
+ * with d = x: the dense route has no base code.  The null model, its 1e-10 stopping rule, the pivot rule and the
+ * 25-step cap, S, M, N, H_N, g_N, c, A, U0, t, V, U, beta, se, stat and p, and the order of the decisions
+ * (TOO_FEW_SAMPLES; CONST_ALLELE; the null model's status; SINGULAR_MATRIX on the augmented Cholesky; otherwise
+ * fitted) are the ones defined there; firth is 0.  obs_ct, a1_freq, TOO_FEW_SAMPLES and CONST_ALLELE equal pgh_glm's
+ * with model = PGH_GLM_LOGISTIC for the same file, bit for bit.  A null fit that fails decides only its own
+ * phenotype's rows.  Against pgh_glm_score_sparse over the same file the estimates agree to rounding (1e-9 on their
+ * scale), with the same errcodes.
+ *
+ * A row is a function of its variant's calls, its own phenotype, the covariates and the subset only: not of the other
+ * phenotypes of the call or its place among them, of v_begin, the variant chunk, the phenotype block, the window the
+ * dataset was opened with or the scratch budget, and the same call returns the same bytes every time.
+ *
+ * PGH_ERR_ARG, `out` untouched: everything pgh_glm_multi refuses in the shared arguments (n_pheno == 0 included); a
+ * non-NaN phenotype value other than 0.0 or 1.0 ("phenotype must be 0 or 1") or a phenotype without a case or a
+ * control ("no cases or no controls"), each followed by the phenotype's index; a sparse-resident dataset ("needs a
+ * dense-resident dataset"); a shard group (pass pgh_shard(group, k)); a dataset whose pgh_info.dosage_variant_ct is
+ * not 0 ("hardcalls only": the x^2 sums are defined on calls).  v_begin == v_end is PGH_OK.
+ *
+ * PGH_GLM_SCORE_SCRATCH_BYTES (environment, read at every call, default 6 GiB) bounds the device scratch that grows
+ * with the phenotypes and variants in flight; the result does not depend on it.
+ * Not offered: saddlepoint or Firth p-values over this route, dosage tracks, shard groups, a table function. */
+int pgh_glm_score_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                        uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
+                        pgh_glm_row *out, char *errbuf);
 /* pgh_glm_score_sparse with a SADDLEPOINT p-value beside the normal one, for the rows the normal tail serves badly:
  * rare variants under an unbalanced case / control ratio (the "fast SPA" of Dey et al. 2017: the exact cumulant
  * generating function over the row's entries, a normal term for every other sample).  Arguments, argument checks and

@@ -2,7 +2,8 @@
 // pgh_glm_multi: the same for many phenotypes in one call; pgh_glm_sparse: the linear fit over a sparse-resident
 // dataset, from its entries (glm_sparse.hip); pgh_burden_sparse: gene-set burden fits over such a dataset
 // (burden_sparse.hip); pgh_glm_score_sparse: the logistic score test over such a dataset, from its entries
-// (glm_score_sparse.hip); pgh_skat_sparse: SKAT and burden score tests of variant sets under that test's null model
+// (glm_score_sparse.hip); pgh_glm_score_multi: that test over a dense-resident dataset for many phenotypes in one
+// call, on the FP64 matrix cores (glm_score_dense.hip); pgh_skat_sparse: SKAT and burden score tests of variant sets under that test's null model
 // (skat_sparse.hip, skat_math.hpp, linalg.cpp).
 #include "api_internal.hpp"
 #include "glm.hpp"
@@ -1263,6 +1264,181 @@ int GlmScoreSparseEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_
 	return GlmScoreSparseOne(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, out, errbuf, spa);
 }
 
+// pgh_glm_score_multi: the byte budget of the scratch that grows with the phenotype block and the variant chunk (read
+// at every call; the result does not depend on it).  Three quarters of it at most go to the column block, which
+// decides how many phenotypes share a walk of the matrix; the rest bounds the chunk.  The default holds the block of
+// 64 phenotypes with 10 covariates over 500 k samples (3.3 GB).  A handful of sample-length vectors of the null fit
+// are outside it, and below one phenotype and one variant nothing shrinks further.
+constexpr uint64_t kGlmScoreScratchBytes = 6ull << 30;
+const char *const kGlmScoreScratchEnv = "PGH_GLM_SCORE_SCRATCH_BYTES";
+constexpr uint32_t kGlmScoreMultiChunk = 65536;
+
+// pgh_glm_score_multi on one dense-resident dataset, after the argument checks.  The null models are fitted phenotype
+// by phenotype by GlmScoreNullFit, as GlmScoreSparseOne fits its one: on the covariates centred over the phenotype's
+// missing-value pattern, which the phenotypes of a pattern share (GlmStage's sums and subtraction, the latter on the
+// device).  Each fit's r and w go straight into the phenotype's columns of the block (glm_score_dense.hip).
+int GlmScoreMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end, uint32_t n_pheno,
+                     const double *phenotypes, uint32_t k, const double *covariates, pgh_glm_row *out, char *errbuf) {
+	PGH_ENTER(ds);
+	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct, n_raw = ds->sample_ct;
+	const uint32_t nv_all = v_end - v_begin;
+	const uint32_t kp = pgh::GlmPadCovar(k);
+	hipStream_t st = PghThreadStream();
+
+	// the phenotypes in the order of their pattern groups, so that a pattern's covariates are centred once
+	const std::vector<std::vector<uint32_t>> groups = GlmPatternGroups(n_pheno, phenotypes, n_out);
+	std::vector<uint32_t> order, group_of(n_pheno);
+	for (uint32_t g = 0; g < groups.size(); g++) {
+		for (uint32_t p : groups[g]) {
+			order.push_back(p);
+			group_of[p] = g;
+		}
+	}
+	// sg.hz (and hz_raw): the covariates as they are
+	const GlmStaged sg = GlmStage(ds, subset, phenotypes, k, covariates, GlmCentre::kNone, true);
+
+	const uint64_t n_pad = 64ull * ((static_cast<uint64_t>(n_raw) + 63) / 64), mask_words = n_pad / 16;
+	const uint32_t ns = kp + 6, ne = (k + 1) * (k + 2) / 2 + k + 1;
+	const uint64_t budget = EnvBytes(kGlmScoreScratchEnv, kGlmScoreScratchBytes);
+	const auto block_bytes = [&](uint32_t pb) {
+		return 8ull * n_pad * pgh::GlmScoreDenseLayout(pb, k).ld + 4ull * mask_words * pb;
+	};
+	uint32_t pb_max = std::min(pgh::kGlmScoreDensePb, n_pheno);
+	while (pb_max > 1 && block_bytes(pb_max) > budget / 4 * 3) {
+		pb_max--;
+	}
+	const uint64_t per_variant = static_cast<uint64_t>(pb_max) * (8ull * (ns + ne) + sizeof(pgh_glm_row) + 4);
+	const uint64_t left = budget > block_bytes(pb_max) ? budget - block_bytes(pb_max) : 0;
+	const uint32_t chunk = static_cast<uint32_t>(
+	    std::min<uint64_t>(std::min(kGlmScoreMultiChunk, nv_all), std::max<uint64_t>(1, left / per_variant)));
+
+	const uint64_t n = n_out, nr = n_raw, c = chunk, pbm = pb_max;
+	double *d_y, *d_z0, *d_z, *d_zr0, *d_r, *d_w, *d_part, *d_hg1, *d_hg, *d_mz, *d_b, *d_sums, *d_hgn;
+	uint32_t *d_ny, *d_mask, *d_nmiss;
+	pgh_glm_row *d_rows;
+	ScratchLayout lay;
+	lay.Add(&d_y, n);
+	lay.Add(&d_z0, n * kp + 1); // one element of slack, here and in d_z, d_zr0, d_mz
+	lay.Add(&d_z, n * kp + 1);
+	lay.Add(&d_zr0, nr * kp + 1, subset != nullptr);
+	lay.Add(&d_r, nr);
+	lay.Add(&d_w, nr);
+	lay.Add(&d_part, static_cast<uint64_t>(pgh::kGlmScoreNullParts) * ne);
+	lay.Add(&d_hg1, ne);
+	lay.Add(&d_hg, pbm * ne);
+	lay.Add(&d_mz, pbm * kp + 1);
+	lay.Add(&d_ny, pbm);
+	lay.Add(&d_mask, pbm * mask_words);
+	lay.Add(&d_b, n_pad * pgh::GlmScoreDenseLayout(pb_max, k).ld);
+	lay.Add(&d_sums, pbm * c * ns);
+	lay.Add(&d_hgn, pbm * c * ne);
+	lay.Add(&d_nmiss, pbm * c);
+	lay.Add(&d_rows, pbm * c);
+	void *scratch = nullptr;
+	PGH_HIP(PghThreadScratch(lay.total, st, &scratch), "glm_score_multi scratch");
+	lay.Bind(scratch);
+	if (!subset) {
+		d_zr0 = d_z0;
+	}
+
+	// per pattern group, staged when its first phenotype comes up: |S|, the covariates' means over S and S as the
+	// kernels' sample mask (one bit per 2-bit code, raw-sample order)
+	struct GroupStage {
+		bool ready = false;
+		uint32_t n_y = 0;
+		std::vector<double> mz;
+		std::vector<uint32_t> mask;
+	};
+	std::vector<GroupStage> gs(groups.size());
+	std::vector<uint32_t> h_ny(pb_max);
+	std::vector<int> status(pb_max);
+	std::vector<pgh_glm_row> hrows(static_cast<size_t>(chunk) * pb_max);
+	HostSourceFence fence(st); // sg, gs, h_ny and the caller's phenotypes feed asynchronous uploads
+	if (kp) {
+		PGH_HIP(hipMemcpyAsync(d_z0, sg.hz.data(), 8ull * sg.hz.size(), hipMemcpyHostToDevice, st),
+		        "glm_score_multi covariate upload");
+	}
+	if (sg.raw && kp) {
+		PGH_HIP(hipMemcpyAsync(d_zr0, sg.hz_raw.data(), 8ull * sg.hz_raw.size(), hipMemcpyHostToDevice, st),
+		        "glm_score_multi covariate upload (raw order)");
+	}
+	const uint32_t *d_sel = subset ? subset->d_sel : nullptr;
+	uint32_t centred_for = UINT32_MAX; // the group d_z is centred for
+	for (uint32_t b0 = 0; b0 < n_pheno; b0 += pb_max) {
+		const uint32_t pb = std::min(pb_max, n_pheno - b0);
+		const uint32_t ld = pgh::GlmScoreDenseLayout(pb, k).ld;
+		PGH_HIP(hipMemsetAsync(d_b, 0, 8ull * n_pad * ld, st), "glm_score_multi column block clear");
+		for (uint32_t j = 0; j < pb; j++) {
+			const uint32_t p = order[b0 + j], g = group_of[p];
+			const double *y = phenotypes + static_cast<size_t>(p) * n_out;
+			GroupStage &gr = gs[g];
+			if (!gr.ready) {
+				gr.ready = true;
+				gr.mask.assign(mask_words, 0u);
+				for (uint32_t i = 0; i < n_out; i++) {
+					if (!std::isnan(y[i])) {
+						const uint32_t s = subset ? subset->sel[i] : i;
+						gr.mask[s >> 4] |= 1u << (2u * (s & 15u));
+						gr.n_y++;
+					}
+				}
+				gr.mz.assign(kp + 1, 0.0);
+				for (uint32_t jz = 0; jz < k && gr.n_y; jz++) {
+					const double *zc = covariates + static_cast<size_t>(jz) * n_out;
+					double mz = 0.0;
+					for (uint32_t i = 0; i < n_out; i++) {
+						mz += std::isnan(y[i]) ? 0.0 : zc[i];
+					}
+					gr.mz[jz] = mz / gr.n_y;
+				}
+			}
+			h_ny[j] = gr.n_y;
+			PGH_HIP(hipMemcpyAsync(d_mask + j * mask_words, gr.mask.data(), 4ull * mask_words, hipMemcpyHostToDevice, st),
+			        "glm_score_multi mask upload");
+			if (kp) {
+				PGH_HIP(hipMemcpyAsync(d_mz + static_cast<uint64_t>(j) * kp, gr.mz.data(), 8ull * kp, hipMemcpyHostToDevice, st),
+				        "glm_score_multi mean upload");
+				if (centred_for != g) {
+					PGH_HIP(pgh::LaunchGlmScoreDenseCentre(n_out, kp, d_z0, d_mz + static_cast<uint64_t>(j) * kp, d_z, st),
+					        "glm_score_multi centring kernel");
+					centred_for = g;
+				}
+			}
+			PGH_HIP(hipMemcpyAsync(d_y, y, 8ull * n_out, hipMemcpyHostToDevice, st), "glm_score_multi phenotype upload");
+			const int rc = GlmScoreNullFit(n_out, d_y, d_z, kp, k, d_sel, gr.n_y >= k + 3, d_r, d_w, d_part, d_hg1, st,
+			                               &status[j], errbuf);
+			if (rc != PGH_OK) {
+				return rc;
+			}
+			PGH_HIP(hipMemcpyAsync(d_hg + static_cast<uint64_t>(j) * ne, d_hg1, 8ull * ne, hipMemcpyDeviceToDevice, st),
+			        "glm_score_multi null model copy");
+			PGH_HIP(pgh::LaunchGlmScoreDenseColumns(n_out, d_sel, d_r, d_w, d_z, kp, k, pb, j, d_b, st),
+			        "glm_score_multi column kernel");
+		}
+		PGH_HIP(hipMemcpyAsync(d_ny, h_ny.data(), 4ull * pb, hipMemcpyHostToDevice, st), "glm_score_multi count upload");
+		for (uint32_t c0 = 0; c0 < nv_all; c0 += chunk) {
+			const uint32_t nv = std::min(chunk, nv_all - c0);
+			PGH_HIP(pgh::LaunchGlmScoreDense(ds->View(), v_begin + c0 - ds->v_begin, nv, d_mask, d_ny, pb, d_b, d_zr0, d_mz,
+			                                 kp, k, d_hg, d_sums, d_nmiss, d_hgn, st),
+			        "glm_score_multi kernels");
+			for (uint32_t j = 0; j < pb; j++) {
+				const uint64_t at = static_cast<uint64_t>(j) * nv;
+				PGH_HIP(pgh::LaunchGlmScoreSolve(nv, d_sums + at * ns, kp, k, d_hgn + at * ne, status[j], d_rows + at, st),
+				        "glm_score_multi solve kernel");
+			}
+			PGH_HIP(hipMemcpyAsync(hrows.data(), d_rows, sizeof(pgh_glm_row) * nv * pb, hipMemcpyDeviceToHost, st),
+			        "glm_score_multi rows copy");
+			PGH_HIP(hipStreamSynchronize(st), "glm_score_multi sync");
+			for (uint32_t i = 0; i < nv; i++) {
+				for (uint32_t j = 0; j < pb; j++) {
+					out[static_cast<size_t>(c0 + i) * n_pheno + order[b0 + j]] = hrows[static_cast<size_t>(j) * nv + i];
+				}
+			}
+		}
+	}
+	return PGH_OK;
+}
+
 } // namespace
 
 extern "C" int pgh_glm_score_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
@@ -1285,6 +1461,35 @@ extern "C" int pgh_glm_score_sparse_spa(const pgh_dataset *ds, const pgh_subset 
 	}
 	const GlmScoreSpaArgs spa = {spa_cutoff, p_spa, spa_state};
 	return GlmScoreSparseEntry(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, out, &spa, errbuf);
+}
+
+extern "C" int pgh_glm_score_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                                   uint32_t n_pheno, const double *phenotypes, uint32_t n_covar,
+                                   const double *covariates, pgh_glm_row *out, char *errbuf) {
+	PGH_ONE_DEVICE(ds);
+	PGH_DENSE_ROWS(ds);
+	const int rc = GlmCheckCommon(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, PGH_GLM_LOGISTIC,
+	                              out, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
+	}
+	if (ds->dos_rows) {
+		SetErr(errbuf, "hardcalls only: the dataset holds " + std::to_string(ds->dos_rows) + " dosage tracks");
+		return PGH_ERR_ARG;
+	}
+	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct;
+	for (uint32_t p = 0; p < n_pheno; p++) {
+		char why[PGH_ERRBUF_LEN];
+		why[0] = '\0';
+		if (GlmCheckBinary(phenotypes + static_cast<size_t>(p) * n_out, n_out, why) != PGH_OK) {
+			SetErr(errbuf, std::string(why) + " (phenotype " + std::to_string(p) + ")");
+			return PGH_ERR_ARG;
+		}
+	}
+	if (v_end == v_begin) {
+		return PGH_OK;
+	}
+	return GlmScoreMultiOne(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, errbuf);
 }
 
 extern "C" int pgh_burden_sparse(const pgh_dataset *ds, const pgh_subset *subset, const double *phenotype,

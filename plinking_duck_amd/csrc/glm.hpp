@@ -166,6 +166,37 @@ hipError_t LaunchGlmScoreSolve(uint32_t nv, const double *sums, uint32_t kp, uin
                                int null_status, pgh_glm_row *rows, hipStream_t stream,
                                const GlmScoreSpaOut &spa = GlmScoreSpaOut());
 
+// ---- pgh_glm_score_multi (glm_score_dense.hip): the score test over 2-bit rows for a block of phenotypes ----
+// At most kGlmScoreDensePb phenotypes share a column block; the contraction's workgroup owns kGlmScoreDenseTileV
+// variants x kGlmScoreDenseTileC columns.  No number depends on either, on the block's size or on the chunk.
+constexpr uint32_t kGlmScoreDensePb = 64;
+constexpr uint32_t kGlmScoreDenseTileV = 128;
+constexpr uint32_t kGlmScoreDenseTileC = 64;
+// The column block of pb phenotypes: ld doubles per sample row, the first n_xblocks 16-column blocks taken against x
+// (phenotype j: r, w, w Zt_1 .. w Zt_k from column j (k + 2)), the rest against x^2 (phenotype j: w at
+// 16 n_xblocks + j).  It holds 64 * ceil(sample_ct / 64) rows in RAW sample order.
+struct GlmScoreDenseCols {
+	uint32_t n_xblocks, ld;
+};
+GlmScoreDenseCols GlmScoreDenseLayout(uint32_t pb, uint32_t k);
+// z[i][j] = z0[i][j] - mz[j] (n_out x kp; mz: kp doubles on the device)
+hipError_t LaunchGlmScoreDenseCentre(uint32_t n_out, uint32_t kp, const double *z0, const double *mz, double *z,
+                                     hipStream_t stream);
+// Phenotype j's columns of the block `b` of pb phenotypes (ALL ZERO before its first phenotype is written), from
+// LaunchGlmScoreNull's r_raw / w_raw and the centred covariates z (output-sample order): 0.0 outside S or the subset.
+hipError_t LaunchGlmScoreDenseColumns(uint32_t n_out, const uint32_t *sel, const double *r_raw, const double *w_raw,
+                                      const double *z, uint32_t kp, uint32_t k, uint32_t pb, uint32_t j, double *b,
+                                      hipStream_t stream);
+// For the local rows v0 + i (i < nv) of `view` and the block's phenotypes p < pb: sums[p][i][kp + 6] and hgn[p][i] in
+// LaunchGlmScoreSparse's layouts, ready for LaunchGlmScoreSolve phenotype by phenotype.  mask: per phenotype
+// 4 * ceil(sample_ct / 64) words, bit 2 (s & 15) of word s >> 4 set iff raw sample s is in S_p; n_y[p] = |S_p|.
+// z0: the UNCENTRED covariates in raw-sample order (sample_ct x kp), mz: pb x kp means (LaunchGlmScoreDenseCentre's),
+// hg: pb x (entries of hg).  nmiss: pb x nv words of scratch.
+hipError_t LaunchGlmScoreDense(const RowView &view, uint32_t v0, uint32_t nv, const uint32_t *mask, const uint32_t *n_y,
+                               uint32_t pb, const double *b, const double *z0, const double *mz, uint32_t kp,
+                               uint32_t k, const double *hg, double *sums, uint32_t *nmiss, double *hgn,
+                               hipStream_t stream);
+
 // ---- pgh_glm_score_sparse_spa (glm_score_spa.hip): saddlepoint p-values of the score test's rows ----
 // Bytes of the private stash one workgroup of the workgroup form needs for `sample_ct` samples (a pair of doubles each).
 inline uint64_t GlmScoreSpaStashPerGroup(uint32_t sample_ct) {

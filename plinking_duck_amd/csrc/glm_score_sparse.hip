@@ -33,22 +33,6 @@ namespace {
 constexpr int kBlock = kTeamBlock;
 constexpr int kMaxQ = PGH_GLM_MAX_COVAR + 2; // intercept + covariates + genotype
 
-// Entry e of the packed set {H: sum w Zt_a Zt_b (a <= b <= k, row-major upper), then g: sum r Zt_a (a <= k)} as
-// columns of a list row [Zt_0..Zt_k, w, r]: its term is row[ew] * row[ea] * row[eb] (eb = 0, the 1.0, for g).
-// ea < 0: there is no such entry.
-__device__ __forceinline__ void ScoreOwnedEntry(int e, int k, int *ea, int *eb, int *ew) {
-	const int q1 = k + 1, nh = q1 * (q1 + 1) / 2;
-	*ea = *eb = *ew = -1;
-	if (e < nh) {
-		PackedUpper(e, q1, ea, eb);
-		*ew = k + 1;
-	} else if (e < nh + q1) {
-		*ea = e - nh;
-		*eb = 0;
-		*ew = k + 2;
-	}
-}
-
 // ---------------------------------------------------------------------------
 // the null model: one Newton evaluation at beta
 // ---------------------------------------------------------------------------

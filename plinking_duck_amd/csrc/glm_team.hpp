@@ -46,6 +46,22 @@ __device__ __forceinline__ void PackedUpper(int e, int q, int *a, int *b) {
 	*b = row + e;
 }
 
+// The score test's owned entries (glm_score_sparse.hip, glm_score_dense.hip).  Entry e of the packed set {H: sum w
+// Zt_a Zt_b (a <= b <= k, row-major upper), then g: sum r Zt_a (a <= k)} as columns of a list row [Zt_0..Zt_k, w, r]:
+// its term is row[ew] * row[ea] * row[eb] (eb = 0, the 1.0, for g).  ea < 0: there is no such entry.
+__device__ __forceinline__ void ScoreOwnedEntry(int e, int k, int *ea, int *eb, int *ew) {
+	const int q1 = k + 1, nh = q1 * (q1 + 1) / 2;
+	*ea = *eb = *ew = -1;
+	if (e < nh) {
+		PackedUpper(e, q1, ea, eb);
+		*ew = k + 1;
+	} else if (e < nh + q1) {
+		*ea = e - nh;
+		*eb = 0;
+		*ew = k + 2;
+	}
+}
+
 // The ordered-list step, part one.  Returns how many threads before this one in thread order have `take` set, and in
 // *total how many of the team have: the takers' ranks are 0 .. *total - 1 in thread order, and *total is the same on
 // every thread, so code under `if (*total)` is team-uniform and may hold a barrier.
