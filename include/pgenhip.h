@@ -670,7 +670,8 @@ int pgh_glm_score_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32
  *
  * PGH_GLM_SCORE_SCRATCH_BYTES (environment, read at every call, default 6 GiB) bounds the device scratch that grows
  * with the phenotypes and variants in flight; the result does not depend on it.
- * Not offered: saddlepoint or Firth p-values over this route, dosage tracks, shard groups, a table function. */
+ * Saddlepoint p-values over this route: pgh_glm_score_multi_spa.  Not offered: Firth p-values over this route, dosage
+ * tracks, shard groups, a table function. */
 int pgh_glm_score_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                         uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
                         pgh_glm_row *out, char *errbuf);
@@ -715,6 +716,38 @@ int pgh_glm_score_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_
 int pgh_glm_score_sparse_spa(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                              const double *phenotype, uint32_t n_covar, const double *covariates, double spa_cutoff,
                              pgh_glm_row *out, double *p_spa, uint8_t *spa_state, char *errbuf);
+/* pgh_glm_score_multi with pgh_glm_score_sparse_spa's SADDLEPOINT p-value beside the normal one, for every (variant,
+ * phenotype) row of the dense route.  Arguments, argument checks and error texts are pgh_glm_score_multi's.  In
+ * addition spa_cutoff must be at least 0.1 (+infinity: never apply it; NaN or a smaller value is PGH_ERR_ARG,
+ * "spa_cutoff must be at least 0.1"), and p_spa and spa_state must not be NULL ("null p_spa or spa_state"); they have
+ * out's layout, element (v - v_begin) * n_pheno + p.  On any error all three outputs are untouched.  The refusals are the dense route's: a
+ * sparse-resident dataset, a shard group, a dataset with dosage tracks.
+ *
+ * out is pgh_glm_score_multi's result for the same arguments bit for bit; its p stays the normal p-value.  spa_state
+ * and p_spa mean what they mean for pgh_glm_score_sparse_spa: 0 = not applied (the row is not fitted: p_spa NaN; or
+ * |stat| <= spa_cutoff: p_spa = out.p bit for bit), 1 = applied (p_spa is the saddlepoint p), 2 = attempted and failed
+ * (p_spa = out.p bit for bit).
+ *
+ * Definition, in the notation of pgh_glm_score_sparse and pgh_glm_score_sparse_spa with d = x.  n0 and n2 are the
+ * hom-ref and hom-alt calls among N, the phenotype's called samples; b = 2 if n2 > n0, otherwise 0 (an integer rule).
+ * E = the samples of N with x != b.  gt_i = x_i - Zt_i t for i in N, which does not depend on b (shifting x by b shifts
+ * t_0 by b); mu_i = r_i > 0 ? 1 - r_i : -r_i; V_E = sum_E w gt^2 and V_rest = max(V - V_E, 0).  A fitted row always has
+ * a called sample with x = b (otherwise it would be CONST_ALLELE), so the sparse route's V_rest = 0 by rule does not
+ * arise here.  Everything else is pgh_glm_score_sparse_spa's contract word for word: K, K', K'' with one
+ * exp(-|gt s|) per entry; the safeguarded Newton iteration for q+ and q- = +-|U| from |q| / V with the 1/sqrt(V) step
+ * cap that doubles; the three stopping rules and the cap of 64 evaluations; omega, nu and the two tails; the state-2
+ * conditions.  Membership in S comes from the phenotype's non-NaN values and the subset.
+ *
+ * Against pgh_glm_score_sparse_spa over the same file, a row whose sparse base code equals b (and is not 3) has the
+ * same E: the states agree and p_spa agrees to rounding.
+ *
+ * A row's (out, p_spa, spa_state) is a function of its variant's calls, its own phenotype, the covariates, the subset
+ * and spa_cutoff only: not of the other phenotypes of the call or its place among them, of v_begin, the variant
+ * chunk, the phenotype block, PGH_GLM_SCORE_SCRATCH_BYTES (which here also bounds the saddlepoint kernel's scratch) or
+ * the grid, and the same call returns the same bytes every time. */
+int pgh_glm_score_multi_spa(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                            uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
+                            double spa_cutoff, pgh_glm_row *out, double *p_spa, uint8_t *spa_state, char *errbuf);
 /* Gene-set BURDEN tests over a SPARSE-RESIDENT dataset (pgh_open_sparse), from the variants' entries: per set, the
  * variants are collapsed into one weighted burden per sample and the phenotype is regressed on it (linear).
  *

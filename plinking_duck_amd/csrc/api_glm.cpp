@@ -1199,6 +1199,19 @@ int GlmCheckBinary(const double *phenotype, uint32_t n_out, char *errbuf) {
 	return PGH_OK;
 }
 
+// pgh_glm_score_sparse_spa's and pgh_glm_score_multi_spa's own arguments.
+int GlmCheckSpa(double spa_cutoff, const double *p_spa, const uint8_t *spa_state, char *errbuf) {
+	if (!(spa_cutoff >= 0.1)) { // (NaN too)
+		SetErr(errbuf, "spa_cutoff must be at least 0.1");
+		return PGH_ERR_ARG;
+	}
+	if (!p_spa || !spa_state) {
+		SetErr(errbuf, "null p_spa or spa_state");
+		return PGH_ERR_ARG;
+	}
+	return PGH_OK;
+}
+
 // The set arguments that pgh_burden_sparse and pgh_skat_sparse share (out: the caller's rows).
 int GlmCheckSets(const pgh_dataset *ds, uint32_t n_sets, const uint64_t *set_off, const uint32_t *set_vidx,
                  const double *weight, const void *out, char *errbuf) {
@@ -1277,8 +1290,14 @@ constexpr uint32_t kGlmScoreMultiChunk = 65536;
 // by phenotype by GlmScoreNullFit, as GlmScoreSparseOne fits its one: on the covariates centred over the phenotype's
 // missing-value pattern, which the phenotypes of a pattern share (GlmStage's sums and subtraction, the latter on the
 // device).  Each fit's r and w go straight into the phenotype's columns of the block (glm_score_dense.hip).
+// spa != null (pgh_glm_score_multi_spa): after a block's chunk of rows, GlmScoreDenseSpaKernel replaces the p-value of
+// the rows beyond the cutoff.  Its workgroups' stashes take up to three quarters of what the budget leaves after the
+// column block (at least one stash, at most four workgroups per compute unit: the time of the kernel's iteration
+// falls with their number); [t, U, V], p_spa and the state per row join the chunk's bytes.  spa == null runs the launches it ran before
+// there was a saddlepoint path.
 int GlmScoreMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end, uint32_t n_pheno,
-                     const double *phenotypes, uint32_t k, const double *covariates, pgh_glm_row *out, char *errbuf) {
+                     const double *phenotypes, uint32_t k, const double *covariates, pgh_glm_row *out, char *errbuf,
+                     const GlmScoreSpaArgs *spa = nullptr) {
 	PGH_ENTER(ds);
 	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct, n_raw = ds->sample_ct;
 	const uint32_t nv_all = v_end - v_begin;
@@ -1307,8 +1326,22 @@ int GlmScoreMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v
 	while (pb_max > 1 && block_bytes(pb_max) > budget / 4 * 3) {
 		pb_max--;
 	}
-	const uint64_t per_variant = static_cast<uint64_t>(pb_max) * (8ull * (ns + ne) + sizeof(pgh_glm_row) + 4);
-	const uint64_t left = budget > block_bytes(pb_max) ? budget - block_bytes(pb_max) : 0;
+	const uint64_t per_variant =
+	    static_cast<uint64_t>(pb_max) * (8ull * (ns + ne) + sizeof(pgh_glm_row) + 4 + (spa ? 8ull * (kp + 3) + 8 + 1 : 0));
+	uint64_t left = budget > block_bytes(pb_max) ? budget - block_bytes(pb_max) : 0;
+	const uint64_t per_group = pgh::GlmScoreSpaStashPerGroup(n_raw);
+	uint32_t n_groups = 0;
+	if (spa) {
+		int device = 0, cus = 0;
+		PGH_HIP(hipGetDevice(&device), "glm_score_multi_spa device");
+		PGH_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device),
+		        "glm_score_multi_spa device attribute");
+		const uint64_t rows_all = static_cast<uint64_t>(std::min(kGlmScoreMultiChunk, nv_all)) * pb_max;
+		n_groups = static_cast<uint32_t>(std::max<uint64_t>(
+		    1, std::min<uint64_t>(std::min<uint64_t>(rows_all, 4ull * static_cast<uint32_t>(std::max(cus, 1))),
+		                          left / 4 * 3 / per_group)));
+		left = left > per_group * n_groups ? left - per_group * n_groups : 0;
+	}
 	const uint32_t chunk = static_cast<uint32_t>(
 	    std::min<uint64_t>(std::min(kGlmScoreMultiChunk, nv_all), std::max<uint64_t>(1, left / per_variant)));
 
@@ -1334,6 +1367,14 @@ int GlmScoreMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v
 	lay.Add(&d_hgn, pbm * c * ne);
 	lay.Add(&d_nmiss, pbm * c);
 	lay.Add(&d_rows, pbm * c);
+	pgh::GlmScoreSpaOut so;
+	uint8_t *d_stash = nullptr;
+	if (spa) {
+		lay.Add(&so.t, pbm * c * (kp + 3));
+		lay.Add(&so.p_spa, pbm * c);
+		lay.Add(&so.state, pbm * c);
+		lay.Add(&d_stash, per_group * n_groups);
+	}
 	void *scratch = nullptr;
 	PGH_HIP(PghThreadScratch(lay.total, st, &scratch), "glm_score_multi scratch");
 	lay.Bind(scratch);
@@ -1353,6 +1394,8 @@ int GlmScoreMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v
 	std::vector<uint32_t> h_ny(pb_max);
 	std::vector<int> status(pb_max);
 	std::vector<pgh_glm_row> hrows(static_cast<size_t>(chunk) * pb_max);
+	std::vector<double> hp_spa(spa ? hrows.size() : 0);
+	std::vector<uint8_t> hstate(spa ? hrows.size() : 0);
 	HostSourceFence fence(st); // sg, gs, h_ny and the caller's phenotypes feed asynchronous uploads
 	if (kp) {
 		PGH_HIP(hipMemcpyAsync(d_z0, sg.hz.data(), 8ull * sg.hz.size(), hipMemcpyHostToDevice, st),
@@ -1423,15 +1466,36 @@ int GlmScoreMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v
 			        "glm_score_multi kernels");
 			for (uint32_t j = 0; j < pb; j++) {
 				const uint64_t at = static_cast<uint64_t>(j) * nv;
-				PGH_HIP(pgh::LaunchGlmScoreSolve(nv, d_sums + at * ns, kp, k, d_hgn + at * ne, status[j], d_rows + at, st),
+				pgh::GlmScoreSpaOut soj;
+				if (spa) {
+					soj.t = so.t + at * (kp + 3);
+					soj.p_spa = so.p_spa + at;
+					soj.state = so.state + at;
+				}
+				PGH_HIP(pgh::LaunchGlmScoreSolve(nv, d_sums + at * ns, kp, k, d_hgn + at * ne, status[j], d_rows + at, st, soj),
 				        "glm_score_multi solve kernel");
 			}
 			PGH_HIP(hipMemcpyAsync(hrows.data(), d_rows, sizeof(pgh_glm_row) * nv * pb, hipMemcpyDeviceToHost, st),
 			        "glm_score_multi rows copy");
+			if (spa) {
+				PGH_HIP(pgh::LaunchGlmScoreDenseSpa(ds->View(), v_begin + c0 - ds->v_begin, nv, d_mask, pb, d_b, d_zr0, d_mz, kp,
+				                                    k, d_sums, d_rows, so.t, spa->cutoff, n_groups, d_stash, so.p_spa,
+				                                    so.state, st),
+				        "glm_score_multi_spa kernel");
+				PGH_HIP(hipMemcpyAsync(hp_spa.data(), so.p_spa, 8ull * nv * pb, hipMemcpyDeviceToHost, st),
+				        "glm_score_multi_spa p copy");
+				PGH_HIP(hipMemcpyAsync(hstate.data(), so.state, static_cast<size_t>(nv) * pb, hipMemcpyDeviceToHost, st),
+				        "glm_score_multi_spa state copy");
+			}
 			PGH_HIP(hipStreamSynchronize(st), "glm_score_multi sync");
 			for (uint32_t i = 0; i < nv; i++) {
 				for (uint32_t j = 0; j < pb; j++) {
-					out[static_cast<size_t>(c0 + i) * n_pheno + order[b0 + j]] = hrows[static_cast<size_t>(j) * nv + i];
+					const size_t to = static_cast<size_t>(c0 + i) * n_pheno + order[b0 + j], from = static_cast<size_t>(j) * nv + i;
+					out[to] = hrows[from];
+					if (spa) {
+						spa->p_spa[to] = hp_spa[from];
+						spa->state[to] = hstate[from];
+					}
 				}
 			}
 		}
@@ -1451,21 +1515,20 @@ extern "C" int pgh_glm_score_sparse_spa(const pgh_dataset *ds, const pgh_subset 
                                         uint32_t v_end, const double *phenotype, uint32_t n_covar,
                                         const double *covariates, double spa_cutoff, pgh_glm_row *out, double *p_spa,
                                         uint8_t *spa_state, char *errbuf) {
-	if (!(spa_cutoff >= 0.1)) { // (NaN too)
-		SetErr(errbuf, "spa_cutoff must be at least 0.1");
-		return PGH_ERR_ARG;
-	}
-	if (!p_spa || !spa_state) {
-		SetErr(errbuf, "null p_spa or spa_state");
-		return PGH_ERR_ARG;
+	const int rc = GlmCheckSpa(spa_cutoff, p_spa, spa_state, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
 	}
 	const GlmScoreSpaArgs spa = {spa_cutoff, p_spa, spa_state};
 	return GlmScoreSparseEntry(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, out, &spa, errbuf);
 }
 
-extern "C" int pgh_glm_score_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
-                                   uint32_t n_pheno, const double *phenotypes, uint32_t n_covar,
-                                   const double *covariates, pgh_glm_row *out, char *errbuf) {
+namespace {
+
+// pgh_glm_score_multi and pgh_glm_score_multi_spa (spa != null) after the latter's own argument checks.
+int GlmScoreMultiEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                       uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
+                       pgh_glm_row *out, const GlmScoreSpaArgs *spa, char *errbuf) {
 	PGH_ONE_DEVICE(ds);
 	PGH_DENSE_ROWS(ds);
 	const int rc = GlmCheckCommon(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, PGH_GLM_LOGISTIC,
@@ -1489,7 +1552,27 @@ extern "C" int pgh_glm_score_multi(const pgh_dataset *ds, const pgh_subset *subs
 	if (v_end == v_begin) {
 		return PGH_OK;
 	}
-	return GlmScoreMultiOne(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, errbuf);
+	return GlmScoreMultiOne(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, errbuf, spa);
+}
+
+} // namespace
+
+extern "C" int pgh_glm_score_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                                   uint32_t n_pheno, const double *phenotypes, uint32_t n_covar,
+                                   const double *covariates, pgh_glm_row *out, char *errbuf) {
+	return GlmScoreMultiEntry(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, nullptr, errbuf);
+}
+
+extern "C" int pgh_glm_score_multi_spa(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin,
+                                       uint32_t v_end, uint32_t n_pheno, const double *phenotypes, uint32_t n_covar,
+                                       const double *covariates, double spa_cutoff, pgh_glm_row *out, double *p_spa,
+                                       uint8_t *spa_state, char *errbuf) {
+	const int rc = GlmCheckSpa(spa_cutoff, p_spa, spa_state, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
+	}
+	const GlmScoreSpaArgs spa = {spa_cutoff, p_spa, spa_state};
+	return GlmScoreMultiEntry(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, &spa, errbuf);
 }
 
 extern "C" int pgh_burden_sparse(const pgh_dataset *ds, const pgh_subset *subset, const double *phenotype,

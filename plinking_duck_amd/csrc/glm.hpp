@@ -154,7 +154,8 @@ hipError_t LaunchGlmScoreNull(uint32_t n_out, const double *y, const double *z, 
 hipError_t LaunchGlmScoreSparse(const SparseView &sv, uint32_t v_first, uint32_t nv, const double *r, const double *w,
                                 const double *z, uint32_t kp, uint32_t k, uint32_t n_y, const double *hg, double *sums,
                                 double *hgn, hipStream_t stream);
-// What the solve kernel leaves for pgh_glm_score_sparse_spa (all null: nothing, pgh_glm_score_sparse's launch).
+// What the solve kernel leaves for pgh_glm_score_sparse_spa and pgh_glm_score_multi_spa (all null: nothing, the launch
+// of pgh_glm_score_sparse and pgh_glm_score_multi).
 // t[i][kp + 3] = {H_N^-1 c (kp + 1 doubles, zero past k), U, V} for the fitted rows; p_spa[i] = rows[i].p (NaN when the
 // row is not fitted) and state[i] = 0 for every row.
 struct GlmScoreSpaOut {
@@ -210,6 +211,17 @@ hipError_t LaunchGlmScoreSpa(const SparseView &sv, uint32_t v_first, uint32_t nv
                              const double *z, uint32_t kp, const pgh_glm_row *rows, const double *t,
                              double cutoff, uint32_t n_groups, void *stash, double *p_spa, uint8_t *state,
                              hipStream_t stream);
+
+// ---- pgh_glm_score_multi_spa (glm_score_dense_spa.hip): saddlepoint p-values of the dense route's rows ----
+// For the rows (phenotype p < pb, chunk variant i < nv) at p * nv + i that are fitted with |stat| > cutoff: p_spa and
+// state = 1, or state = 2 with p_spa left as it is; the other rows are not touched.  view, v0, nv, mask, pb, b, z0, mz,
+// kp, k and sums are LaunchGlmScoreDense's (sums as it left them); rows and t ([pb][nv][kp + 3]) are
+// LaunchGlmScoreSolve's, phenotype by phenotype.  stash: n_groups x GlmScoreSpaStashPerGroup bytes, whatever they
+// hold.  Nothing in the output depends on n_groups (>= 1).
+hipError_t LaunchGlmScoreDenseSpa(const RowView &view, uint32_t v0, uint32_t nv, const uint32_t *mask, uint32_t pb,
+                                  const double *b, const double *z0, const double *mz, uint32_t kp, uint32_t k,
+                                  const double *sums, const pgh_glm_row *rows, const double *t, double cutoff,
+                                  uint32_t n_groups, void *stash, double *p_spa, uint8_t *state, hipStream_t stream);
 
 // ---- pgh_burden_sparse (burden_sparse.hip): the linear fit's sums of a weighted burden per variant set ----
 // What the kernel leaves per set beside its sums row.

@@ -7,14 +7,14 @@
 //   phase A  one walk of the row's entries.  A used called entry (the set E) gathers r, w and its z row and becomes
 //            the pair (g, mu): g = d - Zt t, mu = r > 0 ? 1 - r : -r.  The pairs go to the team's stash in entry order
 //            (TeamRank), V_E = sum_E w g^2 is a lane chain and TeamSums.
-//   phase B  u+ and u- (the roots are s = +u+ and s = -u-, both u > 0) by the safeguarded Newton iteration of the
-//            contract.  One evaluation is one pass of the team over the stash, both tails in the same pass: an exp per
-//            pair and tail, four fma chains per lane, TeamSums.  Every thread then holds the same four sums and takes
-//            the same step, so the control flow is team-uniform.  A last pass gives K and K'' at the two roots.
+//   phase B  SpaSolveStash (glm_spa.hpp, shared with glm_score_dense_spa.hip): u+ and u- by the safeguarded Newton
+//            iteration of the contract, one evaluation being one pass of the team over the stash, then K and K'' at
+//            the two roots.  All control flow is team-uniform.
 // The stash of a wave is 1,024 pairs of LDS; a workgroup's is sample_ct pairs of global scratch of its own, and the
 // workgroup form runs as a bounded grid of workgroups that stride over the rows.  No atomics; nothing depends on which
 // workgroup takes a row, on the grid, on the chunk or on where the range starts.
 #include "glm.hpp"
+#include "glm_spa.hpp"
 #include "glm_team.hpp"
 
 #include <hip/hip_runtime.h>
@@ -26,72 +26,7 @@ namespace pgh {
 namespace {
 
 constexpr int kBlock = kTeamBlock;
-constexpr int kSpaMaxEval = 64;        // evaluations of K', K'' per row (both tails in one)
-constexpr double kSpaStop = 1e-12;     // |delta s| sqrt(V) at which a root is taken
-constexpr double kSpaUlps = 0x1p-50;   // ... or |delta s| / |s|
 constexpr uint32_t kSpaWaveStash = kGlmSparseLong; // pairs per wave
-
-// pi = mu e^x / (1 - mu + mu e^x) and 1 - pi from one exp of a non-positive argument.
-__device__ __forceinline__ void SpaPi(double x, double mu, double *pi, double *qi) {
-	const double a = exp(-fabs(x)), nu = 1.0 - mu;
-	const double np = x > 0.0 ? mu : mu * a, nq = x > 0.0 ? nu * a : nu;
-	const double inv = 1.0 / (np + nq);
-	*pi = np * inv;
-	*qi = nq * inv;
-}
-
-// ln(1 - mu + mu e^x) - mu x
-__device__ __forceinline__ double SpaK(double x, double mu) {
-	const double m = x > 0.0 ? 1.0 - mu : mu;
-	return (x > 0.0 ? x : 0.0) + log1p(m * expm1(-fabs(x))) - mu * x;
-}
-
-// One tail's iteration for the root u > 0 of F(u) = |U|, F increasing, F(0) = 0.
-struct SpaRoot {
-	double u, lo, hi, grow;
-	bool done;
-};
-
-// F and F' at r->u are known: the bracket, then the next u.  Returns false when a value is not finite.
-__device__ __forceinline__ bool SpaStep(SpaRoot *r, double f, double fp, double q, double tol) {
-	if (r->done) {
-		return true;
-	}
-	if (!(fabs(f) < INFINITY) || !(fabs(fp) < INFINITY)) {
-		return false;
-	}
-	if (f < q) {
-		r->lo = r->u;
-	} else {
-		r->hi = r->u;
-	}
-	double un = r->u + (q - f) / fp;
-	if (r->hi == INFINITY) {
-		if (!(un <= r->u + r->grow)) { // (a NaN step too)
-			un = r->u + r->grow;
-			r->grow *= 2.0;
-		}
-	} else if (!(un >= r->lo && un <= r->hi)) {
-		un = 0.5 * (r->lo + r->hi);
-	}
-	// (far out, where a step of kSpaStop / sqrt(V) is below the spacing of s, a step of a few ulps is as good)
-	r->done = fabs(un - r->u) <= fmax(tol, kSpaUlps * r->u) || r->hi - r->lo <= tol;
-	r->u = un;
-	return true;
-}
-
-// Phi-bar(|omega + ln(nu / omega) / omega|) of one tail; NaN when the formula cannot be evaluated.
-__device__ __forceinline__ double SpaTail(double u, double q, double kk, double k2) {
-	const double rad = 2.0 * (u * q - kk);
-	if (!(rad > 0.0) || !(k2 > 0.0)) {
-		return NAN;
-	}
-	const double om = sqrt(rad), ratio = u * sqrt(k2) / om;
-	if (!(ratio > 0.0) || !(ratio < INFINITY)) {
-		return NAN;
-	}
-	return 0.5 * erfc(fabs(om + log(ratio) / om) * 0.70710678118654752440);
-}
 
 // One row by one team.  st: the team's stash of at least `cap` pairs (LDS or global).
 template <int KP, int TEAM, class Stash>
@@ -183,49 +118,8 @@ __device__ __forceinline__ void SpaRow(const SparseRows &rows, uint32_t i, const
 	const double v_rest = base3 ? 0.0 : fmax(v - sums[0], 0.0);
 
 	// phase B
-	const double tol = kSpaStop / sqrt(v);
-	SpaRoot ra = {q / v, 0.0, INFINITY, 1.0 / sqrt(v), false}, rb = ra;
-	asm volatile("" : "+v"(ra.lo), "+v"(ra.hi), "+v"(rb.lo), "+v"(rb.hi));
-	for (int ev = 0; ok && ev < kSpaMaxEval && !(ra.done && rb.done); ev++) {
-		sums[0] = sums[1] = sums[2] = sums[3] = 0.0;
-		for (uint32_t j = tid; j < count; j += TEAM) {
-			const double2 e = st[j];
-			const double gg = e.x * e.x;
-			double pi, qi;
-			SpaPi(e.x * ra.u, e.y, &pi, &qi);
-			sums[0] = fma(e.x, pi - e.y, sums[0]);
-			sums[1] = fma(gg, pi * qi, sums[1]);
-			SpaPi(-e.x * rb.u, e.y, &pi, &qi);
-			sums[2] = fma(e.x, pi - e.y, sums[2]);
-			sums[3] = fma(gg, pi * qi, sums[3]);
-		}
-		TeamSums<TEAM>(sums, none, lane, wave);
-		TeamSync<TEAM>();
-		ok = SpaStep(&ra, fma(v_rest, ra.u, sums[0]), sums[1] + v_rest, q, tol) &&
-		     SpaStep(&rb, fma(v_rest, rb.u, -sums[2]), sums[3] + v_rest, q, tol);
-	}
-	ok = ok && ra.done && rb.done;
-	double p = NAN;
-	if (ok) { // (the whole team agrees)
-		// K and K'' at the two roots, a tail at a time (one copy of the code; this pass runs once per row)
-		p = 0.0;
-#pragma nounroll
-		for (int h = 0; h < 2; h++) {
-			const double u = h ? rb.u : ra.u, su = h ? -u : u;
-			sums[0] = sums[1] = sums[2] = sums[3] = 0.0;
-			for (uint32_t j = tid; j < count; j += TEAM) {
-				const double2 e = st[j];
-				double pi, qi;
-				SpaPi(e.x * su, e.y, &pi, &qi);
-				sums[0] += SpaK(e.x * su, e.y);
-				sums[1] = fma(e.x * e.x, pi * qi, sums[1]);
-			}
-			TeamSums<TEAM>(sums, none, lane, wave);
-			TeamSync<TEAM>();
-			p += SpaTail(u, q, fma(0.5 * v_rest * u, u, sums[0]), sums[1] + v_rest);
-		}
-		ok = fabs(p) < INFINITY;
-	}
+	double p;
+	ok = SpaSolveStash<TEAM>(st, count, ok, q, v, v_rest, tid, lane, wave, &p);
 	if (tid == 0) {
 		if (ok) {
 			p_spa[i] = p;

@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = [
     "pgh_reader_unpack_start", "pgh_reader_unpack_wait", "pgh_get_2bit", "pgh_get_counts", "pgh_get_missingness", "pgh_get_int8", "pgh_get_dosage_f64", "pgh_get_phased",
     "pgh_tally_start", "pgh_tally_request", "pgh_tally_wait", "pgh_tally_counts", "pgh_tally_hwe_lnp",
     "pgh_tally_sample_missing", "pgh_tally_destroy", "pgh_tally_passes_started", "pgh_host_alloc", "pgh_host_free", "pgh_trim_device_cache",
-    "pgh_reader_error", "pgh_open_sparse", "pgh_get_sparse_info", "pgh_sparse_opens_started", "pgh_glm", "pgh_glm_multi", "pgh_glm_sparse", "pgh_glm_score_sparse", "pgh_glm_score_multi", "pgh_glm_score_sparse_spa", "pgh_burden_sparse", "pgh_skat_sparse", "pgh_skat_p_from_lambda", "pgh_symmetric_eigenvalues", "pgh_score_sparse", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
+    "pgh_reader_error", "pgh_open_sparse", "pgh_get_sparse_info", "pgh_sparse_opens_started", "pgh_glm", "pgh_glm_multi", "pgh_glm_sparse", "pgh_glm_score_sparse", "pgh_glm_score_multi", "pgh_glm_score_sparse_spa", "pgh_glm_score_multi_spa", "pgh_burden_sparse", "pgh_skat_sparse", "pgh_skat_p_from_lambda", "pgh_symmetric_eigenvalues", "pgh_score_sparse", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
     "pgh_king_counts", "pgh_king_table", "pgh_king_kinship",
     "pgh_ld_window_sums", "pgh_ld_prune", "pgh_ld_exceeds", "pgh_ld_scores", "pgh_ld_r2",
     "pgh_grm", "pgh_grm_standardize",
@@ -252,6 +252,7 @@ def _load():
         "pgh_glm_score_sparse": (C.c_int, [vp, vp, u32, u32, vp, u32, vp, vp, cp]),
         "pgh_glm_score_multi": (C.c_int, [vp, vp, u32, u32, u32, vp, u32, vp, vp, cp]),
         "pgh_glm_score_sparse_spa": (C.c_int, [vp, vp, u32, u32, vp, u32, vp, C.c_double, vp, vp, vp, cp]),
+        "pgh_glm_score_multi_spa": (C.c_int, [vp, vp, u32, u32, u32, vp, u32, vp, C.c_double, vp, vp, vp, cp]),
         "pgh_burden_sparse": (C.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, cp]),
         "pgh_skat_sparse": (C.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, cp]),
         "pgh_skat_p_from_lambda": (C.c_double, [C.c_double, vp, u32, vp]),
@@ -1017,6 +1018,15 @@ class Dataset:
         """pgh_glm_score_multi: the logistic score test of every variant of a dense-resident dataset for every row of
         phenotypes (P x n_out; 0.0 / 1.0, NaN = missing) in one call, on the FP64 matrix cores.  Returns glm_multi()'s
         dict of (V, P) arrays: [v, p] is glm_score_sparse()'s row of phenotype p alone for variant v_begin + v."""
+        v0, v1, y, z = Dataset._score_multi_args(self, phenotypes, covariates, v_begin, v_end, subset)
+        rows = np.zeros((max(0, v1 - v0), y.shape[0]), dtype=GLM_ROW_DTYPE)
+        eb = _errbuf()
+        _check(_lib.pgh_glm_score_multi(self._h, subset._h if subset else None, v0, v1, y.shape[0], _ptr(y), z.shape[0],
+                                        _ptr(z) if z.size else None, _ptr(rows), eb), eb)
+        return Dataset._glm_multi_rows_dict(rows)
+
+    def _score_multi_args(self, phenotypes, covariates, v_begin, v_end, subset):
+        """(v0, v1, y, z) of the dense score-test calls, after their shape checks."""
         v0 = self.v_begin if v_begin is None else v_begin
         v1 = self.v_end if v_end is None else v_end
         n_out = subset.size if subset else self.n_samples
@@ -1029,16 +1039,33 @@ class Dataset:
             z = np.ascontiguousarray(np.atleast_2d(np.asarray(covariates, dtype=np.float64)))
             if z.shape[1] != n_out:
                 raise ValueError(f"covariates must be n_covar x {n_out}, got shape {z.shape}")
-        rows = np.zeros((max(0, v1 - v0), y.shape[0]), dtype=GLM_ROW_DTYPE)
-        eb = _errbuf()
-        _check(_lib.pgh_glm_score_multi(self._h, subset._h if subset else None, v0, v1, y.shape[0], _ptr(y), z.shape[0],
-                                        _ptr(z) if z.size else None, _ptr(rows), eb), eb)
+        return v0, v1, y, z
+
+    @staticmethod
+    def _glm_multi_rows_dict(rows) -> dict:
         return {
             "beta": rows["beta"].copy(), "se": rows["se"].copy(), "stat": rows["stat"].copy(), "p": rows["p"].copy(),
             "a1_freq": rows["a1_freq"].copy(), "obs_ct": rows["obs_ct"].astype(np.int64),
             "errcode": np.array(GLM_ERRCODES, dtype=object)[rows["errcode"]],
             "firth": rows["firth"].astype(bool),
         }
+
+    def glm_score_multi_spa(self, phenotypes, covariates=None, spa_cutoff: float = 2.0, subset: Subset | None = None,
+                            v_begin: int | None = None, v_end: int | None = None) -> dict:
+        """pgh_glm_score_multi_spa: glm_score_multi() plus a saddlepoint p-value for the rows with |stat| > spa_cutoff
+        (spa_cutoff >= 0.1; inf = never).  Returns glm_score_multi()'s dict (p stays the normal p-value) and, both of
+        shape (V, P), p_spa (float64: NaN for a row that is not fitted, p where the saddlepoint was not applied or
+        failed) and spa_state (uint8: 0 = not applied, 1 = applied, 2 = attempted and failed)."""
+        v0, v1, y, z = Dataset._score_multi_args(self, phenotypes, covariates, v_begin, v_end, subset)
+        shape = (max(0, v1 - v0), y.shape[0])
+        rows = np.zeros(shape, dtype=GLM_ROW_DTYPE)
+        p_spa = np.zeros(shape, dtype=np.float64)
+        state = np.zeros(shape, dtype=np.uint8)
+        eb = _errbuf()
+        _check(_lib.pgh_glm_score_multi_spa(self._h, subset._h if subset else None, v0, v1, y.shape[0], _ptr(y),
+                                            z.shape[0], _ptr(z) if z.size else None, float(spa_cutoff), _ptr(rows),
+                                            _ptr(p_spa), _ptr(state), eb), eb)
+        return dict(Dataset._glm_multi_rows_dict(rows), p_spa=p_spa, spa_state=state)
 
     def glm_score_sparse_spa(self, phenotype, covariates=None, cutoff: float = 2.0, v_begin: int | None = None,
                              v_end: int | None = None, subset: Subset | None = None) -> dict:

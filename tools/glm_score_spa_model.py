@@ -101,6 +101,30 @@ def tail(u, q, kk, k2):
     return 0.5 * math.erfc(abs(om + math.log(ratio) / om) * 0.70710678118654752440)
 
 
+def phase_b(g, mu, q, v, v_rest, team):
+    """(p_spa, evaluations) from a team's stash of (g, mu) pairs as the device computes them; p_spa None: state 2."""
+    tol = STOP / math.sqrt(v)
+    ra, rb = Root(q, v), Root(q, v)
+    ok, evals = True, 0
+    while ok and evals < MAX_EVAL and not (ra.done and rb.done):
+        pa, qa = pi_q(g * ra.u, mu)
+        pb, qb = pi_q(-g * rb.u, mu)
+        s0, s1 = team_sum(g * (pa - mu), team), team_sum(g * g * (pa * qa), team)
+        s2, s3 = team_sum(g * (pb - mu), team), team_sum(g * g * (pb * qb), team)
+        evals += 1
+        ok = ra.step(v_rest * ra.u + s0, s1 + v_rest, q, tol) and rb.step(v_rest * rb.u - s2, s3 + v_rest, q, tol)
+    if not (ok and ra.done and rb.done):
+        return None, evals
+    total = 0.0
+    for uu, sg in ((ra.u, 1.0), (rb.u, -1.0)):
+        pa, qa = pi_q(sg * g * uu, mu)
+        kk = team_sum(k_term(sg * g * uu, mu), team) + 0.5 * v_rest * uu * uu
+        total += tail(uu, q, kk, team_sum(g * g * (pa * qa), team) + v_rest)
+    if not math.isfinite(total):
+        return None, evals
+    return total, evals
+
+
 def model_row(codes, nul, base, dense_form, cutoff):
     """(p, p_spa, state, evaluations) of a FITTED row as the device computes them."""
     b = 0 if (dense_form or base == 3) else base
@@ -131,25 +155,8 @@ def model_row(codes, nul, base, dense_form, cutoff):
     mu = np.where(ri > 0, 1.0 - ri, -ri)
     v_e = team_sum(w[in_e] * g * g, team)
     v_rest = 0.0 if (base == 3 and not dense_form) else max(v - v_e, 0.0)
-    q = abs(u)
-    tol = STOP / math.sqrt(v)
-    ra, rb = Root(q, v), Root(q, v)
-    ok, evals = True, 0
-    while ok and evals < MAX_EVAL and not (ra.done and rb.done):
-        pa, qa = pi_q(g * ra.u, mu)
-        pb, qb = pi_q(-g * rb.u, mu)
-        s0, s1 = team_sum(g * (pa - mu), team), team_sum(g * g * (pa * qa), team)
-        s2, s3 = team_sum(g * (pb - mu), team), team_sum(g * g * (pb * qb), team)
-        evals += 1
-        ok = ra.step(v_rest * ra.u + s0, s1 + v_rest, q, tol) and rb.step(v_rest * rb.u - s2, s3 + v_rest, q, tol)
-    if not (ok and ra.done and rb.done):
-        return p, p, 2, evals
-    total = 0.0
-    for uu, sg in ((ra.u, 1.0), (rb.u, -1.0)):
-        pa, qa = pi_q(sg * g * uu, mu)
-        kk = team_sum(k_term(sg * g * uu, mu), team) + 0.5 * v_rest * uu * uu
-        total += tail(uu, q, kk, team_sum(g * g * (pa * qa), team) + v_rest)
-    if not math.isfinite(total):
+    total, evals = phase_b(g, mu, abs(u), v, v_rest, team)
+    if total is None:
         return p, p, 2, evals
     return p, total, 1, evals
 
