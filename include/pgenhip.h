@@ -670,7 +670,8 @@ int pgh_glm_score_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32
  *
  * PGH_GLM_SCORE_SCRATCH_BYTES (environment, read at every call, default 6 GiB) bounds the device scratch that grows
  * with the phenotypes and variants in flight; the result does not depend on it.
- * Saddlepoint p-values over this route: pgh_glm_score_multi_spa.  Not offered: Firth p-values over this route, dosage
+ * Saddlepoint p-values over this route: pgh_glm_score_multi_spa.  Approximate Firth estimates over this route:
+ * pgh_glm_score_multi_firth.  Not offered: a Firth-penalised null fit, Firth and saddlepoint in one call, dosage
  * tracks, shard groups, a table function. */
 int pgh_glm_score_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                         uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
@@ -748,6 +749,77 @@ int pgh_glm_score_sparse_spa(const pgh_dataset *ds, const pgh_subset *subset, ui
 int pgh_glm_score_multi_spa(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                             uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
                             double spa_cutoff, pgh_glm_row *out, double *p_spa, uint8_t *spa_state, char *errbuf);
+/* One (variant, phenotype) result of pgh_glm_score_multi_firth. */
+typedef struct pgh_glm_firth_row {
+	double beta, se, p;
+	uint8_t state;      /* 0 not applied, 1 applied, 2 attempted and failed */
+	uint8_t pad[7];
+} pgh_glm_firth_row;   /* 32 bytes */
+/* pgh_glm_score_multi with an APPROXIMATE FIRTH estimate beside the one-step score estimate, for every (variant,
+ * phenotype) row of the dense route beyond a cutoff (the "approximate Firth" of Mbatchou et al. 2021: the covariate
+ * effects are held fixed at the null fit and only the variant's own coefficient is estimated, under Firth's penalty).
+ * Arguments, argument checks, error texts and refusals are pgh_glm_score_multi's: a sparse-resident dataset, a shard
+ * group, a dataset with dosage tracks, 0/1 phenotypes, cases and controls.  In addition firth_cutoff must be at least
+ * 0.1 (+infinity: never apply it; NaN or a smaller value is PGH_ERR_ARG, "firth_cutoff must be at least 0.1"), and
+ * firth must not be NULL ("null firth"); it has out's layout, element (v - v_begin) * n_pheno + p.  On any error both
+ * outputs are untouched.  v_begin == v_end is PGH_OK.
+ *
+ * out is pgh_glm_score_multi's result for the same arguments bit for bit.  Its firth byte stays 0: that byte records
+ * pgh_glm's full Firth fallback, which this is not.
+ *
+ * firth[i].state and values; pad is zero:
+ *   0  the row is not fitted:                      beta, se, p are NaN
+ *   0  the row is fitted with |stat| <= cutoff:    out's beta, se, p bit for bit
+ *   1  applied:                                    the Firth values below
+ *   2  attempted and failed:                       out's beta, se, p bit for bit
+ *
+ * Definition, in pgh_glm_score_sparse's notation (S, N, r, w).  The null model is that contract's maximum-likelihood
+ * fit, unchanged.
+ *   mu_i = r_i > 0 ? 1 - r_i : -r_i
+ *   y_i - mu_i = r_i
+ *   E = the samples of N with x_i != 0
+ *   G = sum_E x_i r_i
+ * With pi_i(beta) = mu e^(x beta) / (1 - mu + mu e^(x beta)) and v_i = pi_i (1 - pi_i):
+ *   K(beta)     = sum_E [ln(1 - mu + mu e^(x beta)) - mu x beta]
+ *   K'(beta)    = sum_E x (pi - mu)
+ *   K''(beta)   = sum_E x^2 v
+ *   K'''(beta)  = sum_E x^3 v (1 - 2 pi)
+ *   K''''(beta) = sum_E x^4 v (1 - 6 v)
+ *
+ *   l*(beta) = beta G - K(beta) + 1/2 ln K''(beta)          (penalised log-likelihood minus the unpenalised one at 0)
+ *   F(beta)  = G - K'(beta) + 1/2 K'''(beta) / K''(beta)    (Firth's modified score)
+ *   H(beta)  = K''(beta) - 1/2 [K''''(beta)/K''(beta) - (K'''(beta)/K''(beta))^2];  where not H > 0, H = K''(beta)
+ * All sums are evaluated with one exp of -|x beta| per entry, as for pgh_glm_score_sparse_spa, so nothing overflows or
+ * cancels.  With the covariate part fixed a sample with x = 0 contributes a constant, which is why E suffices.
+ *
+ * Root.  The iteration is safeguarded and is the saddlepoint code's scheme.
+ *   1. Evaluate at 0.  F(0) = 0 exactly gives beta^ = 0.
+ *   2. Otherwise the root lies on the side sgn = sign F(0), and the bracket is [0, open) on that side.
+ *   3. From an evaluated point beta the next point is beta + F/H.
+ *   4. While the far side is open, a step may not move more than 1/sqrt(K''(0)) beyond beta.  That limit doubles each
+ *      time it is used.
+ *   5. Once the far side is closed, a point outside the bracket is replaced by the bracket's midpoint.
+ *   6. A point with F of sign sgn becomes the near end.  Any other point becomes the far end.
+ *   7. beta, already evaluated, is taken as beta^ when the proposed move delta meets any of these stopping rules:
+ *      |delta| sqrt(K''(0)) <= 1e-10; the closed bracket is that narrow; |delta| <= 2^-50 |beta|.
+ *   8. F(beta) = 0 exactly also ends the iteration.
+ *   9. There are at most 64 evaluations, the one at 0 included.
+ * State 2 is any of: the cap of 64 evaluations is reached; any of l*, F, H is not finite; K'' is not > 0 at an
+ * evaluated point.
+ *
+ * Result.  beta = beta^;  se = 1 / sqrt(K''(beta^));  D = max(2 (l*(beta^) - l*(0)), 0);  p = pgh_glm_p_from_z(sqrt(D)),
+ * the chi-square tail on 1 df.
+ *
+ * This is a definition: the null fit is not Firth-penalised, unlike REGENIE's.  It has not been compared with another
+ * program's output.
+ *
+ * A row's (out, firth) is a function of its variant's calls, its own phenotype, the covariates, the subset and
+ * firth_cutoff only: not of the other phenotypes of the call or its place among them, of v_begin, the variant chunk,
+ * the phenotype block, PGH_GLM_SCORE_SCRATCH_BYTES (which also bounds this kernel's stashes exactly as for
+ * pgh_glm_score_multi_spa) or the grid, and the same call returns the same bytes every time. */
+int pgh_glm_score_multi_firth(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                              uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
+                              double firth_cutoff, pgh_glm_row *out, pgh_glm_firth_row *firth, char *errbuf);
 /* Gene-set BURDEN tests over a SPARSE-RESIDENT dataset (pgh_open_sparse), from the variants' entries: per set, the
  * variants are collapsed into one weighted burden per sample and the phenotype is regressed on it (linear).
  *

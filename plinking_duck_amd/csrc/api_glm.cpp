@@ -657,6 +657,11 @@ struct GlmScoreSpaArgs {
 	uint8_t *state;
 };
 constexpr uint64_t kSpaStashBytes = 256ull << 20;
+// pgh_glm_score_multi_firth's own arguments.
+struct GlmScoreFirthArgs {
+	double cutoff;
+	pgh_glm_firth_row *rows;
+};
 
 int GlmScoreSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                       const double *phenotype, uint32_t k, const double *covariates, pgh_glm_row *out, char *errbuf,
@@ -1295,9 +1300,12 @@ constexpr uint32_t kGlmScoreMultiChunk = 65536;
 // column block (at least one stash, at most four workgroups per compute unit: the time of the kernel's iteration
 // falls with their number); [t, U, V], p_spa and the state per row join the chunk's bytes.  spa == null runs the launches it ran before
 // there was a saddlepoint path.
+// firth != null (pgh_glm_score_multi_firth; never with spa): after a block's chunk of rows, GlmScoreDenseFirthKernel
+// writes every row's pgh_glm_firth_row.  Its stashes are sized as the saddlepoint's, out of the same budget; a
+// pgh_glm_firth_row per row joins the chunk's bytes.
 int GlmScoreMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end, uint32_t n_pheno,
                      const double *phenotypes, uint32_t k, const double *covariates, pgh_glm_row *out, char *errbuf,
-                     const GlmScoreSpaArgs *spa = nullptr) {
+                     const GlmScoreSpaArgs *spa = nullptr, const GlmScoreFirthArgs *firth = nullptr) {
 	PGH_ENTER(ds);
 	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct, n_raw = ds->sample_ct;
 	const uint32_t nv_all = v_end - v_begin;
@@ -1327,15 +1335,16 @@ int GlmScoreMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v
 		pb_max--;
 	}
 	const uint64_t per_variant =
-	    static_cast<uint64_t>(pb_max) * (8ull * (ns + ne) + sizeof(pgh_glm_row) + 4 + (spa ? 8ull * (kp + 3) + 8 + 1 : 0));
+	    static_cast<uint64_t>(pb_max) * (8ull * (ns + ne) + sizeof(pgh_glm_row) + 4 + (spa ? 8ull * (kp + 3) + 8 + 1 : 0) +
+	                                   (firth ? sizeof(pgh_glm_firth_row) : 0));
 	uint64_t left = budget > block_bytes(pb_max) ? budget - block_bytes(pb_max) : 0;
 	const uint64_t per_group = pgh::GlmScoreSpaStashPerGroup(n_raw);
 	uint32_t n_groups = 0;
-	if (spa) {
+	if (spa || firth) {
 		int device = 0, cus = 0;
-		PGH_HIP(hipGetDevice(&device), "glm_score_multi_spa device");
+		PGH_HIP(hipGetDevice(&device), "glm_score_multi stash device");
 		PGH_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device),
-		        "glm_score_multi_spa device attribute");
+		        "glm_score_multi stash device attribute");
 		const uint64_t rows_all = static_cast<uint64_t>(std::min(kGlmScoreMultiChunk, nv_all)) * pb_max;
 		n_groups = static_cast<uint32_t>(std::max<uint64_t>(
 		    1, std::min<uint64_t>(std::min<uint64_t>(rows_all, 4ull * static_cast<uint32_t>(std::max(cus, 1))),
@@ -1375,6 +1384,11 @@ int GlmScoreMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v
 		lay.Add(&so.state, pbm * c);
 		lay.Add(&d_stash, per_group * n_groups);
 	}
+	pgh_glm_firth_row *d_firth = nullptr;
+	if (firth) {
+		lay.Add(&d_firth, pbm * c);
+		lay.Add(&d_stash, per_group * n_groups);
+	}
 	void *scratch = nullptr;
 	PGH_HIP(PghThreadScratch(lay.total, st, &scratch), "glm_score_multi scratch");
 	lay.Bind(scratch);
@@ -1396,6 +1410,7 @@ int GlmScoreMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v
 	std::vector<pgh_glm_row> hrows(static_cast<size_t>(chunk) * pb_max);
 	std::vector<double> hp_spa(spa ? hrows.size() : 0);
 	std::vector<uint8_t> hstate(spa ? hrows.size() : 0);
+	std::vector<pgh_glm_firth_row> hfirth(firth ? hrows.size() : 0);
 	HostSourceFence fence(st); // sg, gs, h_ny and the caller's phenotypes feed asynchronous uploads
 	if (kp) {
 		PGH_HIP(hipMemcpyAsync(d_z0, sg.hz.data(), 8ull * sg.hz.size(), hipMemcpyHostToDevice, st),
@@ -1487,6 +1502,13 @@ int GlmScoreMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v
 				PGH_HIP(hipMemcpyAsync(hstate.data(), so.state, static_cast<size_t>(nv) * pb, hipMemcpyDeviceToHost, st),
 				        "glm_score_multi_spa state copy");
 			}
+			if (firth) {
+				PGH_HIP(pgh::LaunchGlmScoreDenseFirth(ds->View(), v_begin + c0 - ds->v_begin, nv, d_mask, pb, d_b, k, d_rows,
+				                                      firth->cutoff, n_groups, d_stash, d_firth, st),
+				        "glm_score_multi_firth kernel");
+				PGH_HIP(hipMemcpyAsync(hfirth.data(), d_firth, sizeof(pgh_glm_firth_row) * nv * pb, hipMemcpyDeviceToHost, st),
+				        "glm_score_multi_firth rows copy");
+			}
 			PGH_HIP(hipStreamSynchronize(st), "glm_score_multi sync");
 			for (uint32_t i = 0; i < nv; i++) {
 				for (uint32_t j = 0; j < pb; j++) {
@@ -1495,6 +1517,9 @@ int GlmScoreMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v
 					if (spa) {
 						spa->p_spa[to] = hp_spa[from];
 						spa->state[to] = hstate[from];
+					}
+					if (firth) {
+						firth->rows[to] = hfirth[from];
 					}
 				}
 			}
@@ -1525,10 +1550,12 @@ extern "C" int pgh_glm_score_sparse_spa(const pgh_dataset *ds, const pgh_subset 
 
 namespace {
 
-// pgh_glm_score_multi and pgh_glm_score_multi_spa (spa != null) after the latter's own argument checks.
+// pgh_glm_score_multi, pgh_glm_score_multi_spa (spa != null) and pgh_glm_score_multi_firth (firth != null) after the
+// latter two's own argument checks.
 int GlmScoreMultiEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                        uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
-                       pgh_glm_row *out, const GlmScoreSpaArgs *spa, char *errbuf) {
+                       pgh_glm_row *out, const GlmScoreSpaArgs *spa, char *errbuf,
+                       const GlmScoreFirthArgs *firth = nullptr) {
 	PGH_ONE_DEVICE(ds);
 	PGH_DENSE_ROWS(ds);
 	const int rc = GlmCheckCommon(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, PGH_GLM_LOGISTIC,
@@ -1552,7 +1579,7 @@ int GlmScoreMultiEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_t
 	if (v_end == v_begin) {
 		return PGH_OK;
 	}
-	return GlmScoreMultiOne(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, errbuf, spa);
+	return GlmScoreMultiOne(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, errbuf, spa, firth);
 }
 
 } // namespace
@@ -1573,6 +1600,23 @@ extern "C" int pgh_glm_score_multi_spa(const pgh_dataset *ds, const pgh_subset *
 	}
 	const GlmScoreSpaArgs spa = {spa_cutoff, p_spa, spa_state};
 	return GlmScoreMultiEntry(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, &spa, errbuf);
+}
+
+extern "C" int pgh_glm_score_multi_firth(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin,
+                                         uint32_t v_end, uint32_t n_pheno, const double *phenotypes, uint32_t n_covar,
+                                         const double *covariates, double firth_cutoff, pgh_glm_row *out,
+                                         pgh_glm_firth_row *firth, char *errbuf) {
+	if (!(firth_cutoff >= 0.1)) { // (NaN too)
+		SetErr(errbuf, "firth_cutoff must be at least 0.1");
+		return PGH_ERR_ARG;
+	}
+	if (!firth) {
+		SetErr(errbuf, "null firth");
+		return PGH_ERR_ARG;
+	}
+	const GlmScoreFirthArgs fa = {firth_cutoff, firth};
+	return GlmScoreMultiEntry(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, nullptr, errbuf,
+	                          &fa);
 }
 
 extern "C" int pgh_burden_sparse(const pgh_dataset *ds, const pgh_subset *subset, const double *phenotype,

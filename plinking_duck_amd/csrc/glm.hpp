@@ -223,6 +223,15 @@ hipError_t LaunchGlmScoreDenseSpa(const RowView &view, uint32_t v0, uint32_t nv,
                                   const double *sums, const pgh_glm_row *rows, const double *t, double cutoff,
                                   uint32_t n_groups, void *stash, double *p_spa, uint8_t *state, hipStream_t stream);
 
+// ---- pgh_glm_score_multi_firth (glm_score_dense_firth.hip): approximate Firth estimates of the dense route's rows ----
+// For every row (phenotype p < pb, chunk variant i < nv) at p * nv + i: firth[p * nv + i], the contract's triple and
+// state (the score row's beta, se and p with state 0 where the row is not fitted or |stat| <= cutoff).  view, v0, nv,
+// mask, pb, b and k are LaunchGlmScoreDense's; rows are LaunchGlmScoreSolve's, phenotype by phenotype.  stash: n_groups
+// x GlmScoreSpaStashPerGroup bytes, whatever they hold.  Nothing in the output depends on n_groups (>= 1).
+hipError_t LaunchGlmScoreDenseFirth(const RowView &view, uint32_t v0, uint32_t nv, const uint32_t *mask, uint32_t pb,
+                                    const double *b, uint32_t k, const pgh_glm_row *rows, double cutoff,
+                                    uint32_t n_groups, void *stash, pgh_glm_firth_row *firth, hipStream_t stream);
+
 // ---- pgh_burden_sparse (burden_sparse.hip): the linear fit's sums of a weighted burden per variant set ----
 // What the kernel leaves per set beside its sums row.
 struct BurdenAux {
