@@ -256,6 +256,37 @@ def test_parity_with_the_oracle_for_every_base_code_and_both_forms(gpu_lib, rare
         sp.close()
 
 
+# every padded covariate width of kGlmWidths at its exact value and one above the bucket below it
+# (test_glm_widths_chunks.WIDTHS without the k = 1 of the parity test)
+WIDTHS = [2, 4, 5, 8, 9, 12, 13, 16, 17, 20]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", WIDTHS)
+def test_every_instantiated_width(gpu_lib, rare_files, k):
+    """The kernel's template <int KP> for every width GlmPadCovar returns, at k = KP and one above the width below:
+    the parity test's draw with 12 sets, its mixed-majority set among them, every row held sparse."""
+    n = 4099
+    f = rare_files[n]
+    rng = np.random.default_rng(1000 * n + k)
+    Z = _covariates(rng, k, n)
+    y = _oracle()._pheno(rng, n, "linear", Z)
+    sets = _random_sets(rng, 12, 0, M_R)
+    major = _Forms(f.geno, n, f.pitch).major
+    mixed = [HET_ROWS[0], int(np.flatnonzero(major == 2)[0]), int(np.flatnonzero(major == 3)[0]), HET_ROWS[1],
+             int(np.flatnonzero(major == 0)[5])]
+    assert sorted(major[mixed].tolist()) == [0, 1, 1, 2, 3]
+    sets[11] = np.array(mixed + mixed[:2], dtype=np.uint32)
+    off, vidx = _csr(sets)
+    w = _weights(rng, len(vidx))
+    sp, forms = f.sparse(n)
+    assert sp.sparse_info().dense_variant_ct == 0
+    exp = _expected(f.geno, forms, sets, w, y, Z)
+    assert sum(e["errcode"] is None for e in exp) >= 10 and exp[11]["errcode"] is None
+    _check(gpu_lib, sp.burden_sparse(y, off, vidx, w, Z), exp, ctx=k)
+    sp.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("k", [0, 3])
 def test_one_variant_sets_are_glm_sparse_rows(gpu_lib, rare_files, k):

@@ -6,6 +6,7 @@ results, each within 1e-9 of the oracle); and a row does not depend on the other
 the range, the window, the phenotype block, the variant chunk or the scratch budget: bit for bit."""
 
 import ctypes as C
+import functools
 import os
 import types
 
@@ -30,6 +31,19 @@ SCRATCH_ENV = "PGH_GLM_SCORE_SCRATCH_BYTES"
 PHENO_SPECS = ((0.2, 0.03), (0.5, 0.0), (0.05, 0.1), (0.35, 0.03), (0.1, 0.3))
 STRIDE7 = list(range(0, M, 7))
 MADE = [SS.ROW_ALL_MISSING, SS.ROW_MONO, SS.ROW_BLOCK]
+# every padded covariate width of kGlmWidths at its exact value and one above the bucket below it
+# (test_glm_widths_chunks.WIDTHS without the k = 1 of test_parity_with_the_oracle)
+WIDTHS = [2, 4, 5, 8, 9, 12, 13, 16, 17, 20]
+WIDTHS_N = 4099
+WIDTHS_ROWS = MADE + list(range(0, M, 23))
+# (k, what 17 phenotypes of k + 2 x-columns each do to the 16-column blocks)
+LAYOUTS = [(14, "a phenotype is one block"), (13, "every phenotype after the first straddles a block edge")]
+LAYOUT_PHENOTYPES = 17  # one more than the 16 squared-weight columns of a block: two such blocks
+# sample counts at and next to a 64-sample edge (words16 = ceil(n / 64), B padded to 64, the mask zero past n)
+EDGE_N = (63, 64, 65, 128)
+EDGE_K = (0, 2)
+EDGE_M = SS.M
+EDGE_SPECS = ((0.5, 0.03), (0.35, 0.03))
 
 
 # ---- no device ---------------------------------------------------------------------------------------------------
@@ -118,6 +132,66 @@ def _counts_equal_the_dense_logistic_fit(got, want, ctx=None):
     assert not got["firth"].any(), ctx
 
 
+@functools.lru_cache(maxsize=None)
+def _hard_codes(n, m):
+    return SS.hard_codes(n, m=m)
+
+
+@functools.lru_cache(maxsize=None)
+def width_inputs(k):
+    """(Z, Y) of the width cases: test_parity_with_the_oracle's draw at n = 4099, the six phenotypes."""
+    rng = np.random.default_rng(100 * WIDTHS_N + k)
+    Z = _covariates(rng, k, WIDTHS_N)
+    return Z, _phenotypes(rng, WIDTHS_N, Z)
+
+
+@functools.lru_cache(maxsize=None)
+def layout_inputs(k):
+    """(Z, Y): the six phenotypes of width_inputs in turn at positions 0..15, and at 16 one of its own."""
+    Z, six = width_inputs(k)
+    own = O.pheno(np.random.default_rng(17_000 + k), WIDTHS_N, Z, case_rate=0.25, missing=0.05)
+    Y = np.stack([six[i % len(six)] for i in range(LAYOUT_PHENOTYPES - 1)] + [own])
+    return Z, Y
+
+
+@functools.lru_cache(maxsize=None)
+def edge_inputs(n, k):
+    """(Z, Y) of the sample-count edges: case rates 0.5 and 0.35, 3 % NaN."""
+    rng = np.random.default_rng(100 * n + k)
+    Z = _covariates(rng, k, n)
+    return Z, np.stack([O.pheno(rng, n, Z, case_rate=c, missing=m) for c, m in EDGE_SPECS])
+
+
+# ---- no device: conditions on the inputs ------------------------------------------------------------------------
+
+@pytest.mark.parametrize("k", WIDTHS + [k for k, _ in LAYOUTS])
+def test_the_width_inputs_have_fitted_null_models_and_fitted_rows(k):
+    """So that a GPU case cannot pass on rows that are not fitted: every null model converges, and the oracle fits
+    more than half of the chosen rows of every phenotype that is compared with it."""
+    x = SS.values(_hard_codes(WIDTHS_N, M))
+    Z, Y = layout_inputs(k) if k in dict(LAYOUTS) else width_inputs(k)
+    assert len(set(y.tobytes() for y in Y)) == (7 if k in dict(LAYOUTS) else 6)
+    for p, y in enumerate(Y):
+        if p >= 6 and p != LAYOUT_PHENOTYPES - 1:
+            continue  # a copy
+        nul = O.Null(y, Z)
+        assert nul.status is None, (k, p, nul.status)
+        fitted = sum(O.oracle_row(x[i], nul)["errcode"] is None for i in WIDTHS_ROWS)
+        assert fitted > len(WIDTHS_ROWS) // 2, (k, p, fitted)
+
+
+@pytest.mark.parametrize("k", EDGE_K)
+@pytest.mark.parametrize("n", EDGE_N)
+def test_the_sample_count_edges_have_fitted_null_models_and_fitted_rows(n, k):
+    x = SS.values(_hard_codes(n, EDGE_M))
+    Z, Y = edge_inputs(n, k)
+    for p, y in enumerate(Y):
+        nul = O.Null(y, Z)
+        assert nul.status is None, (n, k, p, nul.status)
+        fitted = sum(O.oracle_row(x[i], nul)["errcode"] is None for i in range(EDGE_M))
+        assert fitted >= 120, (n, k, p, fitted)
+
+
 class _File:
     def __init__(self, L, tmp, name, codes, seed):
         self.codes, self.n = codes, codes.shape[1]
@@ -186,6 +260,74 @@ def test_parity_with_the_oracle(gpu_lib, files, kind, n, k):
             for p, y in enumerate(Y):
                 _close(_col(got, p), sp.glm_score_sparse(y, zc), 2 * REL, ctx=(kind, n, max_minor, p))
             sp.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", WIDTHS)
+def test_every_instantiated_width(gpu_lib, files, k):
+    """The column layout p (k + 2), the epilogue's column -> (phenotype, slot) map and GlmScoreDenseCorrKernel's rows of
+    k + 3 for every width GlmPadCovar returns, at k = KP and one above the width below: the made rows and every 23rd
+    row of every phenotype against the oracle, and the counts of one phenotype against pgh_glm's logistic fit."""
+    f = files["hard", WIDTHS_N]
+    Z, Y = width_inputs(k)
+    got = f.ds.glm_score_multi(Y, Z)
+    assert got["beta"].shape == (M, len(Y))
+    for p, y in enumerate(Y):
+        nul = O.Null(y, Z)
+        fitted, worst = O.check_rows(_col(got, p), f.x, nul, rel=REL, idx=WIDTHS_ROWS)
+        print(f"k={k} phenotype {p}: {fitted} fitted of {len(WIDTHS_ROWS)}, worst {worst:.3g}")
+        assert fitted > len(WIDTHS_ROWS) // 2, (k, p, fitted, nul.status)
+    p = k % len(Y)
+    _counts_equal_the_dense_logistic_fit(_col(got, p), f.ds.glm(Y[p], Z, model="logistic", firth=False), ctx=(k, p))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k,what", LAYOUTS)
+def test_phenotypes_at_and_across_the_column_blocks(gpu_lib, files, k, what):
+    """17 phenotypes, two blocks of squared-weight columns.  k = 14: the k + 2 x-columns of a phenotype are exactly one
+    16-column block; k = 13: 15 columns, so every phenotype after the first straddles a block edge.  The last
+    phenotype, which is no copy of another, and the first and the sixteenth against the oracle; every copy equals
+    its original bit for bit."""
+    f = files["hard", WIDTHS_N]
+    Z, Y = layout_inputs(k)
+    assert len(Y) == LAYOUT_PHENOTYPES and (len(Y) * (k + 2) + 15) // 16 >= 16
+    got = f.ds.glm_score_multi(Y, Z)
+    for p in (0, LAYOUT_PHENOTYPES - 2, LAYOUT_PHENOTYPES - 1):
+        nul = O.Null(Y[p], Z)
+        fitted, worst = O.check_rows(_col(got, p), f.x, nul, rel=REL, idx=WIDTHS_ROWS)
+        print(f"k={k} phenotype {p}: {fitted} fitted of {len(WIDTHS_ROWS)}, worst {worst:.3g}")
+        assert fitted > len(WIDTHS_ROWS) // 2, (k, p, fitted, nul.status)
+    for p in range(6, LAYOUT_PHENOTYPES - 1):
+        _same(_col(got, p), _col(got, p % 6), ctx=(k, p))
+    assert not np.array_equal(got["beta"][:, LAYOUT_PHENOTYPES - 1], got["beta"][:, 0], equal_nan=True)
+
+
+@pytest.fixture(scope="module")
+def edge_files(gpu_lib, tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("glm_score_multi_edges")
+    return {n: _File(gpu_lib, tmp, "edge", _hard_codes(n, EDGE_M), n) for n in EDGE_N}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", EDGE_K)
+@pytest.mark.parametrize("n", EDGE_N)
+def test_sample_counts_at_a_64_sample_edge(gpu_lib, edge_files, n, k):
+    """words16 = ceil(n / 64), B padded to 64-sample steps and a mask that is zero past the last sample: every row of
+    both phenotypes against the oracle, and the counts against pgh_glm's logistic fit."""
+    f = edge_files[n]
+    Z, Y = edge_inputs(n, k)
+    zc = Z if k else None
+    got = f.ds.glm_score_multi(Y, zc)
+    assert got["beta"].shape == (EDGE_M, len(Y))
+    for p, y in enumerate(Y):
+        nul = O.Null(y, Z)
+        fitted, worst = O.check_rows(_col(got, p), f.x, nul, rel=REL)
+        print(f"n={n} k={k} phenotype {p}: {fitted} fitted of {EDGE_M}, worst {worst:.3g}")
+        assert fitted >= 120, (n, k, p, fitted, nul.status)
+        want = f.ds.glm(y, zc, model="logistic", firth=False)
+        _counts_equal_the_dense_logistic_fit(_col(got, p), want, ctx=(n, k, p))
+    assert got["errcode"][SS.ROW_ALL_MISSING].tolist() == ["TOO_FEW_SAMPLES"] * len(Y)
+    assert got["errcode"][SS.ROW_MONO].tolist() == ["CONST_ALLELE"] * len(Y)
 
 
 @pytest.mark.gpu

@@ -7,7 +7,9 @@ phenotype block, the variant chunk or the scratch budget.
 
 TOL is 100 x the worst difference between the numpy model of the kernel's accumulation order
 (tools/glm_score_dense_firth_model.py) and the oracle on the parity inputs, MODEL_WORST below: the factor is
-test_glm_score_sparse_spa's, for device exp / log1p and fma contraction."""
+test_glm_score_sparse_spa's, for device exp / log1p and fma contraction.  The cases at every covariate width and at
+the sample-count edges are held to TOL_WIDTHS, the same rule on their own rows: MODEL_WORST_WIDTHS is what
+`python tools/glm_score_dense_firth_model.py --widths` prints."""
 
 import ctypes as C
 import functools
@@ -24,6 +26,7 @@ import glm_firth_oracle as F
 import glm_score_oracle as O
 import pgen_writer as W
 import subset_shapes as SS
+import test_glm_score_multi_spa as MS
 from test_glm_score_multi_spa import phenotypes
 from test_glm_score_sparse_spa import ParityInputs
 
@@ -31,9 +34,14 @@ NAN = float("nan")
 NEW_SYMBOLS = ["pgh_glm_score_multi_firth"]
 MODEL_WORST = 1.21e-12  # printed by tools/glm_score_dense_firth_model.py
 TOL = 100 * MODEL_WORST
+# printed by tools/glm_score_dense_firth_model.py --widths: the width and sample-count cases below, on the rows they
+# check
+MODEL_WORST_WIDTHS = 4.93e-12
+TOL_WIDTHS = 100 * MODEL_WORST_WIDTHS
 CUTOFF = 2.0
 PARITY_N = (257, 4099)
 PARITY_K = (0, 1, 3)
+WIDTHS, WIDTHS_N, WIDTHS_STRIDE, EDGES, EDGE_K = MS.WIDTHS, MS.WIDTHS_N, MS.WIDTHS_STRIDE, MS.EDGES, MS.EDGE_K
 SCRATCH_ENV = "PGH_GLM_SCORE_SCRATCH_BYTES"
 SUBSET_SHAPE = "stride4"  # every 16-code word of the row is cut: four of its samples are kept
 FIRTH_KEYS = ("beta_firth", "se_firth", "p_firth")
@@ -46,11 +54,15 @@ def inputs(n):
     return ParityInputs(n)
 
 
-def oracle_column(x, codes, y, Z, cutoff=CUTOFF):
-    """Per variant glm_firth_oracle.firth_row's (row, beta, se, p, state, info) of one phenotype."""
+def oracle_column(x, codes, y, Z, cutoff=CUTOFF, idx=None):
+    """Per variant glm_firth_oracle.firth_row's (row, beta, se, p, state, info) of one phenotype; None where idx leaves
+    it out."""
     nul = O.Null(y, Z)
     assert nul.status is None
-    return [F.firth_row(x[i], codes[i], nul, cutoff) for i in range(len(x))]
+    out = [None] * len(x)
+    for i in (range(len(x)) if idx is None else idx):
+        out[i] = F.firth_row(x[i], codes[i], nul, cutoff)
+    return out
 
 
 @functools.lru_cache(maxsize=None)
@@ -61,10 +73,26 @@ def oracle_case(n, k):
     return [oracle_column(case.x, case.geno, y, Z) for y in phenotypes(case)]
 
 
-def check_column(got, p, want, ctx=None):
+@functools.lru_cache(maxsize=None)
+def oracle_thinned(n, k, stride):
+    """oracle_case on every stride-th row: the width and sample-count cases (computed once)."""
+    case = inputs(n)
+    Z = case.covariates(k)
+    return [oracle_column(case.x, case.geno, y, Z, idx=range(0, case.m, stride)) for y in phenotypes(case)]
+
+
+def applied_rows(col):
+    return [w for w in col if w is not None and w[4] == 1]
+
+
+def check_column(got, p, want, tol=None, ctx=None):
     """Column p of Dataset.glm_score_multi_firth's dict against oracle_column's rows.  Returns (applied, worst)."""
+    tol = TOL if tol is None else tol
     applied, worst = 0, 0.0
-    for i, (row, beta, se, pv, state, _) in enumerate(want):
+    for i, w in enumerate(want):
+        if w is None:
+            continue
+        row, beta, se, pv, state, _ = w
         g = [got[key][i, p] for key in FIRTH_KEYS]
         at = (ctx, i, p, row, beta, se, pv, state, g, got["firth_state"][i, p], got["errcode"][i, p])
         assert got["errcode"][i, p] == row["errcode"], at
@@ -76,7 +104,7 @@ def check_column(got, p, want, ctx=None):
         else:
             diffs = (abs(g[0] - beta) / se, abs(g[1] - se) / se, abs(g[2] - pv) / pv)
             worst = max(worst, *diffs)
-            assert max(diffs) <= TOL, (diffs, at)
+            assert max(diffs) <= tol, (diffs, at)
             applied += 1
     return applied, worst
 
@@ -228,6 +256,25 @@ def test_the_parity_inputs_reach_the_cases_of_the_contract():
     assert flipped_all >= 1
 
 
+@pytest.mark.parametrize("k", WIDTHS)
+def test_the_width_inputs_have_applied_rows_at_every_width(k):
+    """Conditions on the inputs, not on the device, so that a width cannot pass on rows that are left alone: on the
+    rows test_every_instantiated_width checks the oracle decides every row (it asserts that every null model is
+    fitted), no row fails, each phenotype has 3 applied rows and the three have 15."""
+    cols = oracle_thinned(WIDTHS_N, k, WIDTHS_STRIDE)
+    applied = [len(applied_rows(col)) for col in cols]
+    print(f"k={k}: {applied} applied")
+    assert not any(w is not None and w[4] == 2 for col in cols for w in col), k
+    assert min(applied) >= 3 and sum(applied) >= 15, k
+
+
+@pytest.mark.parametrize("n,stride", EDGES)
+def test_the_sample_count_edges_have_applied_rows(n, stride):
+    applied = [len(applied_rows(col)) for col in oracle_thinned(n, EDGE_K, stride)]
+    print(f"n={n}: {applied} applied")
+    assert min(applied) >= (15 if n == 4096 else 5), n
+
+
 # ---- on the GPU --------------------------------------------------------------------------------------------------
 
 def _col(out, p, rows=slice(None)):
@@ -305,6 +352,45 @@ def test_parity_with_the_oracle(gpu_lib, files, n, k):
         assert applied == sum(w[4] == 1 for w in col) >= 10
 
 
+@pytest.fixture(scope="module")
+def edge_files(gpu_lib, tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("glm_score_multi_firth_edges")
+    return {n: _File(gpu_lib, tmp, n) for n, _ in EDGES}
+
+
+def _thinned_parity(f, k, stride):
+    """The thinned rows of file f at k covariates against the oracle at TOL_WIDTHS; `out` is glm_score_multi's bit for
+    bit.  Returns the applied rows per phenotype."""
+    Z = f.case.covariates(k)
+    got = f.ds.glm_score_multi_firth(f.Y, Z, firth_cutoff=CUTOFF)
+    _same_rows(got, f.ds.glm_score_multi(f.Y, Z), ctx=(f.n, k))
+    assert not got["firth"].any()
+    counts = []
+    for p, col in enumerate(oracle_thinned(f.n, k, stride)):
+        applied, worst = check_column(got, p, col, tol=TOL_WIDTHS, ctx=(f.n, k))
+        print(f"n={f.n} k={k} phenotype {p}: {applied} applied, worst {worst:.3g} (TOL {TOL_WIDTHS:.3g})")
+        assert applied == len(applied_rows(col))
+        counts.append(applied)
+    return counts
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", WIDTHS)
+def test_every_instantiated_width(gpu_lib, files, k):
+    """Column p (k + 2) of a block whose leading dimension is GlmScoreDenseLayout(pb, k).ld, for every width
+    GlmPadCovar returns at k = KP and one above the width below."""
+    counts = _thinned_parity(files[WIDTHS_N], k, WIDTHS_STRIDE)
+    assert min(counts) >= 3 and sum(counts) >= 15
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,stride", EDGES)
+def test_sample_count_edges(gpu_lib, edge_files, n, stride):
+    """n = 4096: the mask's words fill exactly one 4,096-sample step of the walk; n = 8209: a third step."""
+    counts = _thinned_parity(edge_files[n], EDGE_K, stride)
+    assert min(counts) >= (15 if n == 4096 else 5)
+
+
 @pytest.mark.gpu
 def test_the_same_bytes(gpu_lib, files):
     L = gpu_lib
@@ -356,8 +442,12 @@ def test_a_row_does_not_depend_on_the_range_the_block_the_chunk_or_the_scratch_b
     # 4,099 samples = 65,584; never less than one) and then bounds the chunk.  1 byte: a chunk of one variant (a part
     # of the range); 2,200,960 bytes = block + 70,000: 4,416 bytes are left, at 276 bytes per variant and phenotype
     # (k = 3) a chunk of 16 variants.
+    # 2,430,960 bytes = block_bytes + 300,000 (block_bytes = the block and the mask, 2,130,960; three quarters of the
+    # budget are still less, so pb_max = 1): n_groups = 300,000 / 4 * 3 / per_group = 225,000 / 65,584 = 3 workgroups,
+    # and the 300,000 - 3 x 65,584 = 103,248 bytes left bound the chunk at per_variant = 228 + 32 = 260 (k = 3): 397
+    # variants, so each workgroup walks its chunk's rows at a stride of 3.
     before = os.environ.get(SCRATCH_ENV)
-    for budget, lo, hi in ((1, 200, 260), (2_200_960, 0, c.f.m)):
+    for budget, lo, hi in ((1, 200, 260), (2_200_960, 0, c.f.m), (2_430_960, 0, c.f.m)):
         with pytest.MonkeyPatch.context() as mp:
             mp.setenv(SCRATCH_ENV, str(budget))
             _same(ds.glm_score_multi_firth(Y, Z, v_begin=lo, v_end=hi), _rows(whole, slice(lo, hi)), ctx=budget)

@@ -7,7 +7,9 @@ sparse route agrees on the rows whose base code is the dense b.
 
 TOL is 100 x the worst relative difference between the numpy model of the kernel's accumulation order
 (tools/glm_score_dense_spa_model.py) and the oracle on the parity inputs, MODEL_WORST below: the factor is
-test_glm_score_sparse_spa's, for device exp / log1p and fma contraction."""
+test_glm_score_sparse_spa's, for device exp / log1p and fma contraction.  The cases at every covariate width and at
+the sample-count edges are held to TOL_WIDTHS, the same rule on their own rows: MODEL_WORST_WIDTHS is what
+`python tools/glm_score_dense_spa_model.py --widths` prints."""
 
 import ctypes as C
 import functools
@@ -31,9 +33,16 @@ NAN = float("nan")
 NEW_SYMBOLS = ["pgh_glm_score_multi_spa"]
 MODEL_WORST = 1.41e-11  # printed by tools/glm_score_dense_spa_model.py
 TOL = 100 * MODEL_WORST
+# printed by tools/glm_score_dense_spa_model.py --widths: the width and sample-count cases below, on the rows they check
+MODEL_WORST_WIDTHS = 9.76e-12
+TOL_WIDTHS = 100 * MODEL_WORST_WIDTHS
 CUTOFF = 2.0
 PARITY_N = (257, 4099)
 PARITY_K = (0, 1, 3)
+WIDTHS, WIDTHS_N, WIDTHS_STRIDE = SP.WIDTHS, SP.WIDTHS_N, SP.WIDTHS_STRIDE
+# (n, row stride) at k = EDGE_K: exactly one 4,096-sample step of the walk, and a third step
+EDGES = ((4096, 1), (8209, 3))
+EDGE_K = 3
 SCRATCH_ENV = "PGH_GLM_SCORE_SCRATCH_BYTES"
 SUBSET_SHAPE = "stride4"  # every 16-code word of the row is cut: four of its samples are kept
 
@@ -76,6 +85,18 @@ def oracle_case(n, k):
     case = inputs(n)
     Z = case.covariates(k)
     return [oracle_column(case.x, case.geno, y, Z) for y in phenotypes(case)]
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_thinned(n, k, stride):
+    """oracle_case on every stride-th row: the width and sample-count cases (computed once)."""
+    case = inputs(n)
+    Z = case.covariates(k)
+    return [oracle_column(case.x, case.geno, y, Z, idx=range(0, case.m, stride)) for y in phenotypes(case)]
+
+
+def applied_rows(col):
+    return [w for w in col if w is not None and w[2] == 1]
 
 
 def check_column(got, p, want, tol=None, ctx=None):
@@ -161,6 +182,25 @@ def test_the_parity_inputs_reach_every_case_of_the_dense_rule(n, k):
             assert len(differ) >= 30, (n, k)
 
 
+@pytest.mark.parametrize("k", WIDTHS)
+def test_the_width_inputs_have_applied_rows_at_every_width(k):
+    """Conditions on the inputs, not on the device, so that a width cannot pass on rows that are left alone: on the
+    rows test_every_instantiated_width checks the oracle decides every row (it asserts where the contract does not,
+    and that every null model is fitted), each phenotype has 3 applied rows, the three have 15, and 4 have b = 2."""
+    applied = [applied_rows(col) for col in oracle_thinned(WIDTHS_N, k, WIDTHS_STRIDE)]
+    b2 = sum(w[3] == 2 for a in applied for w in a)
+    print(f"k={k}: {[len(a) for a in applied]} applied, {b2} with b = 2")
+    assert min(len(a) for a in applied) >= 3 and sum(len(a) for a in applied) >= 15 and b2 >= 4, k
+
+
+@pytest.mark.parametrize("n,stride", EDGES)
+def test_the_sample_count_edges_have_applied_rows(n, stride):
+    applied = [applied_rows(col) for col in oracle_thinned(n, EDGE_K, stride)]
+    b2 = sum(w[3] == 2 for a in applied for w in a)
+    print(f"n={n}: {[len(a) for a in applied]} applied, {b2} with b = 2")
+    assert min(len(a) for a in applied) >= (15 if n == 4096 else 5) and b2 >= 1, n
+
+
 # ---- on the GPU --------------------------------------------------------------------------------------------------
 
 def _col(out, p, rows=slice(None)):
@@ -226,6 +266,43 @@ def test_parity_with_the_oracle(gpu_lib, files, n, k):
         assert applied == sum(w[2] == 1 for w in col) >= 7
 
 
+@pytest.fixture(scope="module")
+def edge_files(gpu_lib, tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("glm_score_multi_spa_edges")
+    return {n: _File(gpu_lib, tmp, n) for n, _ in EDGES}
+
+
+def _thinned_parity(f, k, stride):
+    """The thinned rows of file f at k covariates against the oracle at TOL_WIDTHS; `out` is glm_score_multi's bit for
+    bit.  Returns the applied rows per phenotype."""
+    Z = f.case.covariates(k)
+    got = f.ds.glm_score_multi_spa(f.Y, Z, spa_cutoff=CUTOFF)
+    _same_rows(got, f.ds.glm_score_multi(f.Y, Z), ctx=(f.n, k))
+    counts = []
+    for p, col in enumerate(oracle_thinned(f.n, k, stride)):
+        applied, worst = check_column(got, p, col, tol=TOL_WIDTHS, ctx=(f.n, k))
+        print(f"n={f.n} k={k} phenotype {p}: {applied} applied, worst {worst:.3g} (TOL {TOL_WIDTHS:.3g})")
+        assert applied == len(applied_rows(col))
+        counts.append(applied)
+    return counts
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", WIDTHS)
+def test_every_instantiated_width(gpu_lib, files, k):
+    """GlmScoreDenseSpaKernel<KP> for every width GlmPadCovar returns, at k = KP and one above the width below."""
+    counts = _thinned_parity(files[WIDTHS_N], k, WIDTHS_STRIDE)
+    assert min(counts) >= 3 and sum(counts) >= 15
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,stride", EDGES)
+def test_sample_count_edges(gpu_lib, edge_files, n, stride):
+    """n = 4096: the mask's words fill exactly one 4,096-sample step of the walk; n = 8209: a third step."""
+    counts = _thinned_parity(edge_files[n], EDGE_K, stride)
+    assert min(counts) >= (15 if n == 4096 else 5)
+
+
 @pytest.mark.gpu
 def test_the_same_bytes(gpu_lib, files):
     f = files[257]
@@ -269,8 +346,12 @@ def test_a_triple_does_not_depend_on_the_range_the_block_the_chunk_or_the_scratc
     # after the block goes to one workgroup's stash first (16 bytes x 4,099 samples = 65,584; never less than one) and
     # then bounds the chunk at 293 bytes per variant and phenotype (k = 3).  1 byte: a chunk of one variant (a part
     # of the range); 2,200,960 bytes = block + 70,000: (70,000 - 65,584) / 293 = a chunk of 15 variants.
+    # 2,430,960 bytes = block_bytes + 300,000 (block_bytes = the block and the mask, 2,130,960; three quarters of the
+    # budget are still less, so pb_max = 1): n_groups = 300,000 / 4 * 3 / per_group = 225,000 / 65,584 = 3 workgroups,
+    # and the 300,000 - 3 x 65,584 = 103,248 bytes left bound the chunk at per_variant = 293: 352 variants, so each
+    # workgroup walks its chunk's rows at a stride of 3.
     before = os.environ.get(SCRATCH_ENV)
-    for budget, lo, hi in ((1, 200, 260), (2_200_960, 0, c.f.m)):
+    for budget, lo, hi in ((1, 200, 260), (2_200_960, 0, c.f.m), (2_430_960, 0, c.f.m)):
         with pytest.MonkeyPatch.context() as mp:
             mp.setenv(SCRATCH_ENV, str(budget))
             _same(ds.glm_score_multi_spa(Y, Z, v_begin=lo, v_end=hi), _rows(whole, slice(lo, hi)), ctx=budget)

@@ -4,7 +4,9 @@ the score's support) the states are equal and p_spa is within TOL in state 1; th
 for bit; a row's triple does not depend on the range, the window or the chunk.
 
 TOL is 100 x the worst relative difference between the numpy model of the kernel's accumulation order
-(tools/glm_score_spa_model.py) and the oracle on the parity test's inputs, MODEL_WORST below."""
+(tools/glm_score_spa_model.py) and the oracle on the parity test's inputs, MODEL_WORST below.  The cases at every
+covariate width are held to TOL_WIDTHS, the same rule on their own rows: MODEL_WORST_WIDTHS is what
+`python tools/glm_score_spa_model.py --widths` prints."""
 
 import math
 import os
@@ -23,6 +25,8 @@ NAN = float("nan")
 NEW_SYMBOLS = ["pgh_glm_score_sparse_spa"]
 MODEL_WORST = 8.13e-12  # printed by tools/glm_score_spa_model.py
 TOL = 100 * MODEL_WORST
+MODEL_WORST_WIDTHS = 1.78e-12  # printed by tools/glm_score_spa_model.py --widths: the width cases, on their rows
+TOL_WIDTHS = 100 * MODEL_WORST_WIDTHS
 CUTOFF = 2.0
 ROW_KEYS = ("beta", "se", "stat", "p", "a1_freq", "obs_ct", "errcode", "firth")
 
@@ -52,6 +56,13 @@ M_R = 600
 PARITY_N = (257, 4099)
 SEEDS = {257: 257, 4099: 4102}  # seeds whose matrices hold no row the contract leaves undecided (the oracle asserts it)
 PARITY_K = (0, 1, 3)
+# every padded covariate width of kGlmWidths at its exact value and one above the bucket below it
+# (test_glm_widths_chunks.WIDTHS without the k = 1 of PARITY_K), at the count that crosses a 4,096-sample step
+WIDTHS = [2, 4, 5, 8, 9, 12, 13, 16, 17, 20]
+WIDTHS_N = 4099
+WIDTHS_STRIDE = 5  # the rows the width cases check: the oracle's time is the test's
+# ... of this file: with the het-majority rows and the row beyond the wave form, so that both teams run at every width
+WIDTHS_ROWS = sorted(set(range(0, M_R, WIDTHS_STRIDE)) | set(HET_ROWS) | {LONG_ROW})
 
 
 class ParityInputs:
@@ -239,6 +250,27 @@ def test_oracle_saddlepoint_is_closer_to_the_exact_p_than_the_normal_p():
     assert closer >= EXACT_SHARE * total
 
 
+@pytest.mark.parametrize("k", WIDTHS)
+def test_the_width_inputs_have_applied_rows_of_both_teams(k):
+    """Conditions on the inputs, not on the device: at every width the null model is fitted, the oracle decides every
+    checked row (it asserts where the contract does not), and with every row held sparse the applied rows lie on both
+    sides of the wave / workgroup threshold of 1,024 entries."""
+    case = ParityInputs(WIDTHS_N)
+    nul = O.Null(case.y, case.covariates(k))
+    assert nul.status is None
+    for max_minor in (case.n, 0):
+        entries = []
+        for i in WIDTHS_ROWS:
+            base, dense_form = S.row_form(case.geno[i], max_minor)
+            row, p_spa, state = S.spa_row(case.x[i], case.geno[i], nul, base, dense_form, CUTOFF)
+            if state == 1:
+                entries.append(int(S.entry_mask(case.geno[i], base, dense_form).sum()))
+        print(f"k={k} max_minor={max_minor}: {len(entries)} applied, {min(entries)} to {max(entries)} entries")
+        assert len(entries) >= 3, (k, max_minor)
+        if max_minor:
+            assert min(entries) <= 1024 < max(entries), (k, entries)
+
+
 # ---- on the GPU --------------------------------------------------------------------------------------------------
 
 def _same_rows(a, b, ctx=None):
@@ -320,6 +352,29 @@ def test_parity_with_the_oracle_for_every_form(gpu_lib, spa_files, n, k):
                 assert abs(pa - pb) <= 2 * TOL * pb, (n, k, a, b, r, pa, pb)
                 both += 1
         assert both > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", WIDTHS)
+def test_every_instantiated_width(gpu_lib, spa_files, k):
+    """GlmScoreSpaKernel<KP, TEAM> for every width GlmPadCovar returns, at k = KP and one above the width below: with
+    every row held sparse and under the default rule."""
+    f = spa_files[WIDTHS_N]
+    Z = f.covariates(k)
+    nul = O.Null(f.y, Z)
+    assert nul.status is None
+    for max_minor in (f.n, 0):
+        sp = f.sparse(max_minor=max_minor)
+        got = sp.glm_score_sparse_spa(f.y, Z, cutoff=CUTOFF)
+        _same_rows(got, sp.glm_score_sparse(f.y, Z), ctx=(k, max_minor))
+        s = S.check_spa(got, f.x, f.geno, nul, max_minor, CUTOFF, TOL_WIDTHS, idx=WIDTHS_ROWS)
+        print(f"k={k} max_minor={max_minor}: {s['applied']} applied, {s['failed']} failed, worst {s['worst']:.3g} "
+              f"(TOL {TOL_WIDTHS:.3g})")
+        assert s["applied"] >= 3
+        if max_minor:
+            entries = [r[3] for r in s["rows"]]
+            assert min(entries) <= 1024 < max(entries)
+        sp.close()
 
 
 @pytest.mark.gpu

@@ -439,6 +439,44 @@ def test_parity_with_the_oracle_at_a_wide_sample_count(gpu_lib, files):
     assert _parity(gpu_lib, files(SS.N_WIDE), 2, 0.2, True, max_minors=(0,)) >= 9
 
 
+# every padded covariate width of kGlmWidths at its exact value and one above the bucket below it
+# (test_glm_widths_chunks.WIDTHS: no case above has k = 1)
+WIDTHS = [1, 2, 4, 5, 8, 9, 12, 13, 16, 17, 20]
+WIDTHS_N = 4099
+# 12 of set_list's sets: singletons of a hom-ref, a het, a missing and a hom-alt majority, the repeat, the skip path,
+# all linked, the mixed majorities, all missing, no carrier in S, the largest, (zero weights)
+WIDTH_SETS = (0, 2, 4, 5, 6, 7, 8, 9, 10, 14, 16, 17)
+
+
+def width_case(codes, n, k):
+    """(sets, weights) of the width cases: set_list's and set_weights' draws, the 12 sets of WIDTH_SETS."""
+    all_sets, lone = set_list(codes, n)
+    w_all = set_weights(all_sets, 100 * n + k)
+    off_all, _ = _csr(all_sets)
+    sets = [all_sets[i] for i in WIDTH_SETS]
+    w = np.concatenate([w_all[int(off_all[i]):int(off_all[i + 1])] for i in WIDTH_SETS])
+    return sets, w, lone
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", WIDTHS)
+def test_every_instantiated_width(gpu_lib, files, k):
+    """The kernel's template <int KP> for every width GlmPadCovar returns, at k = KP and one above the width below:
+    the parity test's oracle and check on 12 weighted sets, every row held sparse."""
+    f = files(WIDTHS_N)
+    sets, w, lone = width_case(f.codes, f.n, k)
+    off, vidx = _csr(sets)
+    y, Z = phenotype(f, lone, k, 0.2, 37 * f.n + k + 200)
+    sp, forms = f.sparse(f.n)
+    rows, lam = sp.skat_sparse(y, off, vidx, w, Z, return_lambda=True)
+    exp = expected(f, forms, sets, w, y, Z)
+    check(gpu_lib, rows, lam, exp, off, ctx=k)
+    codes = [e["errcode"] for e, _ in exp]
+    print(f"k={k}: {codes}")
+    assert codes[8] == codes[9] == "CONST_ALLELE" and codes[11] == "ZERO_VARIANCE"
+    assert sum(c is None for c in codes) >= 8 and codes[7] is None  # the mixed-majority set is decided
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", ["word_block", "stride4"])
 def test_parity_under_a_sample_subset(gpu_lib, files, shape):

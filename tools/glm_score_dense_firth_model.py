@@ -11,7 +11,8 @@ five chains per thread over the stash at the workgroup's stride and the same red
 step with its 64 evaluations.  A multiply and an add stand where the kernel has an fma.  Which rows are applied is the
 oracle's decision (it refuses a |stat| within 1e-6 of the cutoff).
 
-usage: python tools/glm_score_dense_firth_model.py"""
+usage: python tools/glm_score_dense_firth_model.py [--widths]
+--widths: the inputs of the test's width and sample-count cases instead (its MODEL_WORST_WIDTHS)."""
 
 import math
 import os
@@ -89,35 +90,47 @@ def model_row(codes, nul):
     return phase_b(x, mu, g)
 
 
-def main():
+def run(cases):
+    """cases: (n, k, row stride).  Prints a line per phenotype; returns (worst, evaluations)."""
     import test_glm_score_multi_firth as T
 
     worst_all, evals_all = 0.0, []
-    for n in T.PARITY_N:
+    for n, k, stride in cases:
         case = T.inputs(n)
         Y = T.phenotypes(case)
-        for k in T.PARITY_K:
-            Z = case.covariates(k)
-            for p, y in enumerate(Y):
-                nul = O.Null(y, Z)
-                assert nul.status is None
-                worst, applied, failed, separated, flipped = [0.0, 0.0, 0.0], 0, 0, 0, 0
-                for i in range(len(case.geno)):
-                    row, beta, se, pv, state, info = F.firth_row(case.x[i], case.geno[i], nul, T.CUTOFF)
-                    if state == 0:
-                        continue
-                    mb, mse, mp, evals = model_row(case.geno[i], nul)
-                    assert (mb is None) == (state == 2), (n, k, p, i, state, mb, evals, row)
-                    failed += state == 2
-                    if state == 1:
-                        worst = [max(a, b) for a, b in zip(worst, (abs(mb - beta) / se, abs(mse - se) / se, abs(mp - pv) / pv))]
-                        applied += 1
-                        separated += info["separated"]
-                        flipped += beta * row["beta"] < 0
-                        evals_all.append(evals)
-                print(f"n={n} k={k} phenotype {p}: {applied} applied ({separated} separated, {flipped} of the other sign), "
-                      f"{failed} failed, worst beta {worst[0]:.3g} se {worst[1]:.3g} p {worst[2]:.3g}", flush=True)
-                worst_all = max(worst_all, *worst)
+        Z = case.covariates(k)
+        for p, y in enumerate(Y):
+            nul = O.Null(y, Z)
+            assert nul.status is None
+            worst, applied, failed, separated, flipped = [0.0, 0.0, 0.0], 0, 0, 0, 0
+            for i in range(0, len(case.geno), stride):
+                row, beta, se, pv, state, info = F.firth_row(case.x[i], case.geno[i], nul, T.CUTOFF)
+                if state == 0:
+                    continue
+                mb, mse, mp, evals = model_row(case.geno[i], nul)
+                assert (mb is None) == (state == 2), (n, k, p, i, state, mb, evals, row)
+                failed += state == 2
+                if state == 1:
+                    worst = [max(a, b) for a, b in zip(worst, (abs(mb - beta) / se, abs(mse - se) / se, abs(mp - pv) / pv))]
+                    applied += 1
+                    separated += info["separated"]
+                    flipped += beta * row["beta"] < 0
+                    evals_all.append(evals)
+            print(f"n={n} k={k} phenotype {p}: {applied} applied ({separated} separated, {flipped} of the other sign), "
+                  f"{failed} failed, worst beta {worst[0]:.3g} se {worst[1]:.3g} p {worst[2]:.3g}", flush=True)
+            worst_all = max(worst_all, *worst)
+    return worst_all, evals_all
+
+
+def main():
+    import test_glm_score_multi_firth as T
+
+    if "--widths" in sys.argv[1:]:
+        # the inputs of test_every_instantiated_width and test_sample_count_edges, on the rows they check
+        cases = [(T.WIDTHS_N, k, T.WIDTHS_STRIDE) for k in T.WIDTHS] + [(n, T.EDGE_K, stride) for n, stride in T.EDGES]
+    else:
+        cases = [(n, k, 1) for n in T.PARITY_N for k in T.PARITY_K]
+    worst_all, evals_all = run(cases)
     print(f"worst difference over |delta beta| / se, |delta se| / se, |delta p| / p: {worst_all:.3g}; evaluations per "
           f"applied row: mean {np.mean(evals_all):.2f}, max {max(evals_all)}")
 

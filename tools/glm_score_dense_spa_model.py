@@ -11,7 +11,8 @@ chain over the covariates; mu recovered from r; V_E as one chain per thread over
 over the stash in sample order with the workgroup as the team, which is tools/glm_score_spa_model.py's phase_b.  A
 multiply and an add stand where the kernel has an fma.
 
-usage: python tools/glm_score_dense_spa_model.py"""
+usage: python tools/glm_score_dense_spa_model.py [--widths]
+--widths: the inputs of the test's width and sample-count cases instead (its MODEL_WORST_WIDTHS)."""
 
 import math
 import os
@@ -77,36 +78,48 @@ def model_row(codes, nul, cutoff):
     return p, total, 1, evals
 
 
-def main():
+def run(cases):
+    """cases: (n, k, row stride).  Prints a line per phenotype; returns (worst, evaluations)."""
     import test_glm_score_multi_spa as T
 
     worst_all, evals_all = 0.0, []
-    for n in T.PARITY_N:
-        case = T.ParityInputs(n)
+    for n, k, stride in cases:
+        case = T.inputs(n)
         Y = T.phenotypes(case)
-        for k in T.PARITY_K:
-            Z = case.covariates(k)
-            for p, y in enumerate(Y):
-                nul = O.Null(y, Z)
-                assert nul.status is None
-                worst, applied, differ, failed, b2 = 0.0, 0, 0, 0, 0
-                for i in range(len(case.geno)):
-                    b = dense_base(case.geno[i], nul.in_s)
-                    row, p_spa, state = S.spa_row(case.x[i], case.geno[i], nul, b, False, T.CUTOFF)
-                    if row["errcode"] is not None:
-                        continue
-                    _, mp, mstate, evals = model_row(case.geno[i], nul, T.CUTOFF)
-                    assert mstate == state, (n, k, p, i, b, state, mstate, evals, row)
-                    if state == 1:
-                        worst = max(worst, abs(mp - p_spa) / p_spa)
-                        applied += 1
-                        b2 += b == 2
-                        differ += not 0.5 <= p_spa / row["p"] <= 2
-                        evals_all.append(evals)
-                    failed += state == 2
-                print(f"n={n} k={k} phenotype {p}: {applied} applied ({b2} with b = 2), {differ} beyond 2x, {failed} failed, "
-                      f"worst {worst:.3g}", flush=True)
-                worst_all = max(worst_all, worst)
+        Z = case.covariates(k)
+        for p, y in enumerate(Y):
+            nul = O.Null(y, Z)
+            assert nul.status is None
+            worst, applied, differ, failed, b2 = 0.0, 0, 0, 0, 0
+            for i in range(0, len(case.geno), stride):
+                b = dense_base(case.geno[i], nul.in_s)
+                row, p_spa, state = S.spa_row(case.x[i], case.geno[i], nul, b, False, T.CUTOFF)
+                if row["errcode"] is not None:
+                    continue
+                _, mp, mstate, evals = model_row(case.geno[i], nul, T.CUTOFF)
+                assert mstate == state, (n, k, p, i, b, state, mstate, evals, row)
+                if state == 1:
+                    worst = max(worst, abs(mp - p_spa) / p_spa)
+                    applied += 1
+                    b2 += b == 2
+                    differ += not 0.5 <= p_spa / row["p"] <= 2
+                    evals_all.append(evals)
+                failed += state == 2
+            print(f"n={n} k={k} phenotype {p}: {applied} applied ({b2} with b = 2), {differ} beyond 2x, {failed} failed, "
+                  f"worst {worst:.3g}", flush=True)
+            worst_all = max(worst_all, worst)
+    return worst_all, evals_all
+
+
+def main():
+    import test_glm_score_multi_spa as T
+
+    if "--widths" in sys.argv[1:]:
+        # the inputs of test_every_instantiated_width and test_sample_count_edges, on the rows they check
+        cases = [(T.WIDTHS_N, k, T.WIDTHS_STRIDE) for k in T.WIDTHS] + [(n, T.EDGE_K, stride) for n, stride in T.EDGES]
+    else:
+        cases = [(n, k, 1) for n in T.PARITY_N for k in T.PARITY_K]
+    worst_all, evals_all = run(cases)
     print(f"worst relative difference of p_spa: {worst_all:.3g}; evaluations per applied row: mean "
           f"{np.mean(evals_all):.2f}, max {max(evals_all)}")
 

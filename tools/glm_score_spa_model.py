@@ -10,7 +10,8 @@ per lane at the team's stride, a butterfly over the 64 lanes and the waves in or
 tail, and the safeguarded Newton iteration with its 64 evaluations.  A multiply and an add stand where the kernel has an
 fma.
 
-usage: python tools/glm_score_spa_model.py"""
+usage: python tools/glm_score_spa_model.py [--widths]
+--widths: the inputs of the test's width cases instead (its MODEL_WORST_WIDTHS)."""
 
 import math
 import os
@@ -164,16 +165,17 @@ def model_row(codes, nul, base, dense_form, cutoff):
 def main():
     import test_glm_score_sparse_spa as T
 
+    widths = "--widths" in sys.argv[1:]
     worst_all, evals_all = 0.0, []
-    for n in T.PARITY_N:
+    for n in (T.WIDTHS_N,) if widths else T.PARITY_N:
         case = T.ParityInputs(n)
-        for k in T.PARITY_K:
+        for k in T.WIDTHS if widths else T.PARITY_K:
             y, Z = case.y, case.covariates(k)
             nul = O.Null(y, Z)
             assert nul.status is None
-            for max_minor in (0, 1, n):
+            for max_minor in (0, n) if widths else (0, 1, n):
                 worst, applied, differ, failed, kinds = 0.0, 0, 0, 0, set()
-                for i in range(len(case.geno)):
+                for i in T.WIDTHS_ROWS if widths else range(len(case.geno)):
                     base, dense_form = S.row_form(case.geno[i], max_minor)
                     row, p_spa, state = S.spa_row(case.x[i], case.geno[i], nul, base, dense_form, T.CUTOFF)
                     if row["errcode"] is not None:
@@ -192,6 +194,8 @@ def main():
                 worst_all = max(worst_all, worst)
     print(f"worst relative difference of p_spa: {worst_all:.3g}; evaluations per applied row: mean "
           f"{np.mean(evals_all):.2f}, max {max(evals_all)}")
+    if widths:
+        return
     # the long-row test's inputs: its dense-form rows of more than 10,000 entries
     case = T.long_inputs()
     nul = O.Null(case.y, case.covariates(T.LONG_K))
