@@ -349,14 +349,17 @@ void pgh_trim_device_cache(void);
 int pgh_unpack_range(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end, int8_t *out,
                      uint64_t *validity, int missing_code, char *errbuf);
 /* d_out row stride = out_pitch bytes (>= n_out, multiple of 16); d_validity row
- * stride = ceil(n_out/64) words; either may be NULL. */
+ * stride = ceil(n_out/64) words; either may be NULL.  Of a d_out row the call writes the
+ * first ceil(n_out/16)*16 bytes (what lies past n_out there is unspecified) and leaves the
+ * rest of the pitch untouched. */
 int pgh_unpack_range_dev(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                          void *d_out, size_t out_pitch, void *d_validity, int missing_code, void *stream,
                          char *errbuf);
 
 /* Measurement aid for pgh_unpack_range_dev: a bare kernel with that kernel's traffic shape -- a lane reads 16 bytes
  * and writes 64 + 8 -- and no arithmetic, on the current device.  d_src: n_vec x 16 B, d_dst: n_vec x 64 B, d_val:
- * n_vec x 8 B.  bench.py times it beside the unpack and reports it as roofline.store_ceiling. */
+ * n_vec x 8 B; n_vec a multiple of 64 (a wave stores whole 4 KiB tiles of d_dst; PGH_ERR_ARG otherwise).  bench.py
+ * times it beside the unpack and reports it as roofline.store_ceiling. */
 int pgh_probe_unpack_shape_dev(const void *d_src, size_t n_vec, void *d_dst, void *d_val, void *stream, char *errbuf);
 
 /* plink_score phase 1 (src/plink_score.cpp:575-654) for n_scored variants and
@@ -384,7 +387,11 @@ int pgh_score_counts(const pgh_dataset *ds, const pgh_subset *subset, uint32_t n
                      const double *weights, const uint8_t *flip, uint32_t n_cols, int mode, const uint32_t (*counts)[4],
                      double *score_sum, double *dosage_sum, uint32_t *allele_ct, char *errbuf);
 /* Device form: raw-sample order (no compaction), outputs are caller-owned device
- * buffers of raw_sample_ct rows, overwritten. */
+ * buffers of raw_sample_ct rows, overwritten -- every row, the rows of samples outside
+ * the subset too.  Those are not zeroed: the kernels score every raw sample, so such a
+ * row holds that sample's own sums and allele count under the per-variant means,
+ * variances and skips of the included samples.  A caller that wants the included
+ * samples reads the rows the subset names (the host forms compact exactly those). */
 int pgh_score_dev(const pgh_dataset *ds, const pgh_subset *subset, uint32_t n_scored, const uint32_t *vidx,
                   const double *weights, const uint8_t *flip, uint32_t n_cols, int mode, void *d_score_sum,
                   void *d_dosage_sum, void *d_allele_ct, void *stream, char *errbuf);

@@ -257,6 +257,10 @@ extern "C" int pgh_probe_unpack_shape_dev(const void *d_src, size_t n_vec, void 
 		SetErr(errbuf, "null argument");
 		return PGH_ERR_ARG;
 	}
+	if (n_vec % 64 != 0) { // a wave stores whole 4 KiB tiles: a ragged last one would run past d_dst
+		SetErr(errbuf, "n_vec must be a multiple of 64");
+		return PGH_ERR_ARG;
+	}
 	PGH_HIP(pgh::LaunchUnpackShapeProbe(d_src, n_vec, d_dst, d_val, static_cast<hipStream_t>(stream)), "store probe");
 	return PGH_OK;
 }

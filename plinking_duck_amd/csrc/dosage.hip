@@ -415,6 +415,10 @@ __global__ __launch_bounds__(256) void k_dosage_sums(const uint8_t *__restrict__
 	const uint4 *row128 = reinterpret_cast<const uint4 *>(rows + static_cast<uint64_t>(lv) * pitch);
 	const int32_t r = dos.row_of ? dos.row_of[lv] : -1;
 	const uint64_t *present = r >= 0 ? dos.present + static_cast<uint64_t>(r) * dos.words : nullptr;
+	// a variant without a track has r == -1: neither val_off[r] nor rank[r * words + w] may be touched for it (each is
+	// an allocation of its own, and what lies in front of it need not be mapped)
+	const uint16_t *row_vals = r >= 0 ? dos.values + dos.val_off[r] : nullptr;
+	const uint32_t *row_rank = r >= 0 ? dos.rank + static_cast<uint64_t>(r) * dos.words : nullptr;
 	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
 	uint32_t het = 0, hom_alt = 0, called = 0, n_explicit = 0, vsum = 0;
 	uint64_t vssq = 0;
@@ -437,8 +441,8 @@ __global__ __launch_bounds__(256) void k_dosage_sums(const uint8_t *__restrict__
 			called += __popc(kk & ~(lo & hi));
 		}
 		if (HAS_INCLUDE) {
-			uint64_t take = e & m;
-			const uint16_t *vals = dos.values + dos.val_off[r] + dos.rank[static_cast<uint64_t>(r) * dos.words + w];
+			uint64_t take = e & m; // e == 0 without a track
+			const uint16_t *vals = take ? row_vals + row_rank[w] : nullptr;
 			while (take) {
 				const uint32_t b = static_cast<uint32_t>(__ffsll(static_cast<long long>(take))) - 1u;
 				const uint32_t u = vals[__popcll(e & ((1ull << b) - 1ull))];

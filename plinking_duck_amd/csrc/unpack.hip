@@ -115,7 +115,8 @@ __global__ __launch_bounds__(256) void k_unpack_wide(const uint8_t *__restrict__
 		if (out) {
 			uint8_t *orow = reinterpret_cast<uint8_t *>(out) + static_cast<uint64_t>(i) * out_pitch +
 			                static_cast<uint64_t>(wave_col0) * 64u;
-			const uint64_t row_left = out_pitch - static_cast<uint64_t>(wave_col0) * 64u;
+			// the row's own bytes, ceil16(sample_ct): what lies between them and out_pitch belongs to the caller
+			const uint64_t row_left = (static_cast<uint64_t>(sample_ct) + 15u) / 16u * 16u - static_cast<uint64_t>(wave_col0) * 64u;
 #pragma unroll
 			for (int k = 0; k < 4; k++) {
 				const uint32_t piece = k * 64u + lane;

@@ -491,6 +491,12 @@ def hwe_lnp_batch_dev(d_counts: int, n: int, d_ln_p: int, midp: bool = False, st
     _check(_lib.pgh_hwe_lnp_batch_dev(d_counts, n, 1 if midp else 0, d_ln_p, stream, eb), eb)
 
 
+def ld_pairs_status():
+    """pgh_ld_pairs_status: waits for the calling thread's last ld_pairs(_dev) launch; raises if it refused a task."""
+    eb = _errbuf()
+    _check(_lib.pgh_ld_pairs_status(eb), eb)
+
+
 def probe_unpack_shape_dev(d_src: int, n_vec: int, d_dst: int, d_val: int, stream: int = 0):
     eb = _errbuf()
     _check(_lib.pgh_probe_unpack_shape_dev(d_src, n_vec, d_dst, d_val, stream, eb), eb)
