@@ -224,20 +224,14 @@ int GlmOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, ui
 	std::vector<uint32_t> flist;
 	std::vector<pgh::GlmState> hst;
 	HostSourceFence fence(st); // sg, dos, flist feed asynchronous uploads
-	int rc = GlmUpload(sg, d_y, d_z, nullptr, nullptr, st, "glm", "phenotype", errbuf);
-	if (rc != PGH_OK) {
-		return rc;
-	}
+	PGH_TRY(GlmUpload(sg, d_y, d_z, nullptr, nullptr, st, "glm", "phenotype", errbuf));
 	if (!logistic) {
 		PGH_HIP(pgh::LaunchGlmGram(nullptr, 1, nullptr, 0, n_y, n_out, d_y, d_z, kp, k, d_gram, st), "glm gram kernel");
 	}
 	for (uint32_t c0 = 0; c0 < nv_all; c0 += chunk) {
 		const uint32_t nv = std::min(chunk, nv_all - c0);
 		pgh::GlmX g;
-		rc = dos.Chunk(c0, nv, d_slot, d_list, d_dos, st, "glm", &g, errbuf);
-		if (rc != PGH_OK) {
-			return rc;
-		}
+		PGH_TRY(dos.Chunk(c0, nv, d_slot, d_list, d_dos, st, "glm", &g, errbuf));
 		if (!logistic) {
 			PGH_HIP(pgh::LaunchGlmSums(g, nv, d_y, d_z, kp, d_sums, st), "glm sums kernel");
 			PGH_HIP(pgh::LaunchGlmGram(&g, nv, d_sums, ns, n_y, n_out, d_y, d_z, kp, k, d_corr, st), "glm correction kernel");
@@ -377,10 +371,7 @@ int GlmMultiLinear(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_b
 	std::vector<double> hyb(static_cast<size_t>(n_out) * pb_max);
 	std::vector<pgh_glm_row> hrows(static_cast<size_t>(chunk) * pb_max);
 	HostSourceFence fence(st); // sg, dos, hyb feed asynchronous uploads
-	int rc = GlmUpload(sg, d_pat, d_z, nullptr, nullptr, st, "glm_multi", "pattern", errbuf);
-	if (rc != PGH_OK) {
-		return rc;
-	}
+	PGH_TRY(GlmUpload(sg, d_pat, d_z, nullptr, nullptr, st, "glm_multi", "pattern", errbuf));
 	PGH_HIP(pgh::LaunchGlmGram(nullptr, 1, nullptr, 0, n_y, n_out, d_pat, d_z, kp, k, d_gram, st), "glm_multi gram kernel");
 	for (uint32_t b0 = 0; b0 < np; b0 += pb_max) {
 		const uint32_t pb = std::min(pb_max, np - b0);
@@ -399,10 +390,7 @@ int GlmMultiLinear(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_b
 		for (uint32_t c0 = 0; c0 < nv_all; c0 += chunk) {
 			const uint32_t nv = std::min(chunk, nv_all - c0);
 			pgh::GlmX g;
-			rc = dos.Chunk(c0, nv, d_slot, d_list, d_dos, st, "glm_multi", &g, errbuf);
-			if (rc != PGH_OK) {
-				return rc;
-			}
+			PGH_TRY(dos.Chunk(c0, nv, d_slot, d_list, d_dos, st, "glm_multi", &g, errbuf));
 			PGH_HIP(pgh::LaunchGlmSums(g, nv, d_pat, d_z, kp, d_sums, st), "glm_multi sums kernel");
 			PGH_HIP(pgh::LaunchGlmMultiXy(g, nv, d_yb, pb, d_sxy, st), "glm_multi genotype x phenotype kernel");
 			PGH_HIP(pgh::LaunchGlmMultiCorr(g, nv, d_sums, n_y, d_pat, d_yb, pb, d_z, kp, k, d_cs, d_cp, st),
@@ -432,11 +420,8 @@ int GlmMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begi
 	if (model == PGH_GLM_LOGISTIC) {
 		std::vector<pgh_glm_row> rows(nv);
 		for (uint32_t p = 0; p < n_pheno; p++) {
-			const int rc = GlmOne(ds, subset, v_begin, v_end, phenotypes + static_cast<size_t>(p) * n_out, k, covariates,
-			                      model, firth, rows.data(), errbuf);
-			if (rc != PGH_OK) {
-				return rc;
-			}
+			PGH_TRY(GlmOne(ds, subset, v_begin, v_end, phenotypes + static_cast<size_t>(p) * n_out, k, covariates, model, firth,
+			               rows.data(), errbuf));
 			for (uint32_t v = 0; v < nv; v++) {
 				out[static_cast<size_t>(v) * n_pheno + p] = rows[v];
 			}
@@ -444,10 +429,7 @@ int GlmMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begi
 		return PGH_OK;
 	}
 	for (const std::vector<uint32_t> &idx : GlmPatternGroups(n_pheno, phenotypes, n_out)) {
-		const int rc = GlmMultiLinear(ds, subset, v_begin, v_end, n_pheno, phenotypes, idx, k, covariates, out, errbuf);
-		if (rc != PGH_OK) {
-			return rc;
-		}
+		PGH_TRY(GlmMultiLinear(ds, subset, v_begin, v_end, n_pheno, phenotypes, idx, k, covariates, out, errbuf));
 	}
 	return PGH_OK;
 }
@@ -457,10 +439,7 @@ int GlmMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begi
 int GlmCheckCommon(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end, uint32_t n_pheno,
                    const double *phenotypes, uint32_t n_covar, const double *covariates, int model,
                    const pgh_glm_row *out, char *errbuf) {
-	int rc = CheckRange(ds, v_begin, v_end, errbuf);
-	if (rc != PGH_OK) {
-		return rc;
-	}
+	PGH_TRY(CheckRange(ds, v_begin, v_end, errbuf));
 	if (model != PGH_GLM_LINEAR && model != PGH_GLM_LOGISTIC) {
 		SetErr(errbuf, "model must be PGH_GLM_LINEAR or PGH_GLM_LOGISTIC");
 		return PGH_ERR_ARG;
@@ -474,13 +453,8 @@ int GlmCheckCommon(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_b
 		                   std::to_string(n_covar));
 		return PGH_ERR_ARG;
 	}
-	rc = CheckSubset(ds, subset, errbuf);
-	if (rc == PGH_OK) {
-		rc = RefuseEmptySubset(subset, errbuf);
-	}
-	if (rc != PGH_OK) {
-		return rc;
-	}
+	PGH_TRY(CheckSubset(ds, subset, errbuf));
+	PGH_TRY(RefuseEmptySubset(subset, errbuf));
 	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct;
 	if ((n_out && !phenotypes) || (n_covar && n_out && !covariates) || (v_end > v_begin && !out)) {
 		SetErr(errbuf, "null argument");
@@ -551,10 +525,7 @@ int GlmSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_beg
 
 	std::vector<pgh_glm_row> hdrows(dense_max);
 	HostSourceFence fence(st); // sg feeds asynchronous uploads
-	const int rc = GlmUpload(sg, d_y, d_z, d_yr, d_zr, st, "glm_sparse", "phenotype", errbuf);
-	if (rc != PGH_OK) {
-		return rc;
-	}
+	PGH_TRY(GlmUpload(sg, d_y, d_z, d_yr, d_zr, st, "glm_sparse", "phenotype", errbuf));
 	PGH_HIP(pgh::LaunchGlmGram(nullptr, 1, nullptr, 0, n_y, n_out, d_y, d_z, kp, k, d_gram, st), "glm_sparse gram kernel");
 	for (uint32_t c0 = 0; c0 < nv_all; c0 += chunk) {
 		const uint32_t nv = std::min(chunk, nv_all - c0);
@@ -657,11 +628,6 @@ struct GlmScoreSpaArgs {
 	uint8_t *state;
 };
 constexpr uint64_t kSpaStashBytes = 256ull << 20;
-// pgh_glm_score_multi_firth's own arguments.
-struct GlmScoreFirthArgs {
-	double cutoff;
-	pgh_glm_firth_row *rows;
-};
 
 int GlmScoreSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                       const double *phenotype, uint32_t k, const double *covariates, pgh_glm_row *out, char *errbuf,
@@ -697,13 +663,8 @@ int GlmScoreSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t 
 	uint8_t *d_stash = nullptr;
 	uint32_t n_groups = 0;
 	if (spa) {
-		int device = 0, cus = 0;
-		PGH_HIP(hipGetDevice(&device), "glm_score_sparse_spa device");
-		PGH_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device),
-		        "glm_score_sparse_spa device attribute");
 		const uint64_t per_group = pgh::GlmScoreSpaStashPerGroup(n_raw);
-		n_groups = static_cast<uint32_t>(std::min<uint64_t>(std::min<uint64_t>(chunk, 4ull * static_cast<uint32_t>(std::max(cus, 1))),
-		                                                    std::max<uint64_t>(1, kSpaStashBytes / per_group)));
+		PGH_TRY(StashGroups(chunk, 4, per_group, kSpaStashBytes, &n_groups, "glm_score_sparse_spa", errbuf));
 		lay.Add(&so.t, c * (kp + 3));
 		lay.Add(&so.p_spa, c);
 		lay.Add(&so.state, c);
@@ -717,19 +678,13 @@ int GlmScoreSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t 
 	}
 
 	HostSourceFence fence(st); // sg feeds asynchronous uploads
-	int rc = GlmUpload(sg, d_y, d_z, d_r, d_zr, st, "glm_score_sparse", "phenotype", errbuf);
-	if (rc != PGH_OK) {
-		return rc;
-	}
+	PGH_TRY(GlmUpload(sg, d_y, d_z, d_r, d_zr, st, "glm_score_sparse", "phenotype", errbuf));
 	if (subset) {
 		PGH_HIP(hipMemsetAsync(d_w, 0, 8ull * nr, st), "glm_score_sparse weight clear");
 	}
 	int null_status = PGH_GLM_OK;
-	rc = GlmScoreNullFit(n_out, d_y, d_z, kp, k, subset ? subset->d_sel : nullptr, n_y >= k + 3, d_r, d_w, d_part, d_hg, st,
-	                     &null_status, errbuf);
-	if (rc != PGH_OK) {
-		return rc;
-	}
+	PGH_TRY(GlmScoreNullFit(n_out, d_y, d_z, kp, k, subset ? subset->d_sel : nullptr, n_y >= k + 3, d_r, d_w, d_part, d_hg, st,
+	                        &null_status, errbuf));
 	for (uint32_t c0 = 0; c0 < nv_all; c0 += chunk) {
 		const uint32_t nv = std::min(chunk, nv_all - c0);
 		PGH_HIP(pgh::LaunchGlmScoreSparse(ds->Sparse(), l_begin + c0, nv, d_r, d_w, d_zr, kp, k, n_y, d_hg, d_sums, d_hgn, st),
@@ -757,17 +712,6 @@ const char *const kBurdenScratchEnv = "PGH_BURDEN_SCRATCH_BYTES";
 
 // The byte budget of the workgroups' private vectors (read at every call; the result does not depend on it: it only
 // bounds how many sets are in flight, and anything below one vector still gives one workgroup).
-uint64_t EnvBytes(const char *name, uint64_t fallback) {
-	const char *s = std::getenv(name);
-	if (s && *s) {
-		char *end = nullptr;
-		const unsigned long long v = std::strtoull(s, &end, 10);
-		if (end && *end == '\0') {
-			return v;
-		}
-	}
-	return fallback;
-}
 uint64_t BurdenScratchBytes() {
 	return EnvBytes(kBurdenScratchEnv, kBurdenScratchBytes);
 }
@@ -785,13 +729,9 @@ int BurdenSparseOne(const pgh_dataset *ds, const pgh_subset *subset, const doubl
 	const uint32_t n_y = sg.n_y;
 
 	// the grid: a private vector per workgroup within the byte budget, at most eight workgroups per compute unit
-	int device = 0, cus = 0;
-	PGH_HIP(hipGetDevice(&device), "burden_sparse device");
-	PGH_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device), "burden_sparse device attribute");
 	const uint64_t per_group = pgh::BurdenScratchPerGroup(n_raw);
-	const uint32_t n_groups = static_cast<uint32_t>(std::min<uint64_t>(
-	    std::min<uint64_t>(n_sets, 8ull * static_cast<uint32_t>(std::max(cus, 1))),
-	    std::max<uint64_t>(1, BurdenScratchBytes() / per_group)));
+	uint32_t n_groups = 0;
+	PGH_TRY(StashGroups(n_sets, 8, per_group, BurdenScratchBytes(), &n_groups, "burden_sparse", errbuf));
 	DevBuf vectors;
 	PGH_HIP(vectors.Alloc(per_group * n_groups), "burden_sparse vectors");
 
@@ -828,10 +768,7 @@ int BurdenSparseOne(const pgh_dataset *ds, const pgh_subset *subset, const doubl
 	std::vector<pgh_glm_row> rows(n_sets);
 	std::vector<pgh::BurdenAux> aux(n_sets);
 	HostSourceFence fence(st); // sg's vectors and the caller's set arrays feed asynchronous uploads
-	const int rc = GlmUpload(sg, d_y, d_z, d_yr, d_zr, st, "burden_sparse", "phenotype", errbuf);
-	if (rc != PGH_OK) {
-		return rc;
-	}
+	PGH_TRY(GlmUpload(sg, d_y, d_z, d_yr, d_zr, st, "burden_sparse", "phenotype", errbuf));
 	PGH_HIP(hipMemcpyAsync(d_off, set_off, 8ull * (n_sets + 1ull), hipMemcpyHostToDevice, st), "burden_sparse set upload");
 	if (n_memb) {
 		PGH_HIP(hipMemcpyAsync(d_vidx, set_vidx, 4ull * n_memb, hipMemcpyHostToDevice, st), "burden_sparse member upload");
@@ -990,14 +927,10 @@ int SkatSparseOne(const pgh_dataset *ds, const pgh_subset *subset, const double 
 
 	// the grid and the chunks: the workgroups' private vectors take at most half of the byte budget (one vector at
 	// least, eight workgroups per compute unit at most), a chunk's sums the rest (one set at least)
-	int device = 0, cus = 0;
-	PGH_HIP(hipGetDevice(&device), "skat_sparse device");
-	PGH_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device), "skat_sparse device attribute");
 	const uint64_t budget = EnvBytes(kSkatScratchEnv, kSkatScratchBytes);
 	const uint64_t per_group = pgh::BurdenScratchPerGroup(n_raw);
-	const uint32_t n_groups = static_cast<uint32_t>(std::min<uint64_t>(
-	    std::min<uint64_t>(n_sets, 8ull * static_cast<uint32_t>(std::max(cus, 1))),
-	    std::max<uint64_t>(1, budget / 2 / per_group)));
+	uint32_t n_groups = 0;
+	PGH_TRY(StashGroups(n_sets, 8, per_group, budget / 2, &n_groups, "skat_sparse", errbuf));
 	const uint64_t vec_bytes = per_group * n_groups;
 	uint64_t largest = 0;
 	for (uint32_t s = 0; s < n_sets; s++) {
@@ -1053,10 +986,7 @@ int SkatSparseOne(const pgh_dataset *ds, const pgh_subset *subset, const double 
 	std::vector<double> lam(std::max<uint64_t>(n_memb, 1), std::nan("")), hsums(std::max<uint64_t>(region, 1)), hg(ne);
 	std::vector<pgh::SkatSetCounts> counts(n_sets);
 	HostSourceFence fence(st); // sg's vectors, out_off and the caller's set arrays feed asynchronous uploads
-	int rc = GlmUpload(sg, d_y, d_z, d_r, d_zr, st, "skat_sparse", "phenotype", errbuf);
-	if (rc != PGH_OK) {
-		return rc;
-	}
+	PGH_TRY(GlmUpload(sg, d_y, d_z, d_r, d_zr, st, "skat_sparse", "phenotype", errbuf));
 	if (subset) {
 		PGH_HIP(hipMemsetAsync(d_w, 0, 8ull * nr, st), "skat_sparse weight clear");
 	}
@@ -1068,11 +998,8 @@ int SkatSparseOne(const pgh_dataset *ds, const pgh_subset *subset, const double 
 	// zeroed at every call: nothing is assumed of what an earlier call, or another user of the block, left there
 	PGH_HIP(hipMemsetAsync(vectors.p, 0, vec_bytes, st), "skat_sparse vectors clear");
 	int null_status = PGH_GLM_OK;
-	rc = GlmScoreNullFit(n_out, d_y, d_z, kp, k, subset ? subset->d_sel : nullptr, n_y >= k + 3, d_r, d_w, d_part, d_hg, st,
-	                     &null_status, errbuf);
-	if (rc != PGH_OK) {
-		return rc;
-	}
+	PGH_TRY(GlmScoreNullFit(n_out, d_y, d_z, kp, k, subset ? subset->d_sel : nullptr, n_y >= k + 3, d_r, d_w, d_part, d_hg, st,
+	                        &null_status, errbuf));
 	// the Cholesky factor of the final H and L^-1 g_S
 	double chol[M * M] = {}, yg[M] = {};
 	const bool fitted = n_y >= k + 3 && null_status == PGH_GLM_OK;
@@ -1267,15 +1194,8 @@ int GlmScoreSparseEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_
                         const GlmScoreSpaArgs *spa, char *errbuf) {
 	PGH_ONE_DEVICE(ds);
 	PGH_SPARSE_ROWS(ds);
-	const int rc = GlmCheckCommon(ds, subset, v_begin, v_end, 1, phenotype, n_covar, covariates, PGH_GLM_LOGISTIC, out,
-	                              errbuf);
-	if (rc != PGH_OK) {
-		return rc;
-	}
-	const int rc_y = GlmCheckBinary(phenotype, subset ? subset->n_out : ds->sample_ct, errbuf);
-	if (rc_y != PGH_OK) {
-		return rc_y;
-	}
+	PGH_TRY(GlmCheckCommon(ds, subset, v_begin, v_end, 1, phenotype, n_covar, covariates, PGH_GLM_LOGISTIC, out, errbuf));
+	PGH_TRY(GlmCheckBinary(phenotype, subset ? subset->n_out : ds->sample_ct, errbuf));
 	if (v_end == v_begin) {
 		return PGH_OK;
 	}
@@ -1291,73 +1211,145 @@ constexpr uint64_t kGlmScoreScratchBytes = 6ull << 30;
 const char *const kGlmScoreScratchEnv = "PGH_GLM_SCORE_SCRATCH_BYTES";
 constexpr uint32_t kGlmScoreMultiChunk = 65536;
 
-// pgh_glm_score_multi on one dense-resident dataset, after the argument checks.  The null models are fitted phenotype
-// by phenotype by GlmScoreNullFit, as GlmScoreSparseOne fits its one: on the covariates centred over the phenotype's
-// missing-value pattern, which the phenotypes of a pattern share (GlmStage's sums and subtraction, the latter on the
-// device).  Each fit's r and w go straight into the phenotype's columns of the block (glm_score_dense.hip).
-// spa != null (pgh_glm_score_multi_spa): after a block's chunk of rows, GlmScoreDenseSpaKernel replaces the p-value of
-// the rows beyond the cutoff.  Its workgroups' stashes take up to three quarters of what the budget leaves after the
-// column block (at least one stash, at most four workgroups per compute unit: the time of the kernel's iteration
-// falls with their number); [t, U, V], p_spa and the state per row join the chunk's bytes.  spa == null runs the launches it ran before
-// there was a saddlepoint path.
-// firth != null (pgh_glm_score_multi_firth; never with spa): after a block's chunk of rows, GlmScoreDenseFirthKernel
-// writes every row's pgh_glm_firth_row.  Its stashes are sized as the saddlepoint's, out of the same budget; a
-// pgh_glm_firth_row per row joins the chunk's bytes.
-int GlmScoreMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end, uint32_t n_pheno,
-                     const double *phenotypes, uint32_t k, const double *covariates, pgh_glm_row *out, char *errbuf,
-                     const GlmScoreSpaArgs *spa = nullptr, const GlmScoreFirthArgs *firth = nullptr) {
-	PGH_ENTER(ds);
-	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct, n_raw = ds->sample_ct;
-	const uint32_t nv_all = v_end - v_begin;
-	const uint32_t kp = pgh::GlmPadCovar(k);
-	hipStream_t st = PghThreadStream();
+// What a call of the dense route does after a block's chunk of rows: nothing, GlmScoreDenseSpaKernel, which replaces
+// the p-value of the rows beyond the cutoff (pgh_glm_score_multi_spa), or GlmScoreDenseFirthKernel, which writes every
+// row's pgh_glm_firth_row (pgh_glm_score_multi_firth).  One of the three; the outputs belong to the kind.
+struct GlmScoreFollowUp {
+	enum Kind { kNone, kSpa, kFirth };
+	Kind kind = kNone;
+	double cutoff = 0.0;
+	double *p_spa = nullptr;            // kSpa
+	uint8_t *state = nullptr;           // kSpa
+	pgh_glm_firth_row *firth = nullptr; // kFirth
+};
 
-	// the phenotypes in the order of their pattern groups, so that a pattern's covariates are centred once
+// The device arrays that scale with the chunk, per (block phenotype, chunk variant).  AddTo is their one declaration:
+// the scratch layout binds it, and the plan charges a chunk variant what it declares for c = 1.
+struct GlmScoreMultiChunkArrays {
+	double *sums = nullptr, *hgn = nullptr;
+	uint32_t *nmiss = nullptr;
+	pgh_glm_row *rows = nullptr;
+	pgh::GlmScoreSpaOut so;             // kSpa: [t, U, V], p_spa and the state
+	pgh_glm_firth_row *firth = nullptr; // kFirth
+	void AddTo(ScratchLayout &lay, uint64_t pb_max, uint64_t c, uint32_t kp, uint32_t k, GlmScoreFollowUp::Kind kind) {
+		const uint64_t n = pb_max * c, ns = kp + 6, ne = (k + 1) * (k + 2) / 2 + k + 1;
+		lay.Add(&sums, n * ns);
+		lay.Add(&hgn, n * ne);
+		lay.Add(&nmiss, n);
+		lay.Add(&rows, n);
+		lay.Add(&so.t, n * (kp + 3), kind == GlmScoreFollowUp::kSpa);
+		lay.Add(&so.p_spa, n, kind == GlmScoreFollowUp::kSpa);
+		lay.Add(&so.state, n, kind == GlmScoreFollowUp::kSpa);
+		lay.Add(&firth, n, kind == GlmScoreFollowUp::kFirth);
+	}
+};
+
+// How a call splits its budget.  The column block of pb_max phenotypes takes three quarters of it at most.  A
+// follow-up's workgroups' stashes take up to three quarters of what the block leaves (StashGroupsFor: at least one
+// stash, at most four workgroups per compute unit, since the time of the kernel's iteration falls with their number).
+// What is left then bounds the chunk, at GlmScoreMultiChunkArrays' bytes per variant before ScratchLayout's rounding:
+// the rounding and the block's own small arrays are not charged, so the scratch block can pass the budget by that much.
+struct GlmScoreMultiPlan {
+	uint32_t pb_max = 0;   // phenotypes of a column block
+	uint32_t n_groups = 0; // workgroups of the follow-up kernel (0: there is none)
+	uint32_t chunk = 0;    // variants of a chunk
+	uint64_t stash_bytes = 0;
+};
+GlmScoreMultiPlan GlmScoreMultiPlanFor(uint32_t n_raw, uint32_t n_pheno, uint32_t k, uint32_t nv_all, uint64_t budget,
+                                       int cus, GlmScoreFollowUp::Kind kind) {
+	const uint32_t kp = pgh::GlmPadCovar(k);
+	const uint64_t n_pad = 64ull * ((static_cast<uint64_t>(n_raw) + 63) / 64), mask_words = n_pad / 16;
+	const auto block_bytes = [&](uint32_t pb) {
+		return 8ull * n_pad * pgh::GlmScoreDenseLayout(pb, k).ld + 4ull * mask_words * pb;
+	};
+	GlmScoreMultiPlan plan;
+	plan.pb_max = std::min(pgh::kGlmScoreDensePb, n_pheno);
+	while (plan.pb_max > 1 && block_bytes(plan.pb_max) > budget / 4 * 3) {
+		plan.pb_max--;
+	}
+	GlmScoreMultiChunkArrays unit;
+	ScratchLayout one_variant;
+	unit.AddTo(one_variant, plan.pb_max, 1, kp, k, kind);
+	uint64_t left = budget > block_bytes(plan.pb_max) ? budget - block_bytes(plan.pb_max) : 0;
+	const uint32_t nv_most = std::min(kGlmScoreMultiChunk, nv_all);
+	if (kind != GlmScoreFollowUp::kNone) {
+		const uint64_t per_group = pgh::GlmScoreSpaStashPerGroup(n_raw);
+		plan.n_groups = StashGroupsFor(static_cast<uint64_t>(nv_most) * plan.pb_max, 4, per_group, left / 4 * 3, cus);
+		plan.stash_bytes = per_group * plan.n_groups;
+		left = left > plan.stash_bytes ? left - plan.stash_bytes : 0;
+	}
+	plan.chunk = static_cast<uint32_t>(std::min<uint64_t>(nv_most, std::max<uint64_t>(1, left / one_variant.payload)));
+	return plan;
+}
+
+// One call of pgh_glm_score_multi* on one dense-resident dataset, after the argument checks: what its parts share.
+// The null models are fitted phenotype by phenotype by GlmScoreNullFit, as GlmScoreSparseOne fits its one: on the
+// covariates centred over the phenotype's missing-value pattern, which the phenotypes of a pattern share (GlmStage's
+// sums and subtraction, the latter on the device).  Each fit's r and w go straight into the phenotype's columns of the
+// block (glm_score_dense.hip).
+struct GlmScoreMultiCall {
+	const pgh_dataset *ds;
+	const pgh_subset *subset;
+	uint32_t v_begin, nv_all, n_pheno, k;
+	const double *phenotypes, *covariates;
+	GlmScoreFollowUp fu;
+	char *errbuf;
+	hipStream_t st = PghThreadStream();
+	uint32_t n_out = subset ? subset->n_out : ds->sample_ct, n_raw = ds->sample_ct;
+	uint32_t kp = pgh::GlmPadCovar(k), ns = kp + 6, ne = (k + 1) * (k + 2) / 2 + k + 1;
+	uint64_t n_pad = 64ull * ((static_cast<uint64_t>(n_raw) + 63) / 64), mask_words = n_pad / 16;
+	const uint32_t *d_sel = subset ? subset->d_sel : nullptr;
+	GlmScoreMultiPlan plan;
+
+	// the phenotypes in the order of their pattern groups, so that a pattern's covariates are centred once; per group,
+	// staged when its first phenotype comes up: |S|, the covariates' means over S and S as the kernels' sample mask
+	// (one bit per 2-bit code, raw-sample order)
+	struct GroupStage {
+		bool ready = false;
+		uint32_t n_y = 0;
+		std::vector<double> mz;
+		std::vector<uint32_t> mask;
+	};
+	std::vector<uint32_t> order, group_of;
+	std::vector<GroupStage> gs;
+	uint32_t centred_for = UINT32_MAX; // the group d_z is centred for
+
+	double *d_y, *d_z0, *d_z, *d_zr0, *d_r, *d_w, *d_part, *d_hg1, *d_hg, *d_mz, *d_b;
+	uint32_t *d_ny, *d_mask;
+	GlmScoreMultiChunkArrays ch;
+	uint8_t *d_stash;
+	// the current block's |S| and null-fit status per phenotype, the current chunk's results
+	std::vector<uint32_t> h_ny;
+	std::vector<int> status;
+	std::vector<pgh_glm_row> hrows;
+	std::vector<double> hp_spa;
+	std::vector<uint8_t> hstate;
+	std::vector<pgh_glm_firth_row> hfirth;
+
+	int Prepare();
+	int StageBlock(uint32_t b0, uint32_t pb);
+	int RunChunk(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t nv, pgh_glm_row *out);
+};
+
+// The pattern order, the plan, the scratch block and the host buffers.
+int GlmScoreMultiCall::Prepare() {
 	const std::vector<std::vector<uint32_t>> groups = GlmPatternGroups(n_pheno, phenotypes, n_out);
-	std::vector<uint32_t> order, group_of(n_pheno);
+	group_of.resize(n_pheno);
 	for (uint32_t g = 0; g < groups.size(); g++) {
 		for (uint32_t p : groups[g]) {
 			order.push_back(p);
 			group_of[p] = g;
 		}
 	}
-	// sg.hz (and hz_raw): the covariates as they are
-	const GlmStaged sg = GlmStage(ds, subset, phenotypes, k, covariates, GlmCentre::kNone, true);
+	gs.resize(groups.size());
 
-	const uint64_t n_pad = 64ull * ((static_cast<uint64_t>(n_raw) + 63) / 64), mask_words = n_pad / 16;
-	const uint32_t ns = kp + 6, ne = (k + 1) * (k + 2) / 2 + k + 1;
-	const uint64_t budget = EnvBytes(kGlmScoreScratchEnv, kGlmScoreScratchBytes);
-	const auto block_bytes = [&](uint32_t pb) {
-		return 8ull * n_pad * pgh::GlmScoreDenseLayout(pb, k).ld + 4ull * mask_words * pb;
-	};
-	uint32_t pb_max = std::min(pgh::kGlmScoreDensePb, n_pheno);
-	while (pb_max > 1 && block_bytes(pb_max) > budget / 4 * 3) {
-		pb_max--;
+	int cus = 0;
+	if (fu.kind != GlmScoreFollowUp::kNone) {
+		PGH_TRY(DeviceCus(&cus, "glm_score_multi stash", errbuf));
 	}
-	const uint64_t per_variant =
-	    static_cast<uint64_t>(pb_max) * (8ull * (ns + ne) + sizeof(pgh_glm_row) + 4 + (spa ? 8ull * (kp + 3) + 8 + 1 : 0) +
-	                                   (firth ? sizeof(pgh_glm_firth_row) : 0));
-	uint64_t left = budget > block_bytes(pb_max) ? budget - block_bytes(pb_max) : 0;
-	const uint64_t per_group = pgh::GlmScoreSpaStashPerGroup(n_raw);
-	uint32_t n_groups = 0;
-	if (spa || firth) {
-		int device = 0, cus = 0;
-		PGH_HIP(hipGetDevice(&device), "glm_score_multi stash device");
-		PGH_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device),
-		        "glm_score_multi stash device attribute");
-		const uint64_t rows_all = static_cast<uint64_t>(std::min(kGlmScoreMultiChunk, nv_all)) * pb_max;
-		n_groups = static_cast<uint32_t>(std::max<uint64_t>(
-		    1, std::min<uint64_t>(std::min<uint64_t>(rows_all, 4ull * static_cast<uint32_t>(std::max(cus, 1))),
-		                          left / 4 * 3 / per_group)));
-		left = left > per_group * n_groups ? left - per_group * n_groups : 0;
-	}
-	const uint32_t chunk = static_cast<uint32_t>(
-	    std::min<uint64_t>(std::min(kGlmScoreMultiChunk, nv_all), std::max<uint64_t>(1, left / per_variant)));
+	plan = GlmScoreMultiPlanFor(n_raw, n_pheno, k, nv_all, EnvBytes(kGlmScoreScratchEnv, kGlmScoreScratchBytes), cus, fu.kind);
 
-	const uint64_t n = n_out, nr = n_raw, c = chunk, pbm = pb_max;
-	double *d_y, *d_z0, *d_z, *d_zr0, *d_r, *d_w, *d_part, *d_hg1, *d_hg, *d_mz, *d_b, *d_sums, *d_hgn;
-	uint32_t *d_ny, *d_mask, *d_nmiss;
-	pgh_glm_row *d_rows;
+	const uint64_t n = n_out, nr = n_raw, pbm = plan.pb_max;
 	ScratchLayout lay;
 	lay.Add(&d_y, n);
 	lay.Add(&d_z0, n * kp + 1); // one element of slack, here and in d_z, d_zr0, d_mz
@@ -1371,24 +1363,9 @@ int GlmScoreMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v
 	lay.Add(&d_mz, pbm * kp + 1);
 	lay.Add(&d_ny, pbm);
 	lay.Add(&d_mask, pbm * mask_words);
-	lay.Add(&d_b, n_pad * pgh::GlmScoreDenseLayout(pb_max, k).ld);
-	lay.Add(&d_sums, pbm * c * ns);
-	lay.Add(&d_hgn, pbm * c * ne);
-	lay.Add(&d_nmiss, pbm * c);
-	lay.Add(&d_rows, pbm * c);
-	pgh::GlmScoreSpaOut so;
-	uint8_t *d_stash = nullptr;
-	if (spa) {
-		lay.Add(&so.t, pbm * c * (kp + 3));
-		lay.Add(&so.p_spa, pbm * c);
-		lay.Add(&so.state, pbm * c);
-		lay.Add(&d_stash, per_group * n_groups);
-	}
-	pgh_glm_firth_row *d_firth = nullptr;
-	if (firth) {
-		lay.Add(&d_firth, pbm * c);
-		lay.Add(&d_stash, per_group * n_groups);
-	}
+	lay.Add(&d_b, n_pad * pgh::GlmScoreDenseLayout(plan.pb_max, k).ld);
+	ch.AddTo(lay, pbm, plan.chunk, kp, k, fu.kind);
+	lay.Add(&d_stash, plan.stash_bytes, fu.kind != GlmScoreFollowUp::kNone);
 	void *scratch = nullptr;
 	PGH_HIP(PghThreadScratch(lay.total, st, &scratch), "glm_score_multi scratch");
 	lay.Bind(scratch);
@@ -1396,133 +1373,142 @@ int GlmScoreMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v
 		d_zr0 = d_z0;
 	}
 
-	// per pattern group, staged when its first phenotype comes up: |S|, the covariates' means over S and S as the
-	// kernels' sample mask (one bit per 2-bit code, raw-sample order)
-	struct GroupStage {
-		bool ready = false;
-		uint32_t n_y = 0;
-		std::vector<double> mz;
-		std::vector<uint32_t> mask;
-	};
-	std::vector<GroupStage> gs(groups.size());
-	std::vector<uint32_t> h_ny(pb_max);
-	std::vector<int> status(pb_max);
-	std::vector<pgh_glm_row> hrows(static_cast<size_t>(chunk) * pb_max);
-	std::vector<double> hp_spa(spa ? hrows.size() : 0);
-	std::vector<uint8_t> hstate(spa ? hrows.size() : 0);
-	std::vector<pgh_glm_firth_row> hfirth(firth ? hrows.size() : 0);
-	HostSourceFence fence(st); // sg, gs, h_ny and the caller's phenotypes feed asynchronous uploads
-	if (kp) {
-		PGH_HIP(hipMemcpyAsync(d_z0, sg.hz.data(), 8ull * sg.hz.size(), hipMemcpyHostToDevice, st),
+	h_ny.resize(plan.pb_max);
+	status.resize(plan.pb_max);
+	hrows.resize(static_cast<size_t>(plan.chunk) * plan.pb_max);
+	hp_spa.resize(fu.kind == GlmScoreFollowUp::kSpa ? hrows.size() : 0);
+	hstate.resize(fu.kind == GlmScoreFollowUp::kSpa ? hrows.size() : 0);
+	hfirth.resize(fu.kind == GlmScoreFollowUp::kFirth ? hrows.size() : 0);
+	return PGH_OK;
+}
+
+// The block of the phenotypes order[b0 .. b0 + pb): per phenotype its group's mask and means, the centring, the null
+// fit and the columns.
+int GlmScoreMultiCall::StageBlock(uint32_t b0, uint32_t pb) {
+	const uint32_t ld = pgh::GlmScoreDenseLayout(pb, k).ld;
+	PGH_HIP(hipMemsetAsync(d_b, 0, 8ull * n_pad * ld, st), "glm_score_multi column block clear");
+	for (uint32_t j = 0; j < pb; j++) {
+		const uint32_t p = order[b0 + j], g = group_of[p];
+		const double *y = phenotypes + static_cast<size_t>(p) * n_out;
+		GroupStage &gr = gs[g];
+		if (!gr.ready) {
+			gr.ready = true;
+			gr.mask.assign(mask_words, 0u);
+			for (uint32_t i = 0; i < n_out; i++) {
+				if (!std::isnan(y[i])) {
+					const uint32_t s = subset ? subset->sel[i] : i;
+					gr.mask[s >> 4] |= 1u << (2u * (s & 15u));
+					gr.n_y++;
+				}
+			}
+			gr.mz.assign(kp + 1, 0.0);
+			for (uint32_t jz = 0; jz < k && gr.n_y; jz++) {
+				const double *zc = covariates + static_cast<size_t>(jz) * n_out;
+				double mz = 0.0;
+				for (uint32_t i = 0; i < n_out; i++) {
+					mz += std::isnan(y[i]) ? 0.0 : zc[i];
+				}
+				gr.mz[jz] = mz / gr.n_y;
+			}
+		}
+		h_ny[j] = gr.n_y;
+		PGH_HIP(hipMemcpyAsync(d_mask + j * mask_words, gr.mask.data(), 4ull * mask_words, hipMemcpyHostToDevice, st),
+		        "glm_score_multi mask upload");
+		if (kp) {
+			PGH_HIP(hipMemcpyAsync(d_mz + static_cast<uint64_t>(j) * kp, gr.mz.data(), 8ull * kp, hipMemcpyHostToDevice, st),
+			        "glm_score_multi mean upload");
+			if (centred_for != g) {
+				PGH_HIP(pgh::LaunchGlmScoreDenseCentre(n_out, kp, d_z0, d_mz + static_cast<uint64_t>(j) * kp, d_z, st),
+				        "glm_score_multi centring kernel");
+				centred_for = g;
+			}
+		}
+		PGH_HIP(hipMemcpyAsync(d_y, y, 8ull * n_out, hipMemcpyHostToDevice, st), "glm_score_multi phenotype upload");
+		PGH_TRY(GlmScoreNullFit(n_out, d_y, d_z, kp, k, d_sel, gr.n_y >= k + 3, d_r, d_w, d_part, d_hg1, st, &status[j],
+		                        errbuf));
+		PGH_HIP(hipMemcpyAsync(d_hg + static_cast<uint64_t>(j) * ne, d_hg1, 8ull * ne, hipMemcpyDeviceToDevice, st),
+		        "glm_score_multi null model copy");
+		PGH_HIP(pgh::LaunchGlmScoreDenseColumns(n_out, d_sel, d_r, d_w, d_z, kp, k, pb, j, d_b, st),
+		        "glm_score_multi column kernel");
+	}
+	PGH_HIP(hipMemcpyAsync(d_ny, h_ny.data(), 4ull * pb, hipMemcpyHostToDevice, st), "glm_score_multi count upload");
+	return PGH_OK;
+}
+
+// The variants c0 .. c0 + nv - 1 of the range against the staged block: the launches, the copies, and the scatter
+// into the caller's arrays ([variant][phenotype], the phenotypes in the caller's order).
+int GlmScoreMultiCall::RunChunk(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t nv, pgh_glm_row *out) {
+	const uint32_t l0 = v_begin + c0 - ds->v_begin;
+	const size_t n_rows = static_cast<size_t>(nv) * pb;
+	PGH_HIP(pgh::LaunchGlmScoreDense(ds->View(), l0, nv, d_mask, d_ny, pb, d_b, d_zr0, d_mz, kp, k, d_hg, ch.sums, ch.nmiss,
+	                                 ch.hgn, st),
+	        "glm_score_multi kernels");
+	for (uint32_t j = 0; j < pb; j++) {
+		const uint64_t at = static_cast<uint64_t>(j) * nv;
+		pgh::GlmScoreSpaOut soj;
+		if (fu.kind == GlmScoreFollowUp::kSpa) {
+			soj.t = ch.so.t + at * (kp + 3);
+			soj.p_spa = ch.so.p_spa + at;
+			soj.state = ch.so.state + at;
+		}
+		PGH_HIP(pgh::LaunchGlmScoreSolve(nv, ch.sums + at * ns, kp, k, ch.hgn + at * ne, status[j], ch.rows + at, st, soj),
+		        "glm_score_multi solve kernel");
+	}
+	PGH_HIP(hipMemcpyAsync(hrows.data(), ch.rows, sizeof(pgh_glm_row) * n_rows, hipMemcpyDeviceToHost, st),
+	        "glm_score_multi rows copy");
+	if (fu.kind == GlmScoreFollowUp::kSpa) {
+		PGH_HIP(pgh::LaunchGlmScoreDenseSpa(ds->View(), l0, nv, d_mask, pb, d_b, d_zr0, d_mz, kp, k, ch.sums, ch.rows, ch.so.t,
+		                                    fu.cutoff, plan.n_groups, d_stash, ch.so.p_spa, ch.so.state, st),
+		        "glm_score_multi_spa kernel");
+		PGH_HIP(hipMemcpyAsync(hp_spa.data(), ch.so.p_spa, 8ull * n_rows, hipMemcpyDeviceToHost, st),
+		        "glm_score_multi_spa p copy");
+		PGH_HIP(hipMemcpyAsync(hstate.data(), ch.so.state, n_rows, hipMemcpyDeviceToHost, st),
+		        "glm_score_multi_spa state copy");
+	} else if (fu.kind == GlmScoreFollowUp::kFirth) {
+		PGH_HIP(pgh::LaunchGlmScoreDenseFirth(ds->View(), l0, nv, d_mask, pb, d_b, k, ch.rows, fu.cutoff, plan.n_groups,
+		                                      d_stash, ch.firth, st),
+		        "glm_score_multi_firth kernel");
+		PGH_HIP(hipMemcpyAsync(hfirth.data(), ch.firth, sizeof(pgh_glm_firth_row) * n_rows, hipMemcpyDeviceToHost, st),
+		        "glm_score_multi_firth rows copy");
+	}
+	PGH_HIP(hipStreamSynchronize(st), "glm_score_multi sync");
+	for (uint32_t i = 0; i < nv; i++) {
+		for (uint32_t j = 0; j < pb; j++) {
+			const size_t to = static_cast<size_t>(c0 + i) * n_pheno + order[b0 + j], from = static_cast<size_t>(j) * nv + i;
+			out[to] = hrows[from];
+			if (fu.kind == GlmScoreFollowUp::kSpa) {
+				fu.p_spa[to] = hp_spa[from];
+				fu.state[to] = hstate[from];
+			} else if (fu.kind == GlmScoreFollowUp::kFirth) {
+				fu.firth[to] = hfirth[from];
+			}
+		}
+	}
+	return PGH_OK;
+}
+
+int GlmScoreMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end, uint32_t n_pheno,
+                     const double *phenotypes, uint32_t k, const double *covariates, pgh_glm_row *out, char *errbuf,
+                     const GlmScoreFollowUp &fu) {
+	PGH_ENTER(ds);
+	GlmScoreMultiCall c {ds, subset, v_begin, v_end - v_begin, n_pheno, k, phenotypes, covariates, fu, errbuf};
+	// sg.hz (and hz_raw): the covariates as they are
+	const GlmStaged sg = GlmStage(ds, subset, phenotypes, k, covariates, GlmCentre::kNone, true);
+	HostSourceFence fence(c.st); // sg, c's vectors and the caller's phenotypes feed asynchronous uploads
+	PGH_TRY(c.Prepare());
+	if (c.kp) {
+		PGH_HIP(hipMemcpyAsync(c.d_z0, sg.hz.data(), 8ull * sg.hz.size(), hipMemcpyHostToDevice, c.st),
 		        "glm_score_multi covariate upload");
 	}
-	if (sg.raw && kp) {
-		PGH_HIP(hipMemcpyAsync(d_zr0, sg.hz_raw.data(), 8ull * sg.hz_raw.size(), hipMemcpyHostToDevice, st),
+	if (sg.raw && c.kp) {
+		PGH_HIP(hipMemcpyAsync(c.d_zr0, sg.hz_raw.data(), 8ull * sg.hz_raw.size(), hipMemcpyHostToDevice, c.st),
 		        "glm_score_multi covariate upload (raw order)");
 	}
-	const uint32_t *d_sel = subset ? subset->d_sel : nullptr;
-	uint32_t centred_for = UINT32_MAX; // the group d_z is centred for
-	for (uint32_t b0 = 0; b0 < n_pheno; b0 += pb_max) {
-		const uint32_t pb = std::min(pb_max, n_pheno - b0);
-		const uint32_t ld = pgh::GlmScoreDenseLayout(pb, k).ld;
-		PGH_HIP(hipMemsetAsync(d_b, 0, 8ull * n_pad * ld, st), "glm_score_multi column block clear");
-		for (uint32_t j = 0; j < pb; j++) {
-			const uint32_t p = order[b0 + j], g = group_of[p];
-			const double *y = phenotypes + static_cast<size_t>(p) * n_out;
-			GroupStage &gr = gs[g];
-			if (!gr.ready) {
-				gr.ready = true;
-				gr.mask.assign(mask_words, 0u);
-				for (uint32_t i = 0; i < n_out; i++) {
-					if (!std::isnan(y[i])) {
-						const uint32_t s = subset ? subset->sel[i] : i;
-						gr.mask[s >> 4] |= 1u << (2u * (s & 15u));
-						gr.n_y++;
-					}
-				}
-				gr.mz.assign(kp + 1, 0.0);
-				for (uint32_t jz = 0; jz < k && gr.n_y; jz++) {
-					const double *zc = covariates + static_cast<size_t>(jz) * n_out;
-					double mz = 0.0;
-					for (uint32_t i = 0; i < n_out; i++) {
-						mz += std::isnan(y[i]) ? 0.0 : zc[i];
-					}
-					gr.mz[jz] = mz / gr.n_y;
-				}
-			}
-			h_ny[j] = gr.n_y;
-			PGH_HIP(hipMemcpyAsync(d_mask + j * mask_words, gr.mask.data(), 4ull * mask_words, hipMemcpyHostToDevice, st),
-			        "glm_score_multi mask upload");
-			if (kp) {
-				PGH_HIP(hipMemcpyAsync(d_mz + static_cast<uint64_t>(j) * kp, gr.mz.data(), 8ull * kp, hipMemcpyHostToDevice, st),
-				        "glm_score_multi mean upload");
-				if (centred_for != g) {
-					PGH_HIP(pgh::LaunchGlmScoreDenseCentre(n_out, kp, d_z0, d_mz + static_cast<uint64_t>(j) * kp, d_z, st),
-					        "glm_score_multi centring kernel");
-					centred_for = g;
-				}
-			}
-			PGH_HIP(hipMemcpyAsync(d_y, y, 8ull * n_out, hipMemcpyHostToDevice, st), "glm_score_multi phenotype upload");
-			const int rc = GlmScoreNullFit(n_out, d_y, d_z, kp, k, d_sel, gr.n_y >= k + 3, d_r, d_w, d_part, d_hg1, st,
-			                               &status[j], errbuf);
-			if (rc != PGH_OK) {
-				return rc;
-			}
-			PGH_HIP(hipMemcpyAsync(d_hg + static_cast<uint64_t>(j) * ne, d_hg1, 8ull * ne, hipMemcpyDeviceToDevice, st),
-			        "glm_score_multi null model copy");
-			PGH_HIP(pgh::LaunchGlmScoreDenseColumns(n_out, d_sel, d_r, d_w, d_z, kp, k, pb, j, d_b, st),
-			        "glm_score_multi column kernel");
-		}
-		PGH_HIP(hipMemcpyAsync(d_ny, h_ny.data(), 4ull * pb, hipMemcpyHostToDevice, st), "glm_score_multi count upload");
-		for (uint32_t c0 = 0; c0 < nv_all; c0 += chunk) {
-			const uint32_t nv = std::min(chunk, nv_all - c0);
-			PGH_HIP(pgh::LaunchGlmScoreDense(ds->View(), v_begin + c0 - ds->v_begin, nv, d_mask, d_ny, pb, d_b, d_zr0, d_mz,
-			                                 kp, k, d_hg, d_sums, d_nmiss, d_hgn, st),
-			        "glm_score_multi kernels");
-			for (uint32_t j = 0; j < pb; j++) {
-				const uint64_t at = static_cast<uint64_t>(j) * nv;
-				pgh::GlmScoreSpaOut soj;
-				if (spa) {
-					soj.t = so.t + at * (kp + 3);
-					soj.p_spa = so.p_spa + at;
-					soj.state = so.state + at;
-				}
-				PGH_HIP(pgh::LaunchGlmScoreSolve(nv, d_sums + at * ns, kp, k, d_hgn + at * ne, status[j], d_rows + at, st, soj),
-				        "glm_score_multi solve kernel");
-			}
-			PGH_HIP(hipMemcpyAsync(hrows.data(), d_rows, sizeof(pgh_glm_row) * nv * pb, hipMemcpyDeviceToHost, st),
-			        "glm_score_multi rows copy");
-			if (spa) {
-				PGH_HIP(pgh::LaunchGlmScoreDenseSpa(ds->View(), v_begin + c0 - ds->v_begin, nv, d_mask, pb, d_b, d_zr0, d_mz, kp,
-				                                    k, d_sums, d_rows, so.t, spa->cutoff, n_groups, d_stash, so.p_spa,
-				                                    so.state, st),
-				        "glm_score_multi_spa kernel");
-				PGH_HIP(hipMemcpyAsync(hp_spa.data(), so.p_spa, 8ull * nv * pb, hipMemcpyDeviceToHost, st),
-				        "glm_score_multi_spa p copy");
-				PGH_HIP(hipMemcpyAsync(hstate.data(), so.state, static_cast<size_t>(nv) * pb, hipMemcpyDeviceToHost, st),
-				        "glm_score_multi_spa state copy");
-			}
-			if (firth) {
-				PGH_HIP(pgh::LaunchGlmScoreDenseFirth(ds->View(), v_begin + c0 - ds->v_begin, nv, d_mask, pb, d_b, k, d_rows,
-				                                      firth->cutoff, n_groups, d_stash, d_firth, st),
-				        "glm_score_multi_firth kernel");
-				PGH_HIP(hipMemcpyAsync(hfirth.data(), d_firth, sizeof(pgh_glm_firth_row) * nv * pb, hipMemcpyDeviceToHost, st),
-				        "glm_score_multi_firth rows copy");
-			}
-			PGH_HIP(hipStreamSynchronize(st), "glm_score_multi sync");
-			for (uint32_t i = 0; i < nv; i++) {
-				for (uint32_t j = 0; j < pb; j++) {
-					const size_t to = static_cast<size_t>(c0 + i) * n_pheno + order[b0 + j], from = static_cast<size_t>(j) * nv + i;
-					out[to] = hrows[from];
-					if (spa) {
-						spa->p_spa[to] = hp_spa[from];
-						spa->state[to] = hstate[from];
-					}
-					if (firth) {
-						firth->rows[to] = hfirth[from];
-					}
-				}
-			}
+	for (uint32_t b0 = 0; b0 < n_pheno; b0 += c.plan.pb_max) {
+		const uint32_t pb = std::min(c.plan.pb_max, n_pheno - b0);
+		PGH_TRY(c.StageBlock(b0, pb));
+		for (uint32_t c0 = 0; c0 < c.nv_all; c0 += c.plan.chunk) {
+			PGH_TRY(c.RunChunk(b0, pb, c0, std::min(c.plan.chunk, c.nv_all - c0), out));
 		}
 	}
 	return PGH_OK;
@@ -1540,29 +1526,22 @@ extern "C" int pgh_glm_score_sparse_spa(const pgh_dataset *ds, const pgh_subset 
                                         uint32_t v_end, const double *phenotype, uint32_t n_covar,
                                         const double *covariates, double spa_cutoff, pgh_glm_row *out, double *p_spa,
                                         uint8_t *spa_state, char *errbuf) {
-	const int rc = GlmCheckSpa(spa_cutoff, p_spa, spa_state, errbuf);
-	if (rc != PGH_OK) {
-		return rc;
-	}
+	PGH_TRY(GlmCheckSpa(spa_cutoff, p_spa, spa_state, errbuf));
 	const GlmScoreSpaArgs spa = {spa_cutoff, p_spa, spa_state};
 	return GlmScoreSparseEntry(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, out, &spa, errbuf);
 }
 
 namespace {
 
-// pgh_glm_score_multi, pgh_glm_score_multi_spa (spa != null) and pgh_glm_score_multi_firth (firth != null) after the
-// latter two's own argument checks.
+// pgh_glm_score_multi, pgh_glm_score_multi_spa and pgh_glm_score_multi_firth after the latter two's own argument
+// checks.
 int GlmScoreMultiEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                        uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
-                       pgh_glm_row *out, const GlmScoreSpaArgs *spa, char *errbuf,
-                       const GlmScoreFirthArgs *firth = nullptr) {
+                       pgh_glm_row *out, const GlmScoreFollowUp &fu, char *errbuf) {
 	PGH_ONE_DEVICE(ds);
 	PGH_DENSE_ROWS(ds);
-	const int rc = GlmCheckCommon(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, PGH_GLM_LOGISTIC,
-	                              out, errbuf);
-	if (rc != PGH_OK) {
-		return rc;
-	}
+	PGH_TRY(GlmCheckCommon(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, PGH_GLM_LOGISTIC, out,
+	                       errbuf));
 	if (ds->dos_rows) {
 		SetErr(errbuf, "hardcalls only: the dataset holds " + std::to_string(ds->dos_rows) + " dosage tracks");
 		return PGH_ERR_ARG;
@@ -1579,7 +1558,7 @@ int GlmScoreMultiEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_t
 	if (v_end == v_begin) {
 		return PGH_OK;
 	}
-	return GlmScoreMultiOne(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, errbuf, spa, firth);
+	return GlmScoreMultiOne(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, errbuf, fu);
 }
 
 } // namespace
@@ -1587,19 +1566,16 @@ int GlmScoreMultiEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_t
 extern "C" int pgh_glm_score_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                                    uint32_t n_pheno, const double *phenotypes, uint32_t n_covar,
                                    const double *covariates, pgh_glm_row *out, char *errbuf) {
-	return GlmScoreMultiEntry(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, nullptr, errbuf);
+	return GlmScoreMultiEntry(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, {}, errbuf);
 }
 
 extern "C" int pgh_glm_score_multi_spa(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin,
                                        uint32_t v_end, uint32_t n_pheno, const double *phenotypes, uint32_t n_covar,
                                        const double *covariates, double spa_cutoff, pgh_glm_row *out, double *p_spa,
                                        uint8_t *spa_state, char *errbuf) {
-	const int rc = GlmCheckSpa(spa_cutoff, p_spa, spa_state, errbuf);
-	if (rc != PGH_OK) {
-		return rc;
-	}
-	const GlmScoreSpaArgs spa = {spa_cutoff, p_spa, spa_state};
-	return GlmScoreMultiEntry(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, &spa, errbuf);
+	PGH_TRY(GlmCheckSpa(spa_cutoff, p_spa, spa_state, errbuf));
+	const GlmScoreFollowUp fu = {GlmScoreFollowUp::kSpa, spa_cutoff, p_spa, spa_state, nullptr};
+	return GlmScoreMultiEntry(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, fu, errbuf);
 }
 
 extern "C" int pgh_glm_score_multi_firth(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin,
@@ -1614,9 +1590,8 @@ extern "C" int pgh_glm_score_multi_firth(const pgh_dataset *ds, const pgh_subset
 		SetErr(errbuf, "null firth");
 		return PGH_ERR_ARG;
 	}
-	const GlmScoreFirthArgs fa = {firth_cutoff, firth};
-	return GlmScoreMultiEntry(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, nullptr, errbuf,
-	                          &fa);
+	const GlmScoreFollowUp fu = {GlmScoreFollowUp::kFirth, firth_cutoff, nullptr, nullptr, firth};
+	return GlmScoreMultiEntry(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, fu, errbuf);
 }
 
 extern "C" int pgh_burden_sparse(const pgh_dataset *ds, const pgh_subset *subset, const double *phenotype,
@@ -1625,15 +1600,9 @@ extern "C" int pgh_burden_sparse(const pgh_dataset *ds, const pgh_subset *subset
 	PGH_ONE_DEVICE(ds);
 	PGH_SPARSE_ROWS(ds);
 	// the arguments pgh_glm_sparse has too, over the whole resident range (its `out` is checked below)
-	const int rc = GlmCheckCommon(ds, subset, ds ? ds->v_begin : 0, ds ? ds->v_begin : 0, 1, phenotype, n_covar, covariates,
-	                              PGH_GLM_LINEAR, nullptr, errbuf);
-	if (rc != PGH_OK) {
-		return rc;
-	}
-	const int rc_sets = GlmCheckSets(ds, n_sets, set_off, set_vidx, weight, out, errbuf);
-	if (rc_sets != PGH_OK) {
-		return rc_sets;
-	}
+	PGH_TRY(GlmCheckCommon(ds, subset, ds ? ds->v_begin : 0, ds ? ds->v_begin : 0, 1, phenotype, n_covar, covariates,
+	                       PGH_GLM_LINEAR, nullptr, errbuf));
+	PGH_TRY(GlmCheckSets(ds, n_sets, set_off, set_vidx, weight, out, errbuf));
 	return BurdenSparseOne(ds, subset, phenotype, n_covar, covariates, n_sets, set_off, set_vidx, weight, out, errbuf);
 }
 

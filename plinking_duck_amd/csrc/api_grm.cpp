@@ -15,15 +15,8 @@ const char *const kGrmBandEnv = "PGH_GRM_BAND_BYTES";
 // The byte budget of a band: kGrmBandBytes, or less when the environment variable asks for it (read at every call;
 // the result does not depend on it -- a test walks a small square in many bands with it)
 uint64_t BandBytes() {
-	const char *s = std::getenv(kGrmBandEnv);
-	if (s && *s) {
-		char *end = nullptr;
-		const unsigned long long v = std::strtoull(s, &end, 10);
-		if (end && *end == '\0' && v >= 1) {
-			return std::min<unsigned long long>(v, kGrmBandBytes);
-		}
-	}
-	return kGrmBandBytes;
+	const uint64_t v = EnvBytes(kGrmBandEnv, kGrmBandBytes);
+	return v >= 1 ? std::min<uint64_t>(v, kGrmBandBytes) : kGrmBandBytes;
 }
 
 // raw samples [lo, hi) behind the output samples [begin, end): sel ascends

@@ -362,6 +362,7 @@ struct DevBuf {
 // One device block cut into typed buffers.  Step one: Add(&p, count) declares a buffer of `count` elements for the
 // pointer p, rounded up to 256 bytes, and `total` grows by it; a buffer that is not `present` takes no bytes.  Step
 // two, once a block of `total` bytes exists: Bind(block) sets every declared pointer, the absent ones to nullptr.
+// `payload` is the bytes of the present buffers before the rounding: what a budget rule charges for them.
 struct ScratchLayout {
 	struct Piece {
 		void *slot; // the T* to set
@@ -369,11 +370,12 @@ struct ScratchLayout {
 		bool present;
 	};
 	std::vector<Piece> pieces;
-	uint64_t total = 0;
+	uint64_t total = 0, payload = 0;
 	template <class T>
 	void Add(T **p, uint64_t count, bool present = true) {
 		pieces.push_back({p, total, present});
 		total += present ? (sizeof(T) * count + 255) / 256 * 256 : 0;
+		payload += present ? sizeof(T) * count : 0;
 	}
 	void Bind(void *block) const {
 		for (const Piece &pc : pieces) {
@@ -382,6 +384,53 @@ struct ScratchLayout {
 		}
 	}
 };
+
+// Returns what a callee returned unless that is PGH_OK.
+#define PGH_TRY(call)                                                                                                  \
+	if (const int rc_ = (call); rc_ != PGH_OK)                                                                         \
+	return rc_
+
+// A count from an environment variable, read at every call: its value when it is a whole decimal number, else
+// `fallback`.  What a caller makes of 0 or of a value past its own limit stays with it.
+[[maybe_unused]] uint64_t EnvBytes(const char *name, uint64_t fallback) {
+	const char *s = std::getenv(name);
+	if (s && *s) {
+		char *end = nullptr;
+		const unsigned long long v = std::strtoull(s, &end, 10);
+		if (end && *end == '\0') {
+			return v;
+		}
+	}
+	return fallback;
+}
+
+// How many workgroups with a private stash or vector of per_group_bytes a launch over `rows` rows gets on a device of
+// `cus` compute units: at most per_cu per compute unit and one per row, within budget_bytes, and at least one whatever
+// the budget.  Every caller has rows >= 1 (pgh_glm_score_sparse_spa and pgh_glm_score_multi* return before for an empty
+// range, GlmCheckSets refuses n_sets == 0), where min(min(rows, cap), max(1, budget / per_group)) is the same number.
+[[maybe_unused]] uint32_t StashGroupsFor(uint64_t rows, uint32_t per_cu, uint64_t per_group_bytes, uint64_t budget_bytes,
+                                         int cus) {
+	const uint64_t cap = static_cast<uint64_t>(per_cu) * static_cast<uint32_t>(std::max(cus, 1));
+	return static_cast<uint32_t>(std::max<uint64_t>(1, std::min(std::min(rows, cap), budget_bytes / per_group_bytes)));
+}
+
+// The compute units of the current device.  what: the caller's label for errbuf.
+[[maybe_unused]] int DeviceCus(int *cus, const char *what, char *errbuf) {
+	int device = 0;
+	PGH_HIP(hipGetDevice(&device), (std::string(what) + " device").c_str());
+	PGH_HIP(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, device),
+	        (std::string(what) + " device attribute").c_str());
+	return PGH_OK;
+}
+
+// StashGroupsFor on the current device.
+[[maybe_unused]] int StashGroups(uint64_t rows, uint32_t per_cu, uint64_t per_group_bytes, uint64_t budget_bytes,
+                                 uint32_t *n_groups, const char *what, char *errbuf) {
+	int cus = 0;
+	PGH_TRY(DeviceCus(&cus, what, errbuf));
+	*n_groups = StashGroupsFor(rows, per_cu, per_group_bytes, budget_bytes, cus);
+	return PGH_OK;
+}
 
 // HIP does not promise that hipMemcpyAsync has finished with a PAGEABLE source when it returns (this runtime
 // happens to stage it first, tools/pageable_async_probe.hip), so a frame-local container that feeds one must

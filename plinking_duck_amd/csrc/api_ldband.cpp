@@ -54,15 +54,8 @@ int Prepare(const pgh_dataset *ds, const pgh_subset *subset, uint32_t variant_be
 
 // tiles per launch: the environment variable when it holds a number of at least 1, capped at `most`
 uint32_t ChunkTiles(const char *env, uint32_t most) {
-	const char *s = std::getenv(env);
-	if (s && *s) {
-		char *end = nullptr;
-		const unsigned long long v = std::strtoull(s, &end, 10);
-		if (end && *end == '\0' && v >= 1) {
-			return static_cast<uint32_t>(std::min<unsigned long long>(v, most));
-		}
-	}
-	return most;
+	const uint64_t v = EnvBytes(env, most);
+	return v >= 1 ? static_cast<uint32_t>(std::min<uint64_t>(v, most)) : most;
 }
 
 int CheckWindows(const uint32_t *win_end, uint32_t n_var, char *errbuf) {

@@ -36,7 +36,7 @@
 //
 // Missing-call corrections (GlmScoreDenseCorrKernel).  H_N = H - sum_M w Zt Zt', g_N = g_S - sum_M Zt r.  A workgroup
 // owns (variant, phenotype): it walks the row 4,096 samples a step (a 16-code word per thread), ranks the missing calls
-// of S in sample order (a prefix sum of the words' counts), writes their list rows [1, Zt, w, r], 256 at a time, and
+// of S in sample order (TeamRankCounts over the words' counts), writes their list rows [1, Zt, w, r], 256 at a time, and
 // every entry's one owner adds its term in list order: the arithmetic and the order of GlmScoreSparseKernel's owners.
 // A variant with M empty copies H and g_S.
 // The rows come from GlmScoreSolveKernel (LaunchGlmScoreSolve), unchanged, once per phenotype.
@@ -316,8 +316,7 @@ __global__ void __launch_bounds__(kBlock) GlmScoreDenseCorrKernel(const uint8_t 
 		}
 		return;
 	}
-	__shared__ uint32_t wave_ct[2][kTeamWaves]; // by the step's parity: a step's readers never meet the next step's writers
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	int ea, eb, ew;
 	ScoreOwnedEntry(threadIdx.x, k, &ea, &eb, &ew);
 	const uint32_t *row = reinterpret_cast<const uint32_t *>(rows + static_cast<uint64_t>(v0 + v) * pitch);
@@ -334,22 +333,8 @@ __global__ void __launch_bounds__(kBlock) GlmScoreDenseCorrKernel(const uint8_t 
 			const uint32_t c = row[wi];
 			mm = c & (c >> 1) & 0x55555555u & m[wi];
 		}
-		const uint32_t cnt = static_cast<uint32_t>(__popc(mm));
-		uint32_t incl = cnt;
-#pragma unroll
-		for (uint32_t off = 1; off < 64u; off <<= 1) {
-			const uint32_t up = static_cast<uint32_t>(__shfl_up(static_cast<int>(incl), off, 64));
-			incl += lane >= off ? up : 0u;
-		}
-		if (lane == 63u) {
-			wave_ct[step & 1u][wave] = incl;
-		}
-		__syncthreads();
-		uint32_t pos = incl - cnt, total = 0;
-		for (uint32_t w = 0; w < static_cast<uint32_t>(kTeamWaves); w++) {
-			pos += w < wave ? wave_ct[step & 1u][w] : 0u;
-			total += wave_ct[step & 1u][w];
-		}
+		uint32_t total;
+		const uint32_t pos = TeamRankCounts(static_cast<uint32_t>(__popc(mm)), step, lane, wave, &total);
 		for (uint32_t base = 0; base < total; base += kBlock) { // total is the same on every thread
 			uint32_t bits = mm, at = pos;
 			while (bits) {

@@ -143,14 +143,13 @@ __global__ void __launch_bounds__(kBlock) GlmScoreSpaKernel(const int32_t *__res
                                                             uint8_t *__restrict__ state) {
 	const SparseRows rows = {row_of, off, entries, pool, pitch, sample_ct, v_first, nv};
 	if constexpr (TEAM == kTeamBlock) {
-		// a bounded grid: workgroup b takes the rows b, b + gridDim.x, ... with its own sample_ct pairs of `stash`
+		// TeamGridRows: a workgroup has its own sample_ct pairs of `stash`
 		double2 *st = stash + static_cast<uint64_t>(blockIdx.x) * sample_ct;
 		// (only thread 0's stores use them: held in vector registers, the loop's scalar registers all fit)
 		asm volatile("" : "+v"(p_spa), "+v"(state));
-		for (uint32_t i = blockIdx.x; i < nv; i += gridDim.x) {
+		TeamGridRows(nv, [&](uint32_t i) {
 			SpaRow<KP, TEAM>(rows, i, rr, ww, z, out, tv, cutoff, st, sample_ct, p_spa, state);
-			__syncthreads(); // the next row rewrites the stash
-		}
+		});
 	} else {
 		__shared__ double2 lds[kTeamWaves * kSpaWaveStash];
 		const uint32_t i = blockIdx.x * kTeamWaves + (threadIdx.x >> 6);

@@ -92,6 +92,33 @@ __device__ __forceinline__ uint32_t TeamRank(bool take, int lane, int wave, uint
 	return before + static_cast<uint32_t>(__popcll(bal & ((1ull << lane) - 1ull)));
 }
 
+// TeamRank for a workgroup whose threads each bring a count, not a bool.  Returns how many selected items the threads
+// before this one in thread order hold, and in *total the workgroup's sum, the same on every thread: an inclusive
+// __shfl_up scan of the counts per wave, then the waves' totals from LDS.  step: the number of the caller's step, 0,
+// 1, 2, ...  The totals sit in wave_ct[step & 1], so a step's readers never meet the next step's writers: between a
+// thread's reads of step s and any thread's writes of step s + 2 stands the barrier of step s + 1, and one barrier a
+// step is enough.  Every thread of the workgroup calls it, under workgroup-uniform control flow.
+__device__ __forceinline__ uint32_t TeamRankCounts(uint32_t cnt, uint32_t step, int lane, int wave, uint32_t *total) {
+	__shared__ uint32_t wave_ct[2][kTeamWaves];
+	uint32_t incl = cnt;
+#pragma unroll
+	for (uint32_t off = 1; off < 64u; off <<= 1) {
+		const uint32_t up = static_cast<uint32_t>(__shfl_up(static_cast<int>(incl), off, 64));
+		incl += static_cast<uint32_t>(lane) >= off ? up : 0u;
+	}
+	if (lane == 63) {
+		wave_ct[step & 1u][wave] = incl;
+	}
+	__syncthreads();
+	uint32_t before = incl - cnt;
+	*total = 0;
+	for (int w = 0; w < kTeamWaves; w++) {
+		before += w < wave ? wave_ct[step & 1u][w] : 0u;
+		*total += wave_ct[step & 1u][w];
+	}
+	return before;
+}
+
 // Team totals of N doubles and four integer counts, on every thread: a butterfly per wave, then (TEAM == 256) the
 // waves' partials added in the order 0..3 from LDS.  One barrier, between the partials' writes and their reads: a
 // caller that calls it again (GlmScoreSpaKernel does, once per evaluation) puts a TeamSync between the calls, or the
@@ -139,6 +166,96 @@ __device__ __forceinline__ void TeamSums(double (&v)[N], long long (&c)[4], int 
 			}
 		}
 	}
+}
+
+// The bounded grid of the workgroup-form kernels whose workgroups own a stash: workgroup g takes the rows g,
+// g + gridDim.x, ... of n_rows, and a barrier after each, because the next row rewrites the stash.
+template <class Row>
+__device__ __forceinline__ void TeamGridRows(uint32_t n_rows, Row row) {
+	for (uint32_t at = blockIdx.x; at < n_rows; at += gridDim.x) {
+		row(at);
+		__syncthreads();
+	}
+}
+
+// What the follow-up kernels of the dense score route (glm_score_dense_spa.hip, glm_score_dense_firth.hip) read of a
+// chunk of a phenotype block: row at = p * nv + v is block phenotype p and chunk variant v.
+struct DenseRows {
+	const uint8_t *rows; // the resident rows
+	uint64_t pitch;
+	uint32_t v0, nv;     // the chunk: local rows v0 .. v0 + nv - 1
+	uint32_t sample_ct;
+	uint32_t mask_words; // 16-code words of a row and of a phenotype's mask (zero past the last sample)
+	const uint32_t *mask;
+	uint32_t pb;
+	const double *b; // the column block
+	uint32_t ld, k;
+
+	__device__ const uint32_t *Row(uint32_t v) const {
+		return reinterpret_cast<const uint32_t *>(rows + static_cast<uint64_t>(v0 + v) * pitch);
+	}
+	__device__ const uint32_t *Mask(uint32_t p) const {
+		return mask + static_cast<uint64_t>(p) * mask_words;
+	}
+};
+
+// The checks the two launch wrappers share and the fields of DenseRows.  hipSuccess with *grid == 0: an empty chunk,
+// nothing to launch.  Otherwise *grid workgroups (n_groups at most, one per row at most) each own a stash.
+inline hipError_t DenseRowsFor(const RowView &view, uint32_t v0, uint32_t nv, const uint32_t *mask, uint32_t pb,
+                               const double *b, uint32_t k, uint32_t n_groups, DenseRows *a, uint32_t *grid) {
+	*grid = 0;
+	if (k > PGH_GLM_MAX_COVAR || pb == 0 || pb > kGlmScoreDensePb) {
+		return hipErrorInvalidValue;
+	}
+	if (nv == 0) {
+		return hipSuccess;
+	}
+	const uint32_t words16 = (view.sample_ct + 63u) / 64u;
+	if (n_groups == 0 || 16ull * words16 > view.pitch) {
+		return hipErrorInvalidValue; // the kernels read whole 16-code words of a row up to the mask's length
+	}
+	*a = {view.rows, view.pitch, v0, nv, view.sample_ct, 4u * words16, mask, pb, b, GlmScoreDenseLayout(pb, k).ld, k};
+	const uint64_t n_rows = static_cast<uint64_t>(nv) * pb;
+	*grid = static_cast<uint32_t>(n_groups < n_rows ? n_groups : n_rows);
+	return hipSuccess;
+}
+
+// Phase A of those kernels: the walk of one 2-bit row under one phenotype's mask by the workgroup, a 16-code word per
+// thread and 4,096 samples a step.  select(c, m) -> em, bit 2 i set where sample 16 wi + i of the word is selected;
+// the selected samples are ranked in sample order (TeamRankCounts over the words' popcounts, then bit order inside a
+// word), and entry(s, code) -> the double2 that goes to st[rank] when rank < cap.  Returns the number selected, on
+// every thread; the caller tests it against cap.
+//
+// The contract is the order: a thread visits its entries by ascending word and, inside a word, ascending bit, and
+// calls entry once for each, so a sum that entry keeps with one fma per call is one chain per thread in that order.
+// The caller reduces it with TeamSums and then runs TeamSync (the pairs before their readers, and TeamSums' LDS before
+// it is written again).  That order of summation is the result, bit for bit: do not reorder the visits.
+template <class Select, class Entry>
+__device__ __forceinline__ uint32_t TeamStashMaskedRow(const uint32_t *row, const uint32_t *m, uint32_t mask_words,
+                                                       double2 *__restrict__ st, uint32_t cap, int tid, int lane,
+                                                       int wave, Select select, Entry entry) {
+	uint32_t count = 0;
+	for (uint32_t w0 = 0, step = 0; w0 < mask_words; w0 += kTeamBlock, step++) {
+		const uint32_t wi = w0 + tid;
+		uint32_t c = 0, em = 0;
+		if (wi < mask_words) {
+			c = row[wi];
+			em = select(c, m[wi]);
+		}
+		uint32_t total;
+		uint32_t pos = count + TeamRankCounts(static_cast<uint32_t>(__popc(em)), step, lane, wave, &total);
+		while (em) {
+			const uint32_t i = static_cast<uint32_t>(__ffs(static_cast<int>(em)) - 1) >> 1;
+			em &= em - 1u;
+			const double2 pair = entry(16u * wi + i, (c >> (2u * i)) & 3u);
+			if (pos < cap) {
+				st[pos] = pair;
+			}
+			pos++;
+		}
+		count += total;
+	}
+	return count;
 }
 
 // The rows of a sparse-resident dataset (SparseView's arrays) that one launch of an entry kernel covers.

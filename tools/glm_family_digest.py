@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """One SHA-256 per case over the result bytes of the GLM family (pgh_glm, pgh_glm_multi, pgh_glm_sparse,
-pgh_glm_score_sparse, pgh_burden_sparse), pgh_score_sparse, and the plink_ld pair sums and sparse counts that share
-their wave sums: the paths a change to the family's kernels, host staging, scratch layout or chunk loops can touch.  Two builds of the library
+pgh_glm_score_sparse, pgh_glm_score_sparse_spa, pgh_glm_score_multi, pgh_glm_score_multi_spa, pgh_glm_score_multi_firth,
+pgh_burden_sparse), pgh_score_sparse, and the plink_ld pair sums and sparse counts that share their wave sums: the
+paths a change to the family's kernels, host staging, scratch layout or chunk loops can touch.  Two builds of the library
 compute the same rows bit for bit exactly when their outputs of this tool are equal line for line; PGENHIP_LIB names
 the build (plinking_duck_amd/lib.py).  A case that differs between two runs of ONE build is not deterministic from
 run to run and its line says nothing.
@@ -34,7 +35,7 @@ out_dir = args.dir or tmp.name
 os.makedirs(out_dir, exist_ok=True)
 
 
-def emit(name, *results):
+def emit(name, *results, note=""):
     h = hashlib.sha256()
     for r in results:
         if isinstance(r, dict):
@@ -46,7 +47,7 @@ def emit(name, *results):
                 h.update(repr(a.tolist()).encode())
             else:
                 h.update(np.ascontiguousarray(a).tobytes())
-    print(f"{name} {h.hexdigest()}", flush=True)
+    print(f"{name} {h.hexdigest()}{note}", flush=True)
 
 
 def pheno(rng, n, Z, kind="linear", missing=0.03):
@@ -184,6 +185,8 @@ for max_minor, form in ((N_R, "entries only"), (1, "with dense-form rows")):
     emit(f"burden_sparse {form}, unweighted", sp.burden_sparse(yr, set_off, set_vidx, covariates=Zr))
     emit(f"burden_sparse {form}, subset", sp.burden_sparse(yrs, set_off, set_vidx, weights=set_w, covariates=Zrs,
                                                               subset=sub))
+    emit(f"skat_sparse {form}, weighted", *sp.skat_sparse(yb, set_off, set_vidx, weights=set_w, covariates=Zr,
+                                                          return_lambda=True))
     for n_cols in (1, 9):
         w = rng.normal(size=(len(scored), n_cols))
         for mode in (L.SCORE_MEAN_IMPUTE, L.SCORE_CENTER, L.SCORE_NO_MEAN_IMPUTATION):
@@ -203,3 +206,81 @@ Zc = covar(rng, 2, N_C)
 emit("glm_sparse across a chunk", sp.glm_sparse(pheno(rng, N_C, Zc), Zc))
 emit("glm_score_sparse across a chunk", sp.glm_score_sparse(pheno(rng, N_C, Zc, "logistic"), Zc))
 sp.close()
+
+# ---- the score tests that share the ranked row walk and the budget plan: pgh_glm_score_multi, _multi_spa, _multi_firth
+# and pgh_glm_score_sparse_spa, on the inputs of their tests ---------------------------------------------------------
+import subset_shapes as SS  # noqa: E402
+import test_glm_score_multi as GM  # noqa: E402
+import test_glm_score_multi_spa as MS  # noqa: E402
+
+SCRATCH_ENV = "PGH_GLM_SCORE_SCRATCH_BYTES"
+CUT = 0.1  # the lowest cutoff the entry points take: the saddlepoint and Firth are tried in most fitted rows
+STEP = 4096  # samples of one step of the walk
+
+
+def share(res, key):
+    """The share of the rows in which the follow-up was applied, next to the share of the fitted rows."""
+    return f"  applied {np.mean(res[key] == 1):.3f} of {np.mean(res['errcode'] == None):.3f} fitted"  # noqa: E711
+
+
+def score_family(tag, dense, Y, Z, **kw):
+    emit(f"glm_score_multi {tag}", dense.glm_score_multi(Y, Z, **kw))
+    spa = dense.glm_score_multi_spa(Y, Z, spa_cutoff=CUT, **kw)
+    emit(f"glm_score_multi_spa {tag}", spa, note=share(spa, "spa_state"))
+    firth = dense.glm_score_multi_firth(Y, Z, firth_cutoff=CUT, **kw)
+    emit(f"glm_score_multi_firth {tag}", firth, note=share(firth, "firth_state"))
+
+
+for n in (4096, 4099, 8209):  # one full step of the walk, a second step of three samples, a third step
+    case = MS.inputs(n)
+    path = os.path.join(out_dir, f"score_walk_{n}.pgen")
+    W.write_pgen(path, case.geno, case.kinds)
+    # test_glm_score_multi_spa's three phenotypes and one with a missing-majority pattern
+    sparse_y = case.y.copy()
+    sparse_y[np.random.default_rng(n).random(n) < 0.6] = np.nan
+    Y = np.vstack([MS.phenotypes(case), sparse_y])
+    assert np.isnan(sparse_y).mean() > 0.5
+    # a step in which the correction kernel ranks more than 256 missing calls and the follow-ups more than 256 entries
+    in_s = ~np.isnan(Y[0][:STEP])
+    assert ((case.geno[:, :STEP] == 3) & in_s).sum(axis=1).max() > 256
+    assert (((case.geno[:, :STEP] == 1) | (case.geno[:, :STEP] == 2)) & in_s).sum(axis=1).max() > 256
+    dense = L.Dataset.open(path)
+    forms = [("entries only", L.Dataset.open(path, sparse=True, max_minor=n)),
+             ("with dense-form rows", L.Dataset.open(path, sparse=True, max_minor=1))]
+    for k in (0, 4, 5, 20):
+        Zk = case.covariates(k) if k else None
+        score_family(f"n={n} k={k}", dense, Y, Zk)
+        for form, sp in forms:
+            res = sp.glm_score_sparse_spa(case.y, Zk, cutoff=CUT)
+            emit(f"glm_score_sparse_spa {form}, n={n} k={k}", res, note=share(res, "spa_state"))
+    if n == 4099:
+        # a subset that cuts every 16-code word
+        keep_w = SS.shapes(n)["stride4"]
+        Zs4 = np.ascontiguousarray(case.covariates(4)[:, keep_w])
+        sub = dense.subset(keep_w)
+        score_family(f"n={n} k=4 subset", dense, np.ascontiguousarray(Y[:, keep_w]), Zs4, subset=sub)
+        sub.close()
+        for form, sp in forms:
+            sub = sp.subset(keep_w)
+            res = sp.glm_score_sparse_spa(case.y[keep_w], Zs4, cutoff=CUT, subset=sub)
+            emit(f"glm_score_sparse_spa {form}, n={n} k=4 subset", res, note=share(res, "spa_state"))
+            sub.close()
+        # Scratch budgets (k = 4).  The block of one phenotype and its mask are 2,129,920 + 1,040 = 2,130,960 bytes,
+        # more than three quarters of either budget: one phenotype per block.  2,400,960 leaves 270,000: 270,000 / 4 * 3 /
+        # 65,584 = 3 stashes, and the 73,248 bytes after them a chunk of 214 variants (341 bytes each with the
+        # saddlepoint) or 237 (308 with Firth); without a follow-up, 270,000 / 276 = 978 variants, the whole range.
+        # 2,200,960 leaves 70,000: one stash and a chunk of 12 or 14 variants, or 253 without a follow-up.
+        for budget in (2_400_960, 2_200_960):
+            before = os.environ.get(SCRATCH_ENV)
+            os.environ[SCRATCH_ENV] = str(budget)
+            score_family(f"n={n} k=4 budget={budget}", dense, Y, case.covariates(4))
+            if before is None:
+                del os.environ[SCRATCH_ENV]
+            else:
+                os.environ[SCRATCH_ENV] = before
+        # 17 phenotypes at k = 13: every phenotype after the first straddles a 16-column block edge
+        Zl, Yl = GM.layout_inputs(13)
+        assert Yl.shape == (17, n)
+        score_family(f"n={n} k=13 P=17", dense, Yl, Zl)
+    for d in [dense] + [sp for _, sp in forms]:
+        d.close()
