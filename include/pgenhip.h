@@ -606,8 +606,9 @@ int pgh_glm_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_be
  * rounding (its sums are accumulated over the entries, in another order); the rows of variants held in the dense
  * form (pgh_sparse_info.dense_variant_ct) are pgh_glm's bit for bit.  A row is a function of its variant's entries,
  * the phenotype, the covariates and the subset only: not of v_begin, the chunk or the rows around it, and the same
- * call returns the same bytes every time.  Logistic Wald and Firth fits over a sparse-resident dataset are not offered
- * (the logistic score test is: pgh_glm_score_sparse). */
+ * call returns the same bytes every time.  Logistic Wald fits and pgh_glm's full Firth fits over a sparse-resident
+ * dataset are not offered (the logistic score test is: pgh_glm_score_sparse; its approximate Firth estimate is:
+ * pgh_glm_score_sparse_firth). */
 int pgh_glm_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                    const double *phenotype, uint32_t n_covar, const double *covariates,
                    pgh_glm_row *out, char *errbuf);
@@ -647,7 +648,9 @@ int pgh_glm_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_b
  * A row is a function of its variant's entries, the phenotype, the covariates and the subset only: not of v_begin,
  * the chunk, the window the dataset was opened with or the rows around it, and the same call returns the same bytes
  * every time, the null fit included.  Datasets opened with another max_minor hold other base codes; their rows agree
- * to rounding (1e-9 on the scale of the estimates), not bit for bit. */
+ * to rounding (1e-9 on the scale of the estimates), not bit for bit.
+ * Saddlepoint p-values over this route: pgh_glm_score_sparse_spa.  Approximate Firth estimates over this route:
+ * pgh_glm_score_sparse_firth. */
 int pgh_glm_score_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                          const double *phenotype, uint32_t n_covar, const double *covariates,
                          pgh_glm_row *out, char *errbuf);
@@ -678,7 +681,7 @@ int pgh_glm_score_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32
  * PGH_GLM_SCORE_SCRATCH_BYTES (environment, read at every call, default 6 GiB) bounds the device scratch that grows
  * with the phenotypes and variants in flight; the result does not depend on it.
  * Saddlepoint p-values over this route: pgh_glm_score_multi_spa.  Approximate Firth estimates over this route:
- * pgh_glm_score_multi_firth.  Not offered: a Firth-penalised null fit, Firth and saddlepoint in one call, dosage
+ * pgh_glm_score_multi_firth (from carrier lists: pgh_glm_score_sparse_firth).  Not offered: a Firth-penalised null fit, Firth and saddlepoint in one call, dosage
  * tracks, shard groups, a table function. */
 int pgh_glm_score_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                         uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
@@ -827,6 +830,57 @@ typedef struct pgh_glm_firth_row {
 int pgh_glm_score_multi_firth(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                               uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
                               double firth_cutoff, pgh_glm_row *out, pgh_glm_firth_row *firth, char *errbuf);
+/* pgh_glm_score_sparse with pgh_glm_score_multi_firth's APPROXIMATE FIRTH estimate beside the one-step score estimate,
+ * for every variant of [v_begin, v_end) of a SPARSE-RESIDENT dataset beyond a cutoff, from the variants' entries: a
+ * row costs in proportion to the samples that differ from its base code.  Arguments, argument checks, error texts and
+ * refusals are pgh_glm_score_sparse's: a dense-resident dataset ("needs a sparse-resident dataset"), a shard group,
+ * 0/1 phenotypes, cases and controls, at most PGH_GLM_MAX_COVAR covariates, the resident range.  In addition
+ * firth_cutoff must be at least 0.1 (+infinity: never apply it; NaN or a smaller value is PGH_ERR_ARG, "firth_cutoff
+ * must be at least 0.1"), and firth, one element per variant, must not be NULL ("null firth").  On any error both
+ * outputs are untouched.  v_begin == v_end is PGH_OK.
+ *
+ * out[i] is pgh_glm_score_sparse's row for the same arguments bit for bit.  Its firth byte stays 0: that byte records
+ * pgh_glm's full Firth fallback, which this is not.
+ *
+ * firth[i].state and values mean what they mean for pgh_glm_score_multi_firth; pad is zero:
+ *   0  the row is not fitted:                      beta, se, p are NaN
+ *   0  the row is fitted with |stat| <= cutoff:    out's beta, se, p bit for bit
+ *   1  applied:                                    the Firth values below
+ *   2  attempted and failed:                       out's beta, se, p bit for bit
+ *
+ * Definition, in pgh_glm_score_sparse's notation (S, N, r, w, the base code b).  The null model is that contract's
+ * maximum-likelihood fit, unchanged.
+ *   mu_i = r_i > 0 ? 1 - r_i : -r_i
+ *   b    = the row's base code; 0 for a missing-majority row and for a row held in the dense form
+ *   d_i  = x_i - b
+ *   E    = the row's used called entries with d_i != 0: an entry is used when its sample is below the sample count and
+ *          in S, and called when its code is not 3
+ *   G    = sum_E d_i r_i
+ * A missing-majority row holds its hom-ref calls as entries; they have d = 0, contribute a constant and are not in E.
+ * The E of a row held in the dense form is its called samples in S with a code other than 0.
+ * K and its four derivatives, l*, F, H with its fallback (where not H > 0, H = K''), the evaluation with one exp of
+ * -|d beta| per entry, the nine-point root iteration, its stopping rules (|delta| sqrt(K''(0)) <= 1e-10, the closed
+ * bracket that narrow, |delta| <= 2^-50 |beta|), the cap of 64 evaluations, the state-2 conditions, and the result
+ * beta = beta^, se = 1 / sqrt(K''(beta^)), D = max(2 (l*(beta^) - l*(0)), 0), p = pgh_glm_p_from_z(sqrt(D)) are
+ * pgh_glm_score_multi_firth's word for word, with d in place of x.
+ *
+ * What follows from d:
+ *   - For a base-0 row, a missing-majority row and a row held in the dense form, E is the dense route's E: the row
+ *     agrees with pgh_glm_score_multi_firth (one phenotype, the same file opened dense) in state and to rounding.
+ *   - For a base-1 or base-2 row the coefficient is estimated with the majority genotype as the reference level and
+ *     the null intercept held fixed.  That is another approximation than the dense route's, not the same number: with a
+ *     fixed offset the estimate depends on the reference coding (the score row does not).  Datasets opened with
+ *     another max_minor agree to rounding only where E is the same set.
+ *   - A fitted row always has a non-empty E (otherwise it would be CONST_ALLELE), so K''(0) > 0.
+ *
+ * A row's (out, firth) is a function of its variant's entries, the phenotype, the covariates, the subset and
+ * firth_cutoff only: not of v_begin, the chunk, the window the dataset was opened with, the grid or the rows around
+ * it, and the same call returns the same bytes every time.  Not offered: a Firth-penalised null fit, Firth and
+ * saddlepoint in one call, the dense route's coding for base-1 and base-2 rows, dosage tracks, shard groups, a table
+ * function. */
+int pgh_glm_score_sparse_firth(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                               const double *phenotype, uint32_t n_covar, const double *covariates,
+                               double firth_cutoff, pgh_glm_row *out, pgh_glm_firth_row *firth, char *errbuf);
 /* Gene-set BURDEN tests over a SPARSE-RESIDENT dataset (pgh_open_sparse), from the variants' entries: per set, the
  * variants are collapsed into one weighted burden per sample and the phenotype is regressed on it (linear).
  *

@@ -617,21 +617,32 @@ int GlmScoreNullFit(uint32_t n_out, const double *d_y, const double *d_z, uint32
 	}
 }
 
+// What a call of a score-test route does after a chunk of rows: nothing; the saddlepoint kernel (GlmScoreSpaKernel,
+// GlmScoreDenseSpaKernel), which replaces the p-value of the rows beyond the cutoff (pgh_glm_score_sparse_spa,
+// pgh_glm_score_multi_spa); or the Firth kernel (GlmScoreSparseFirthKernel, GlmScoreDenseFirthKernel), which writes every
+// row's pgh_glm_firth_row (pgh_glm_score_sparse_firth, pgh_glm_score_multi_firth).  One of the three; the outputs
+// belong to the kind.
+struct GlmScoreFollowUp {
+	enum Kind { kNone, kSpa, kFirth };
+	Kind kind = kNone;
+	double cutoff = 0.0;
+	double *p_spa = nullptr;            // kSpa
+	uint8_t *state = nullptr;           // kSpa
+	pgh_glm_firth_row *firth = nullptr; // kFirth
+};
+
 // pgh_glm_score_sparse on one sparse-resident dataset.  y and z are staged in output-sample order for the null fit,
 // which leaves r and w in raw-sample order (NaN r outside the subset: uploaded so, the fit writes the subset's
 // samples only); z is staged a second time in raw-sample order when there is a subset, as in GlmSparseOne.
-// spa != null (pgh_glm_score_sparse_spa): after a chunk's rows, GlmScoreSpaKernel replaces the p-value of the rows
-// beyond the cutoff; the workgroup form's stashes are cut from the same scratch block, within kSpaStashBytes.
-struct GlmScoreSpaArgs {
-	double cutoff;
-	double *p_spa;
-	uint8_t *state;
-};
+// fu.kind == kSpa (pgh_glm_score_sparse_spa): after a chunk's rows, GlmScoreSpaKernel replaces the p-value of the rows
+// beyond the cutoff.  kFirth (pgh_glm_score_sparse_firth): GlmScoreSparseFirthKernel writes the chunk's
+// pgh_glm_firth_rows.  Either way the workgroup form's stashes are cut from the same scratch block, within
+// kSpaStashBytes.
 constexpr uint64_t kSpaStashBytes = 256ull << 20;
 
 int GlmScoreSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                       const double *phenotype, uint32_t k, const double *covariates, pgh_glm_row *out, char *errbuf,
-                      const GlmScoreSpaArgs *spa = nullptr) {
+                      const GlmScoreFollowUp &fu = GlmScoreFollowUp()) {
 	PGH_ENTER(ds);
 	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct, n_raw = ds->sample_ct;
 	const uint32_t nv_all = v_end - v_begin;
@@ -657,17 +668,21 @@ int GlmScoreSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t 
 	lay.Add(&d_sums, c * ns);
 	lay.Add(&d_hgn, c * ne);
 	lay.Add(&d_rows, c);
-	// the saddlepoint path: [t, U, V], p_spa and the state per chunk variant, and a stash per workgroup of the
-	// workgroup form, at most four workgroups per compute unit
+	// the saddlepoint path: [t, U, V], p_spa and the state per chunk variant; the Firth path: a pgh_glm_firth_row per
+	// chunk variant; both: a stash per workgroup of the workgroup form, at most four workgroups per compute unit
+	const bool spa = fu.kind == GlmScoreFollowUp::kSpa, firth = fu.kind == GlmScoreFollowUp::kFirth;
 	pgh::GlmScoreSpaOut so;
+	pgh_glm_firth_row *d_firth = nullptr;
 	uint8_t *d_stash = nullptr;
 	uint32_t n_groups = 0;
-	if (spa) {
+	if (spa || firth) {
 		const uint64_t per_group = pgh::GlmScoreSpaStashPerGroup(n_raw);
-		PGH_TRY(StashGroups(chunk, 4, per_group, kSpaStashBytes, &n_groups, "glm_score_sparse_spa", errbuf));
-		lay.Add(&so.t, c * (kp + 3));
-		lay.Add(&so.p_spa, c);
-		lay.Add(&so.state, c);
+		PGH_TRY(StashGroups(chunk, 4, per_group, kSpaStashBytes, &n_groups,
+		                    spa ? "glm_score_sparse_spa" : "glm_score_sparse_firth", errbuf));
+		lay.Add(&so.t, c * (kp + 3), spa);
+		lay.Add(&so.p_spa, c, spa);
+		lay.Add(&so.state, c, spa);
+		lay.Add(&d_firth, c, firth);
 		lay.Add(&d_stash, per_group * n_groups);
 	}
 	void *scratch = nullptr;
@@ -694,13 +709,19 @@ int GlmScoreSparseOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t 
 		PGH_HIP(hipMemcpyAsync(out + c0, d_rows, sizeof(pgh_glm_row) * nv, hipMemcpyDeviceToHost, st),
 		        "glm_score_sparse rows copy");
 		if (spa) {
-			PGH_HIP(pgh::LaunchGlmScoreSpa(ds->Sparse(), l_begin + c0, nv, d_r, d_w, d_zr, kp, d_rows, so.t, spa->cutoff,
+			PGH_HIP(pgh::LaunchGlmScoreSpa(ds->Sparse(), l_begin + c0, nv, d_r, d_w, d_zr, kp, d_rows, so.t, fu.cutoff,
 			                               n_groups, d_stash, so.p_spa, so.state, st),
 			        "glm_score_sparse_spa kernel");
-			PGH_HIP(hipMemcpyAsync(spa->p_spa + c0, so.p_spa, 8ull * nv, hipMemcpyDeviceToHost, st),
+			PGH_HIP(hipMemcpyAsync(fu.p_spa + c0, so.p_spa, 8ull * nv, hipMemcpyDeviceToHost, st),
 			        "glm_score_sparse_spa p copy");
-			PGH_HIP(hipMemcpyAsync(spa->state + c0, so.state, nv, hipMemcpyDeviceToHost, st),
+			PGH_HIP(hipMemcpyAsync(fu.state + c0, so.state, nv, hipMemcpyDeviceToHost, st),
 			        "glm_score_sparse_spa state copy");
+		} else if (firth) {
+			PGH_HIP(pgh::LaunchGlmScoreSparseFirth(ds->Sparse(), l_begin + c0, nv, d_r, d_rows, fu.cutoff, n_groups, d_stash,
+			                                       d_firth, st),
+			        "glm_score_sparse_firth kernel");
+			PGH_HIP(hipMemcpyAsync(fu.firth + c0, d_firth, sizeof(pgh_glm_firth_row) * nv, hipMemcpyDeviceToHost, st),
+			        "glm_score_sparse_firth rows copy");
 		}
 		PGH_HIP(hipStreamSynchronize(st), "glm_score_sparse sync");
 	}
@@ -1144,6 +1165,19 @@ int GlmCheckSpa(double spa_cutoff, const double *p_spa, const uint8_t *spa_state
 	return PGH_OK;
 }
 
+// pgh_glm_score_sparse_firth's and pgh_glm_score_multi_firth's own arguments.
+int GlmCheckFirth(double firth_cutoff, const pgh_glm_firth_row *firth, char *errbuf) {
+	if (!(firth_cutoff >= 0.1)) { // (NaN too)
+		SetErr(errbuf, "firth_cutoff must be at least 0.1");
+		return PGH_ERR_ARG;
+	}
+	if (!firth) {
+		SetErr(errbuf, "null firth");
+		return PGH_ERR_ARG;
+	}
+	return PGH_OK;
+}
+
 // The set arguments that pgh_burden_sparse and pgh_skat_sparse share (out: the caller's rows).
 int GlmCheckSets(const pgh_dataset *ds, uint32_t n_sets, const uint64_t *set_off, const uint32_t *set_vidx,
                  const double *weight, const void *out, char *errbuf) {
@@ -1188,10 +1222,11 @@ int GlmCheckSets(const pgh_dataset *ds, uint32_t n_sets, const uint64_t *set_off
 	return PGH_OK;
 }
 
-// pgh_glm_score_sparse and pgh_glm_score_sparse_spa (spa != null) after the latter's own argument checks.
+// pgh_glm_score_sparse, pgh_glm_score_sparse_spa and pgh_glm_score_sparse_firth after the latter two's own argument
+// checks.
 int GlmScoreSparseEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                         const double *phenotype, uint32_t n_covar, const double *covariates, pgh_glm_row *out,
-                        const GlmScoreSpaArgs *spa, char *errbuf) {
+                        const GlmScoreFollowUp &fu, char *errbuf) {
 	PGH_ONE_DEVICE(ds);
 	PGH_SPARSE_ROWS(ds);
 	PGH_TRY(GlmCheckCommon(ds, subset, v_begin, v_end, 1, phenotype, n_covar, covariates, PGH_GLM_LOGISTIC, out, errbuf));
@@ -1199,7 +1234,7 @@ int GlmScoreSparseEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_
 	if (v_end == v_begin) {
 		return PGH_OK;
 	}
-	return GlmScoreSparseOne(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, out, errbuf, spa);
+	return GlmScoreSparseOne(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, out, errbuf, fu);
 }
 
 // pgh_glm_score_multi: the byte budget of the scratch that grows with the phenotype block and the variant chunk (read
@@ -1210,18 +1245,6 @@ int GlmScoreSparseEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_
 constexpr uint64_t kGlmScoreScratchBytes = 6ull << 30;
 const char *const kGlmScoreScratchEnv = "PGH_GLM_SCORE_SCRATCH_BYTES";
 constexpr uint32_t kGlmScoreMultiChunk = 65536;
-
-// What a call of the dense route does after a block's chunk of rows: nothing, GlmScoreDenseSpaKernel, which replaces
-// the p-value of the rows beyond the cutoff (pgh_glm_score_multi_spa), or GlmScoreDenseFirthKernel, which writes every
-// row's pgh_glm_firth_row (pgh_glm_score_multi_firth).  One of the three; the outputs belong to the kind.
-struct GlmScoreFollowUp {
-	enum Kind { kNone, kSpa, kFirth };
-	Kind kind = kNone;
-	double cutoff = 0.0;
-	double *p_spa = nullptr;            // kSpa
-	uint8_t *state = nullptr;           // kSpa
-	pgh_glm_firth_row *firth = nullptr; // kFirth
-};
 
 // The device arrays that scale with the chunk, per (block phenotype, chunk variant).  AddTo is their one declaration:
 // the scratch layout binds it, and the plan charges a chunk variant what it declares for c = 1.
@@ -1519,7 +1542,7 @@ int GlmScoreMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v
 extern "C" int pgh_glm_score_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                                     const double *phenotype, uint32_t n_covar, const double *covariates,
                                     pgh_glm_row *out, char *errbuf) {
-	return GlmScoreSparseEntry(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, out, nullptr, errbuf);
+	return GlmScoreSparseEntry(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, out, {}, errbuf);
 }
 
 extern "C" int pgh_glm_score_sparse_spa(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin,
@@ -1527,8 +1550,17 @@ extern "C" int pgh_glm_score_sparse_spa(const pgh_dataset *ds, const pgh_subset 
                                         const double *covariates, double spa_cutoff, pgh_glm_row *out, double *p_spa,
                                         uint8_t *spa_state, char *errbuf) {
 	PGH_TRY(GlmCheckSpa(spa_cutoff, p_spa, spa_state, errbuf));
-	const GlmScoreSpaArgs spa = {spa_cutoff, p_spa, spa_state};
-	return GlmScoreSparseEntry(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, out, &spa, errbuf);
+	const GlmScoreFollowUp fu = {GlmScoreFollowUp::kSpa, spa_cutoff, p_spa, spa_state, nullptr};
+	return GlmScoreSparseEntry(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, out, fu, errbuf);
+}
+
+extern "C" int pgh_glm_score_sparse_firth(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin,
+                                          uint32_t v_end, const double *phenotype, uint32_t n_covar,
+                                          const double *covariates, double firth_cutoff, pgh_glm_row *out,
+                                          pgh_glm_firth_row *firth, char *errbuf) {
+	PGH_TRY(GlmCheckFirth(firth_cutoff, firth, errbuf));
+	const GlmScoreFollowUp fu = {GlmScoreFollowUp::kFirth, firth_cutoff, nullptr, nullptr, firth};
+	return GlmScoreSparseEntry(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, out, fu, errbuf);
 }
 
 namespace {
@@ -1582,14 +1614,7 @@ extern "C" int pgh_glm_score_multi_firth(const pgh_dataset *ds, const pgh_subset
                                          uint32_t v_end, uint32_t n_pheno, const double *phenotypes, uint32_t n_covar,
                                          const double *covariates, double firth_cutoff, pgh_glm_row *out,
                                          pgh_glm_firth_row *firth, char *errbuf) {
-	if (!(firth_cutoff >= 0.1)) { // (NaN too)
-		SetErr(errbuf, "firth_cutoff must be at least 0.1");
-		return PGH_ERR_ARG;
-	}
-	if (!firth) {
-		SetErr(errbuf, "null firth");
-		return PGH_ERR_ARG;
-	}
+	PGH_TRY(GlmCheckFirth(firth_cutoff, firth, errbuf));
 	const GlmScoreFollowUp fu = {GlmScoreFollowUp::kFirth, firth_cutoff, nullptr, nullptr, firth};
 	return GlmScoreMultiEntry(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, fu, errbuf);
 }

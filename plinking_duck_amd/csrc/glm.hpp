@@ -212,6 +212,15 @@ hipError_t LaunchGlmScoreSpa(const SparseView &sv, uint32_t v_first, uint32_t nv
                              double cutoff, uint32_t n_groups, void *stash, double *p_spa, uint8_t *state,
                              hipStream_t stream);
 
+// ---- pgh_glm_score_sparse_firth (glm_score_sparse_firth.hip): approximate Firth estimates of the score test's rows ----
+// For every row v_first + i (i < nv) of `sv`: firth[i], the contract's triple and state (the score row's beta, se and p
+// with state 0 where the row is not fitted or |stat| <= cutoff).  r: LaunchGlmScoreSparse's; rows: LaunchGlmScoreSolve's.
+// stash: n_groups x GlmScoreSpaStashPerGroup bytes, whatever they hold.  Nothing in the output depends on n_groups
+// (>= 1).
+hipError_t LaunchGlmScoreSparseFirth(const SparseView &sv, uint32_t v_first, uint32_t nv, const double *r,
+                                     const pgh_glm_row *rows, double cutoff, uint32_t n_groups, void *stash,
+                                     pgh_glm_firth_row *firth, hipStream_t stream);
+
 // ---- pgh_glm_score_multi_spa (glm_score_dense_spa.hip): saddlepoint p-values of the dense route's rows ----
 // For the rows (phenotype p < pb, chunk variant i < nv) at p * nv + i that are fitted with |stat| > cutoff: p_spa and
 // state = 1, or state = 2 with p_spa left as it is; the other rows are not touched.  view, v0, nv, mask, pb, b, z0, mz,

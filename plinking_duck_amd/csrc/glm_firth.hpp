@@ -1,6 +1,7 @@
-// glm_firth.hpp -- phase B of GlmScoreDenseFirthKernel (glm_score_dense_firth.hip): the approximate Firth estimate of a
-// row's own coefficient from one team's stash of (x, mu) pairs, with glm_spa.hpp's pi and K (the contract is
-// pgh_glm_score_multi_firth's in include/pgenhip.h).
+// glm_firth.hpp -- phase B of GlmScoreDenseFirthKernel (glm_score_dense_firth.hip) and GlmScoreSparseFirthKernel
+// (glm_score_sparse_firth.hip): the approximate Firth estimate of a row's own coefficient from one team's stash of
+// (x, mu) pairs, with glm_spa.hpp's pi and K (the contract is pgh_glm_score_multi_firth's in include/pgenhip.h;
+// pgh_glm_score_sparse_firth's pairs hold d = x - b in x's place).
 #pragma once
 
 #include "glm_spa.hpp"

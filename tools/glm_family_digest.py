@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """One SHA-256 per case over the result bytes of the GLM family (pgh_glm, pgh_glm_multi, pgh_glm_sparse,
-pgh_glm_score_sparse, pgh_glm_score_sparse_spa, pgh_glm_score_multi, pgh_glm_score_multi_spa, pgh_glm_score_multi_firth,
-pgh_burden_sparse), pgh_score_sparse, and the plink_ld pair sums and sparse counts that share their wave sums: the
+pgh_glm_score_sparse, pgh_glm_score_sparse_spa, pgh_glm_score_sparse_firth, pgh_glm_score_multi, pgh_glm_score_multi_spa,
+pgh_glm_score_multi_firth, pgh_burden_sparse), pgh_score_sparse, and the plink_ld pair sums and sparse counts that share their wave sums: the
 paths a change to the family's kernels, host staging, scratch layout or chunk loops can touch.  Two builds of the library
 compute the same rows bit for bit exactly when their outputs of this tool are equal line for line; PGENHIP_LIB names
 the build (plinking_duck_amd/lib.py).  A case that differs between two runs of ONE build is not deterministic from
@@ -208,7 +208,7 @@ emit("glm_score_sparse across a chunk", sp.glm_score_sparse(pheno(rng, N_C, Zc, 
 sp.close()
 
 # ---- the score tests that share the ranked row walk and the budget plan: pgh_glm_score_multi, _multi_spa, _multi_firth
-# and pgh_glm_score_sparse_spa, on the inputs of their tests ---------------------------------------------------------
+# and pgh_glm_score_sparse_spa, on the inputs of their tests; and pgh_glm_score_sparse_firth beside the latter -----------
 import subset_shapes as SS  # noqa: E402
 import test_glm_score_multi as GM  # noqa: E402
 import test_glm_score_multi_spa as MS  # noqa: E402
@@ -253,6 +253,8 @@ for n in (4096, 4099, 8209):  # one full step of the walk, a second step of thre
         for form, sp in forms:
             res = sp.glm_score_sparse_spa(case.y, Zk, cutoff=CUT)
             emit(f"glm_score_sparse_spa {form}, n={n} k={k}", res, note=share(res, "spa_state"))
+            res = sp.glm_score_sparse_firth(case.y, Zk, firth_cutoff=CUT)
+            emit(f"glm_score_sparse_firth {form}, n={n} k={k}", res, note=share(res, "firth_state"))
     if n == 4099:
         # a subset that cuts every 16-code word
         keep_w = SS.shapes(n)["stride4"]
@@ -264,6 +266,8 @@ for n in (4096, 4099, 8209):  # one full step of the walk, a second step of thre
             sub = sp.subset(keep_w)
             res = sp.glm_score_sparse_spa(case.y[keep_w], Zs4, cutoff=CUT, subset=sub)
             emit(f"glm_score_sparse_spa {form}, n={n} k=4 subset", res, note=share(res, "spa_state"))
+            res = sp.glm_score_sparse_firth(case.y[keep_w], Zs4, firth_cutoff=CUT, subset=sub)
+            emit(f"glm_score_sparse_firth {form}, n={n} k=4 subset", res, note=share(res, "firth_state"))
             sub.close()
         # Scratch budgets (k = 4).  The block of one phenotype and its mask are 2,129,920 + 1,040 = 2,130,960 bytes,
         # more than three quarters of either budget: one phenotype per block.  2,400,960 leaves 270,000: 270,000 / 4 * 3 /

@@ -30,9 +30,9 @@ import glm_score_spa_model as M  # noqa: E402
 from glm_score_dense_spa_model import TEAM, word_sum  # noqa: E402
 
 
-def phase_b(x, mu, g):
-    """(beta, se, p, evaluations) from the workgroup's stash of (x, mu) pairs as the device computes them; beta None:
-    state 2."""
+def phase_b(x, mu, g, TEAM=TEAM):
+    """(beta, se, p, evaluations) from the team's stash of (x, mu) pairs as the device computes them (TEAM: its
+    threads, the workgroup's here; tools/glm_score_sparse_firth_model.py also has a wave's 64); beta None: state 2."""
     sgn, u, lo, hi, grow, tol, l0 = 0.0, 0.0, 0.0, math.inf, 0.0, 0.0, 0.0
     for ev in range(1, F.MAX_EVAL + 1):
         beta = sgn * u
