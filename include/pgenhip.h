@@ -650,7 +650,7 @@ int pgh_glm_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_b
  * every time, the null fit included.  Datasets opened with another max_minor hold other base codes; their rows agree
  * to rounding (1e-9 on the scale of the estimates), not bit for bit.
  * Saddlepoint p-values over this route: pgh_glm_score_sparse_spa.  Approximate Firth estimates over this route:
- * pgh_glm_score_sparse_firth. */
+ * pgh_glm_score_sparse_firth.  Many phenotypes in one walk of the entries: pgh_glm_score_sparse_multi. */
 int pgh_glm_score_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                          const double *phenotype, uint32_t n_covar, const double *covariates,
                          pgh_glm_row *out, char *errbuf);
@@ -681,11 +681,46 @@ int pgh_glm_score_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32
  * PGH_GLM_SCORE_SCRATCH_BYTES (environment, read at every call, default 6 GiB) bounds the device scratch that grows
  * with the phenotypes and variants in flight; the result does not depend on it.
  * Saddlepoint p-values over this route: pgh_glm_score_multi_spa.  Approximate Firth estimates over this route:
- * pgh_glm_score_multi_firth (from carrier lists: pgh_glm_score_sparse_firth).  Not offered: a Firth-penalised null fit, Firth and saddlepoint in one call, dosage
+ * pgh_glm_score_multi_firth (from carrier lists: pgh_glm_score_sparse_firth).  Many phenotypes over a sparse-resident
+ * dataset: pgh_glm_score_sparse_multi.  Not offered: a Firth-penalised null fit, Firth and saddlepoint in one call, dosage
  * tracks, shard groups, a table function. */
 int pgh_glm_score_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                         uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
                         pgh_glm_row *out, char *errbuf);
+/* The logistic score test of every variant of [v_begin, v_end) of a SPARSE-RESIDENT dataset (pgh_open_sparse) for
+ * n_pheno case/control phenotypes in one call: one null fit per phenotype, then one walk of the variants' entries per
+ * block of at most 64 phenotypes, in which an entry's word and covariate row are read once for the block.  The
+ * arguments and the layout of `out` are pgh_glm_score_multi's: phenotypes is [n_pheno][n_out], and
+ * out[(v - v_begin) * n_pheno + p] is phenotype p's row for variant v.
+ *
+ * Row contract.  Each row is the row that pgh_glm_score_sparse's contract above defines, for that phenotype alone: the
+ * base codes, d = x - b, M, C and N, the missing-majority rule, the rows held in the dense form treated as base-0 rows
+ * and the order of the decisions are the ones defined there; firth is 0.  obs_ct, a1_freq, TOO_FEW_SAMPLES and
+ * CONST_ALLELE equal pgh_glm's with model = PGH_GLM_LOGISTIC for the same file, bit for bit (the counts are integers
+ * until they are stored).  The estimates agree with pgh_glm_score_sparse for the same phenotype to rounding (1e-9 on
+ * their scale), with equal errcodes, not bit for bit: the sums are taken in another order (a row's entries in
+ * consecutive segments of 1024, each one chain, added in ascending order).  A null fit that fails decides only its own
+ * phenotype's rows.
+ *
+ * A row is a function of its variant's entries, its own phenotype, the covariates and the subset only: not of the
+ * other phenotypes of the call or its place among them, of n_pheno, the phenotype block, the rows that share a wave or
+ * a workgroup with it, v_begin, the variant chunk, the window the dataset was opened with or the scratch budget, and
+ * the same call returns the same bytes every time.
+ *
+ * PGH_ERR_ARG, `out` untouched: everything pgh_glm_score_multi refuses in the shared arguments (n_pheno == 0, "phenotype
+ * must be 0 or 1" and "no cases or no controls", each followed by the phenotype's index, included); a dataset that is
+ * not sparse-resident ("needs a sparse-resident dataset"); a shard group (pass pgh_shard(group, k)).
+ * v_begin == v_end is PGH_OK.
+ *
+ * PGH_GLM_SCORE_SCRATCH_BYTES (environment, read at every call, default 6 GiB) bounds the device scratch that grows
+ * with the phenotypes and variants in flight (16 bytes per sample and block phenotype, then the chunk's sums); the
+ * result does not depend on it.
+ * Not offered: saddlepoint p-values and approximate Firth estimates over this route (one phenotype at a time:
+ * pgh_glm_score_sparse_spa, pgh_glm_score_sparse_firth), quantitative phenotypes, dosage tracks, shard groups, a table
+ * function. */
+int pgh_glm_score_sparse_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                               uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
+                               pgh_glm_row *out, char *errbuf);
 /* pgh_glm_score_sparse with a SADDLEPOINT p-value beside the normal one, for the rows the normal tail serves badly:
  * rare variants under an unbalanced case / control ratio (the "fast SPA" of Dey et al. 2017: the exact cumulant
  * generating function over the row's entries, a normal term for every other sample).  Arguments, argument checks and

@@ -3,7 +3,8 @@
 // dataset, from its entries (glm_sparse.hip); pgh_burden_sparse: gene-set burden fits over such a dataset
 // (burden_sparse.hip); pgh_glm_score_sparse: the logistic score test over such a dataset, from its entries
 // (glm_score_sparse.hip); pgh_glm_score_multi: that test over a dense-resident dataset for many phenotypes in one
-// call, on the FP64 matrix cores (glm_score_dense.hip); pgh_skat_sparse: SKAT and burden score tests of variant sets under that test's null model
+// call, on the FP64 matrix cores (glm_score_dense.hip); pgh_glm_score_sparse_multi: that test over a sparse-resident
+// dataset for many phenotypes in one walk of its entries (glm_score_sparse_multi.hip); pgh_skat_sparse: SKAT and burden score tests of variant sets under that test's null model
 // (skat_sparse.hip, skat_math.hpp, linalg.cpp).
 #include "api_internal.hpp"
 #include "glm.hpp"
@@ -1305,18 +1306,46 @@ GlmScoreMultiPlan GlmScoreMultiPlanFor(uint32_t n_raw, uint32_t n_pheno, uint32_
 	return plan;
 }
 
-// One call of pgh_glm_score_multi* on one dense-resident dataset, after the argument checks: what its parts share.
+// pgh_glm_score_sparse_multi: how a call splits the same budget.  The pair block takes 16 n_raw bytes per phenotype; it
+// gets the most phenotypes, kGlmScoreSparsePb at most, that leave one chunk variant's arrays within the budget (one
+// phenotype whatever the budget), and what it leaves bounds the chunk at GlmScoreMultiChunkArrays' bytes per variant.
+// The rounding and the block's own small arrays are not charged, as in GlmScoreMultiPlanFor.
+GlmScoreMultiPlan GlmScoreSparseMultiPlanFor(uint32_t n_raw, uint32_t n_pheno, uint32_t k, uint32_t nv_all,
+                                             uint64_t budget) {
+	const uint32_t kp = pgh::GlmPadCovar(k);
+	const auto block_bytes = [&](uint32_t pb) { return 16ull * n_raw * pb; };
+	const auto variant_bytes = [&](uint32_t pb) {
+		GlmScoreMultiChunkArrays unit;
+		ScratchLayout one_variant;
+		unit.AddTo(one_variant, pb, 1, kp, k, GlmScoreFollowUp::kNone);
+		return one_variant.payload;
+	};
+	GlmScoreMultiPlan plan;
+	plan.pb_max = std::min(pgh::kGlmScoreSparsePb, n_pheno);
+	while (plan.pb_max > 1 && block_bytes(plan.pb_max) + variant_bytes(plan.pb_max) > budget) {
+		plan.pb_max--;
+	}
+	const uint64_t left = budget > block_bytes(plan.pb_max) ? budget - block_bytes(plan.pb_max) : 0;
+	const uint32_t nv_most = std::min(kGlmScoreMultiChunk, nv_all);
+	plan.chunk = static_cast<uint32_t>(std::min<uint64_t>(nv_most, std::max<uint64_t>(1, left / variant_bytes(plan.pb_max))));
+	return plan;
+}
+
+// What one call of pgh_glm_score_multi* (a dense-resident dataset) and of pgh_glm_score_sparse_multi (a sparse-resident
+// one) share after the argument checks: the pattern order, the staging of a pattern group, the null fit of a block
+// phenotype, the solve of a chunk's rows phenotype by phenotype and their scatter into the caller's rows.
 // The null models are fitted phenotype by phenotype by GlmScoreNullFit, as GlmScoreSparseOne fits its one: on the
 // covariates centred over the phenotype's missing-value pattern, which the phenotypes of a pattern share (GlmStage's
-// sums and subtraction, the latter on the device).  Each fit's r and w go straight into the phenotype's columns of the
-// block (glm_score_dense.hip).
-struct GlmScoreMultiCall {
+// sums and subtraction, the latter on the device).
+struct GlmScoreBlockCall {
 	const pgh_dataset *ds;
 	const pgh_subset *subset;
 	uint32_t v_begin, nv_all, n_pheno, k;
 	const double *phenotypes, *covariates;
 	GlmScoreFollowUp fu;
 	char *errbuf;
+	const char *who; // the entry point's name in the error texts
+	bool want_mask;  // a group's S as the dense kernels' sample mask
 	hipStream_t st = PghThreadStream();
 	uint32_t n_out = subset ? subset->n_out : ds->sample_ct, n_raw = ds->sample_ct;
 	uint32_t kp = pgh::GlmPadCovar(k), ns = kp + 6, ne = (k + 1) * (k + 2) / 2 + k + 1;
@@ -1337,25 +1366,28 @@ struct GlmScoreMultiCall {
 	std::vector<GroupStage> gs;
 	uint32_t centred_for = UINT32_MAX; // the group d_z is centred for
 
-	double *d_y, *d_z0, *d_z, *d_zr0, *d_r, *d_w, *d_part, *d_hg1, *d_hg, *d_mz, *d_b;
-	uint32_t *d_ny, *d_mask;
+	double *d_y, *d_z0, *d_z, *d_zr0, *d_r, *d_w, *d_part, *d_hg1, *d_hg, *d_mz;
+	uint32_t *d_ny;
 	GlmScoreMultiChunkArrays ch;
-	uint8_t *d_stash;
-	// the current block's |S| and null-fit status per phenotype, the current chunk's results
+	// the current block's |S| and null-fit status per phenotype, the current chunk's rows
 	std::vector<uint32_t> h_ny;
 	std::vector<int> status;
 	std::vector<pgh_glm_row> hrows;
-	std::vector<double> hp_spa;
-	std::vector<uint8_t> hstate;
-	std::vector<pgh_glm_firth_row> hfirth;
 
-	int Prepare();
-	int StageBlock(uint32_t b0, uint32_t pb);
-	int RunChunk(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t nv, pgh_glm_row *out);
+	std::string What(const char *part) const {
+		return std::string(who) + " " + part;
+	}
+	void PatternOrder();
+	void AddShared(ScratchLayout &lay);
+	int UploadCovariates(const GlmStaged &sg);
+	GroupStage &StageGroup(uint32_t p);
+	int FitPhenotype(uint32_t b0, uint32_t j);
+	int SolveRows(uint32_t pb, uint32_t nv);
+	template <class T>
+	void Scatter(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t nv, const std::vector<T> &from, T *to) const;
 };
 
-// The pattern order, the plan, the scratch block and the host buffers.
-int GlmScoreMultiCall::Prepare() {
+void GlmScoreBlockCall::PatternOrder() {
 	const std::vector<std::vector<uint32_t>> groups = GlmPatternGroups(n_pheno, phenotypes, n_out);
 	group_of.resize(n_pheno);
 	for (uint32_t g = 0; g < groups.size(); g++) {
@@ -1365,15 +1397,11 @@ int GlmScoreMultiCall::Prepare() {
 		}
 	}
 	gs.resize(groups.size());
+}
 
-	int cus = 0;
-	if (fu.kind != GlmScoreFollowUp::kNone) {
-		PGH_TRY(DeviceCus(&cus, "glm_score_multi stash", errbuf));
-	}
-	plan = GlmScoreMultiPlanFor(n_raw, n_pheno, k, nv_all, EnvBytes(kGlmScoreScratchEnv, kGlmScoreScratchBytes), cus, fu.kind);
-
+// The arrays of every route, after the plan is made; sizes the host buffers of a block and a chunk.
+void GlmScoreBlockCall::AddShared(ScratchLayout &lay) {
 	const uint64_t n = n_out, nr = n_raw, pbm = plan.pb_max;
-	ScratchLayout lay;
 	lay.Add(&d_y, n);
 	lay.Add(&d_z0, n * kp + 1); // one element of slack, here and in d_z, d_zr0, d_mz
 	lay.Add(&d_z, n * kp + 1);
@@ -1385,87 +1413,80 @@ int GlmScoreMultiCall::Prepare() {
 	lay.Add(&d_hg, pbm * ne);
 	lay.Add(&d_mz, pbm * kp + 1);
 	lay.Add(&d_ny, pbm);
-	lay.Add(&d_mask, pbm * mask_words);
-	lay.Add(&d_b, n_pad * pgh::GlmScoreDenseLayout(plan.pb_max, k).ld);
-	ch.AddTo(lay, pbm, plan.chunk, kp, k, fu.kind);
-	lay.Add(&d_stash, plan.stash_bytes, fu.kind != GlmScoreFollowUp::kNone);
-	void *scratch = nullptr;
-	PGH_HIP(PghThreadScratch(lay.total, st, &scratch), "glm_score_multi scratch");
-	lay.Bind(scratch);
-	if (!subset) {
-		d_zr0 = d_z0;
-	}
-
 	h_ny.resize(plan.pb_max);
 	status.resize(plan.pb_max);
 	hrows.resize(static_cast<size_t>(plan.chunk) * plan.pb_max);
-	hp_spa.resize(fu.kind == GlmScoreFollowUp::kSpa ? hrows.size() : 0);
-	hstate.resize(fu.kind == GlmScoreFollowUp::kSpa ? hrows.size() : 0);
-	hfirth.resize(fu.kind == GlmScoreFollowUp::kFirth ? hrows.size() : 0);
+}
+
+// sg.hz (and hz_raw): the covariates as they are
+int GlmScoreBlockCall::UploadCovariates(const GlmStaged &sg) {
+	if (!subset) {
+		d_zr0 = d_z0;
+	}
+	if (kp) {
+		PGH_HIP(hipMemcpyAsync(d_z0, sg.hz.data(), 8ull * sg.hz.size(), hipMemcpyHostToDevice, st),
+		        What("covariate upload").c_str());
+	}
+	if (sg.raw && kp) {
+		PGH_HIP(hipMemcpyAsync(d_zr0, sg.hz_raw.data(), 8ull * sg.hz_raw.size(), hipMemcpyHostToDevice, st),
+		        What("covariate upload (raw order)").c_str());
+	}
 	return PGH_OK;
 }
 
-// The block of the phenotypes order[b0 .. b0 + pb): per phenotype its group's mask and means, the centring, the null
-// fit and the columns.
-int GlmScoreMultiCall::StageBlock(uint32_t b0, uint32_t pb) {
-	const uint32_t ld = pgh::GlmScoreDenseLayout(pb, k).ld;
-	PGH_HIP(hipMemsetAsync(d_b, 0, 8ull * n_pad * ld, st), "glm_score_multi column block clear");
-	for (uint32_t j = 0; j < pb; j++) {
-		const uint32_t p = order[b0 + j], g = group_of[p];
-		const double *y = phenotypes + static_cast<size_t>(p) * n_out;
-		GroupStage &gr = gs[g];
-		if (!gr.ready) {
-			gr.ready = true;
-			gr.mask.assign(mask_words, 0u);
-			for (uint32_t i = 0; i < n_out; i++) {
-				if (!std::isnan(y[i])) {
+GlmScoreBlockCall::GroupStage &GlmScoreBlockCall::StageGroup(uint32_t p) {
+	const double *y = phenotypes + static_cast<size_t>(p) * n_out;
+	GroupStage &gr = gs[group_of[p]];
+	if (!gr.ready) {
+		gr.ready = true;
+		gr.mask.assign(want_mask ? mask_words : 0, 0u);
+		for (uint32_t i = 0; i < n_out; i++) {
+			if (!std::isnan(y[i])) {
+				if (want_mask) {
 					const uint32_t s = subset ? subset->sel[i] : i;
 					gr.mask[s >> 4] |= 1u << (2u * (s & 15u));
-					gr.n_y++;
 				}
-			}
-			gr.mz.assign(kp + 1, 0.0);
-			for (uint32_t jz = 0; jz < k && gr.n_y; jz++) {
-				const double *zc = covariates + static_cast<size_t>(jz) * n_out;
-				double mz = 0.0;
-				for (uint32_t i = 0; i < n_out; i++) {
-					mz += std::isnan(y[i]) ? 0.0 : zc[i];
-				}
-				gr.mz[jz] = mz / gr.n_y;
+				gr.n_y++;
 			}
 		}
-		h_ny[j] = gr.n_y;
-		PGH_HIP(hipMemcpyAsync(d_mask + j * mask_words, gr.mask.data(), 4ull * mask_words, hipMemcpyHostToDevice, st),
-		        "glm_score_multi mask upload");
-		if (kp) {
-			PGH_HIP(hipMemcpyAsync(d_mz + static_cast<uint64_t>(j) * kp, gr.mz.data(), 8ull * kp, hipMemcpyHostToDevice, st),
-			        "glm_score_multi mean upload");
-			if (centred_for != g) {
-				PGH_HIP(pgh::LaunchGlmScoreDenseCentre(n_out, kp, d_z0, d_mz + static_cast<uint64_t>(j) * kp, d_z, st),
-				        "glm_score_multi centring kernel");
-				centred_for = g;
+		gr.mz.assign(kp + 1, 0.0);
+		for (uint32_t jz = 0; jz < k && gr.n_y; jz++) {
+			const double *zc = covariates + static_cast<size_t>(jz) * n_out;
+			double mz = 0.0;
+			for (uint32_t i = 0; i < n_out; i++) {
+				mz += std::isnan(y[i]) ? 0.0 : zc[i];
 			}
+			gr.mz[jz] = mz / gr.n_y;
 		}
-		PGH_HIP(hipMemcpyAsync(d_y, y, 8ull * n_out, hipMemcpyHostToDevice, st), "glm_score_multi phenotype upload");
-		PGH_TRY(GlmScoreNullFit(n_out, d_y, d_z, kp, k, d_sel, gr.n_y >= k + 3, d_r, d_w, d_part, d_hg1, st, &status[j],
-		                        errbuf));
-		PGH_HIP(hipMemcpyAsync(d_hg + static_cast<uint64_t>(j) * ne, d_hg1, 8ull * ne, hipMemcpyDeviceToDevice, st),
-		        "glm_score_multi null model copy");
-		PGH_HIP(pgh::LaunchGlmScoreDenseColumns(n_out, d_sel, d_r, d_w, d_z, kp, k, pb, j, d_b, st),
-		        "glm_score_multi column kernel");
 	}
-	PGH_HIP(hipMemcpyAsync(d_ny, h_ny.data(), 4ull * pb, hipMemcpyHostToDevice, st), "glm_score_multi count upload");
+	return gr;
+}
+
+// Block phenotype j, the phenotype order[b0 + j]: its group's stage, the means and the centring, and the null fit,
+// which leaves r and w in d_r / d_w (raw-sample order, the subset's samples) and the packed sums in d_hg[j].
+int GlmScoreBlockCall::FitPhenotype(uint32_t b0, uint32_t j) {
+	const uint32_t p = order[b0 + j], g = group_of[p];
+	const double *y = phenotypes + static_cast<size_t>(p) * n_out;
+	const GroupStage &gr = StageGroup(p);
+	h_ny[j] = gr.n_y;
+	if (kp) {
+		PGH_HIP(hipMemcpyAsync(d_mz + static_cast<uint64_t>(j) * kp, gr.mz.data(), 8ull * kp, hipMemcpyHostToDevice, st),
+		        What("mean upload").c_str());
+		if (centred_for != g) {
+			PGH_HIP(pgh::LaunchGlmScoreDenseCentre(n_out, kp, d_z0, d_mz + static_cast<uint64_t>(j) * kp, d_z, st),
+			        What("centring kernel").c_str());
+			centred_for = g;
+		}
+	}
+	PGH_HIP(hipMemcpyAsync(d_y, y, 8ull * n_out, hipMemcpyHostToDevice, st), What("phenotype upload").c_str());
+	PGH_TRY(GlmScoreNullFit(n_out, d_y, d_z, kp, k, d_sel, gr.n_y >= k + 3, d_r, d_w, d_part, d_hg1, st, &status[j], errbuf));
+	PGH_HIP(hipMemcpyAsync(d_hg + static_cast<uint64_t>(j) * ne, d_hg1, 8ull * ne, hipMemcpyDeviceToDevice, st),
+	        What("null model copy").c_str());
 	return PGH_OK;
 }
 
-// The variants c0 .. c0 + nv - 1 of the range against the staged block: the launches, the copies, and the scatter
-// into the caller's arrays ([variant][phenotype], the phenotypes in the caller's order).
-int GlmScoreMultiCall::RunChunk(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t nv, pgh_glm_row *out) {
-	const uint32_t l0 = v_begin + c0 - ds->v_begin;
-	const size_t n_rows = static_cast<size_t>(nv) * pb;
-	PGH_HIP(pgh::LaunchGlmScoreDense(ds->View(), l0, nv, d_mask, d_ny, pb, d_b, d_zr0, d_mz, kp, k, d_hg, ch.sums, ch.nmiss,
-	                                 ch.hgn, st),
-	        "glm_score_multi kernels");
+// The rows of the chunk's nv variants from ch.sums and ch.hgn, phenotype by phenotype, and their copy to hrows.
+int GlmScoreBlockCall::SolveRows(uint32_t pb, uint32_t nv) {
 	for (uint32_t j = 0; j < pb; j++) {
 		const uint64_t at = static_cast<uint64_t>(j) * nv;
 		pgh::GlmScoreSpaOut soj;
@@ -1475,10 +1496,89 @@ int GlmScoreMultiCall::RunChunk(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t 
 			soj.state = ch.so.state + at;
 		}
 		PGH_HIP(pgh::LaunchGlmScoreSolve(nv, ch.sums + at * ns, kp, k, ch.hgn + at * ne, status[j], ch.rows + at, st, soj),
-		        "glm_score_multi solve kernel");
+		        What("solve kernel").c_str());
 	}
-	PGH_HIP(hipMemcpyAsync(hrows.data(), ch.rows, sizeof(pgh_glm_row) * n_rows, hipMemcpyDeviceToHost, st),
-	        "glm_score_multi rows copy");
+	PGH_HIP(hipMemcpyAsync(hrows.data(), ch.rows, sizeof(pgh_glm_row) * nv * pb, hipMemcpyDeviceToHost, st),
+	        What("rows copy").c_str());
+	return PGH_OK;
+}
+
+// from[block phenotype j][chunk variant i] into the caller's [variant][phenotype], the phenotypes in the caller's order.
+template <class T>
+void GlmScoreBlockCall::Scatter(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t nv, const std::vector<T> &from,
+                                T *to) const {
+	for (uint32_t i = 0; i < nv; i++) {
+		for (uint32_t j = 0; j < pb; j++) {
+			to[static_cast<size_t>(c0 + i) * n_pheno + order[b0 + j]] = from[static_cast<size_t>(j) * nv + i];
+		}
+	}
+}
+
+// One call of pgh_glm_score_multi* on one dense-resident dataset.  Each fit's r and w go straight into the phenotype's
+// columns of the block (glm_score_dense.hip).
+struct GlmScoreMultiCall : GlmScoreBlockCall {
+	double *d_b;
+	uint32_t *d_mask;
+	uint8_t *d_stash;
+	std::vector<double> hp_spa;
+	std::vector<uint8_t> hstate;
+	std::vector<pgh_glm_firth_row> hfirth;
+
+	int Prepare();
+	int StageBlock(uint32_t b0, uint32_t pb);
+	int RunChunk(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t nv, pgh_glm_row *out);
+};
+
+// The pattern order, the plan, the scratch block and the host buffers.
+int GlmScoreMultiCall::Prepare() {
+	PatternOrder();
+	int cus = 0;
+	if (fu.kind != GlmScoreFollowUp::kNone) {
+		PGH_TRY(DeviceCus(&cus, "glm_score_multi stash", errbuf));
+	}
+	plan = GlmScoreMultiPlanFor(n_raw, n_pheno, k, nv_all, EnvBytes(kGlmScoreScratchEnv, kGlmScoreScratchBytes), cus, fu.kind);
+
+	ScratchLayout lay;
+	AddShared(lay);
+	lay.Add(&d_mask, plan.pb_max * mask_words);
+	lay.Add(&d_b, n_pad * pgh::GlmScoreDenseLayout(plan.pb_max, k).ld);
+	ch.AddTo(lay, plan.pb_max, plan.chunk, kp, k, fu.kind);
+	lay.Add(&d_stash, plan.stash_bytes, fu.kind != GlmScoreFollowUp::kNone);
+	void *scratch = nullptr;
+	PGH_HIP(PghThreadScratch(lay.total, st, &scratch), "glm_score_multi scratch");
+	lay.Bind(scratch);
+
+	hp_spa.resize(fu.kind == GlmScoreFollowUp::kSpa ? hrows.size() : 0);
+	hstate.resize(fu.kind == GlmScoreFollowUp::kSpa ? hrows.size() : 0);
+	hfirth.resize(fu.kind == GlmScoreFollowUp::kFirth ? hrows.size() : 0);
+	return PGH_OK;
+}
+
+// The block of the phenotypes order[b0 .. b0 + pb): per phenotype its null fit, its group's mask and the columns.
+int GlmScoreMultiCall::StageBlock(uint32_t b0, uint32_t pb) {
+	const uint32_t ld = pgh::GlmScoreDenseLayout(pb, k).ld;
+	PGH_HIP(hipMemsetAsync(d_b, 0, 8ull * n_pad * ld, st), "glm_score_multi column block clear");
+	for (uint32_t j = 0; j < pb; j++) {
+		PGH_TRY(FitPhenotype(b0, j));
+		PGH_HIP(hipMemcpyAsync(d_mask + j * mask_words, StageGroup(order[b0 + j]).mask.data(), 4ull * mask_words,
+		                       hipMemcpyHostToDevice, st),
+		        "glm_score_multi mask upload");
+		PGH_HIP(pgh::LaunchGlmScoreDenseColumns(n_out, d_sel, d_r, d_w, d_z, kp, k, pb, j, d_b, st),
+		        "glm_score_multi column kernel");
+	}
+	PGH_HIP(hipMemcpyAsync(d_ny, h_ny.data(), 4ull * pb, hipMemcpyHostToDevice, st), "glm_score_multi count upload");
+	return PGH_OK;
+}
+
+// The variants c0 .. c0 + nv - 1 of the range against the staged block: the launches, the copies, and the scatter
+// into the caller's arrays.
+int GlmScoreMultiCall::RunChunk(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t nv, pgh_glm_row *out) {
+	const uint32_t l0 = v_begin + c0 - ds->v_begin;
+	const size_t n_rows = static_cast<size_t>(nv) * pb;
+	PGH_HIP(pgh::LaunchGlmScoreDense(ds->View(), l0, nv, d_mask, d_ny, pb, d_b, d_zr0, d_mz, kp, k, d_hg, ch.sums, ch.nmiss,
+	                                 ch.hgn, st),
+	        "glm_score_multi kernels");
+	PGH_TRY(SolveRows(pb, nv));
 	if (fu.kind == GlmScoreFollowUp::kSpa) {
 		PGH_HIP(pgh::LaunchGlmScoreDenseSpa(ds->View(), l0, nv, d_mask, pb, d_b, d_zr0, d_mz, kp, k, ch.sums, ch.rows, ch.so.t,
 		                                    fu.cutoff, plan.n_groups, d_stash, ch.so.p_spa, ch.so.state, st),
@@ -1495,16 +1595,76 @@ int GlmScoreMultiCall::RunChunk(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t 
 		        "glm_score_multi_firth rows copy");
 	}
 	PGH_HIP(hipStreamSynchronize(st), "glm_score_multi sync");
-	for (uint32_t i = 0; i < nv; i++) {
-		for (uint32_t j = 0; j < pb; j++) {
-			const size_t to = static_cast<size_t>(c0 + i) * n_pheno + order[b0 + j], from = static_cast<size_t>(j) * nv + i;
-			out[to] = hrows[from];
-			if (fu.kind == GlmScoreFollowUp::kSpa) {
-				fu.p_spa[to] = hp_spa[from];
-				fu.state[to] = hstate[from];
-			} else if (fu.kind == GlmScoreFollowUp::kFirth) {
-				fu.firth[to] = hfirth[from];
-			}
+	Scatter(b0, pb, c0, nv, hrows, out);
+	if (fu.kind == GlmScoreFollowUp::kSpa) {
+		Scatter(b0, pb, c0, nv, hp_spa, fu.p_spa);
+		Scatter(b0, pb, c0, nv, hstate, fu.state);
+	} else if (fu.kind == GlmScoreFollowUp::kFirth) {
+		Scatter(b0, pb, c0, nv, hfirth, fu.firth);
+	}
+	return PGH_OK;
+}
+
+// One call of pgh_glm_score_sparse_multi on one sparse-resident dataset.  Each fit's r and w go into the phenotype's
+// column of the pair block (glm_score_sparse_multi.hip); the entry kernel centres the raw-order covariates per lane on
+// the block's means d_mz.
+struct GlmScoreSparseMultiCall : GlmScoreBlockCall {
+	double *d_pair;
+
+	int Prepare();
+	int StageBlock(uint32_t b0, uint32_t pb);
+	int RunChunk(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t nv, pgh_glm_row *out);
+};
+
+int GlmScoreSparseMultiCall::Prepare() {
+	PatternOrder();
+	plan = GlmScoreSparseMultiPlanFor(n_raw, n_pheno, k, nv_all, EnvBytes(kGlmScoreScratchEnv, kGlmScoreScratchBytes));
+	ScratchLayout lay;
+	AddShared(lay);
+	lay.Add(&d_pair, 2ull * n_raw * plan.pb_max);
+	ch.AddTo(lay, plan.pb_max, plan.chunk, kp, k, GlmScoreFollowUp::kNone);
+	void *scratch = nullptr;
+	PGH_HIP(PghThreadScratch(lay.total, st, &scratch), "glm_score_sparse_multi scratch");
+	lay.Bind(scratch);
+	return PGH_OK;
+}
+
+// The block of the phenotypes order[b0 .. b0 + pb): the pair block cleared, then per phenotype its null fit and its
+// pairs.  With a subset the fit writes the subset's samples only, and only those are scattered.
+int GlmScoreSparseMultiCall::StageBlock(uint32_t b0, uint32_t pb) {
+	PGH_HIP(pgh::LaunchGlmScoreSparsePairClear(n_raw, pb, d_pair, st), "glm_score_sparse_multi pair block clear");
+	for (uint32_t j = 0; j < pb; j++) {
+		PGH_TRY(FitPhenotype(b0, j));
+		PGH_HIP(pgh::LaunchGlmScoreSparsePairs(n_out, d_sel, d_r, d_w, pb, j, d_pair, st), "glm_score_sparse_multi pair kernel");
+	}
+	PGH_HIP(hipMemcpyAsync(d_ny, h_ny.data(), 4ull * pb, hipMemcpyHostToDevice, st), "glm_score_sparse_multi count upload");
+	return PGH_OK;
+}
+
+int GlmScoreSparseMultiCall::RunChunk(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t nv, pgh_glm_row *out) {
+	const uint32_t l0 = v_begin + c0 - ds->v_begin;
+	PGH_HIP(pgh::LaunchGlmScoreSparseMulti(ds->Sparse(), l0, nv, d_pair, d_ny, pb, d_zr0, d_mz, kp, k, d_hg, ch.sums, ch.nmiss,
+	                                       ch.hgn, st),
+	        "glm_score_sparse_multi kernels");
+	PGH_TRY(SolveRows(pb, nv));
+	PGH_HIP(hipStreamSynchronize(st), "glm_score_sparse_multi sync");
+	Scatter(b0, pb, c0, nv, hrows, out);
+	return PGH_OK;
+}
+
+// The block loop over the chunk loop of either route.
+template <class Call>
+int GlmScoreBlocksRun(Call &c, pgh_glm_row *out) {
+	// sg.hz (and hz_raw): the covariates as they are
+	const GlmStaged sg = GlmStage(c.ds, c.subset, c.phenotypes, c.k, c.covariates, GlmCentre::kNone, true);
+	HostSourceFence fence(c.st); // sg, c's vectors and the caller's phenotypes feed asynchronous uploads
+	PGH_TRY(c.Prepare());
+	PGH_TRY(c.UploadCovariates(sg));
+	for (uint32_t b0 = 0; b0 < c.n_pheno; b0 += c.plan.pb_max) {
+		const uint32_t pb = std::min(c.plan.pb_max, c.n_pheno - b0);
+		PGH_TRY(c.StageBlock(b0, pb));
+		for (uint32_t c0 = 0; c0 < c.nv_all; c0 += c.plan.chunk) {
+			PGH_TRY(c.RunChunk(b0, pb, c0, std::min(c.plan.chunk, c.nv_all - c0), out));
 		}
 	}
 	return PGH_OK;
@@ -1514,27 +1674,18 @@ int GlmScoreMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v
                      const double *phenotypes, uint32_t k, const double *covariates, pgh_glm_row *out, char *errbuf,
                      const GlmScoreFollowUp &fu) {
 	PGH_ENTER(ds);
-	GlmScoreMultiCall c {ds, subset, v_begin, v_end - v_begin, n_pheno, k, phenotypes, covariates, fu, errbuf};
-	// sg.hz (and hz_raw): the covariates as they are
-	const GlmStaged sg = GlmStage(ds, subset, phenotypes, k, covariates, GlmCentre::kNone, true);
-	HostSourceFence fence(c.st); // sg, c's vectors and the caller's phenotypes feed asynchronous uploads
-	PGH_TRY(c.Prepare());
-	if (c.kp) {
-		PGH_HIP(hipMemcpyAsync(c.d_z0, sg.hz.data(), 8ull * sg.hz.size(), hipMemcpyHostToDevice, c.st),
-		        "glm_score_multi covariate upload");
-	}
-	if (sg.raw && c.kp) {
-		PGH_HIP(hipMemcpyAsync(c.d_zr0, sg.hz_raw.data(), 8ull * sg.hz_raw.size(), hipMemcpyHostToDevice, c.st),
-		        "glm_score_multi covariate upload (raw order)");
-	}
-	for (uint32_t b0 = 0; b0 < n_pheno; b0 += c.plan.pb_max) {
-		const uint32_t pb = std::min(c.plan.pb_max, n_pheno - b0);
-		PGH_TRY(c.StageBlock(b0, pb));
-		for (uint32_t c0 = 0; c0 < c.nv_all; c0 += c.plan.chunk) {
-			PGH_TRY(c.RunChunk(b0, pb, c0, std::min(c.plan.chunk, c.nv_all - c0), out));
-		}
-	}
-	return PGH_OK;
+	GlmScoreMultiCall c {{ds, subset, v_begin, v_end - v_begin, n_pheno, k, phenotypes, covariates, fu, errbuf,
+	                      "glm_score_multi", true}};
+	return GlmScoreBlocksRun(c, out);
+}
+
+int GlmScoreSparseMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                           uint32_t n_pheno, const double *phenotypes, uint32_t k, const double *covariates,
+                           pgh_glm_row *out, char *errbuf) {
+	PGH_ENTER(ds);
+	GlmScoreSparseMultiCall c {{ds, subset, v_begin, v_end - v_begin, n_pheno, k, phenotypes, covariates, {}, errbuf,
+	                            "glm_score_sparse_multi", false}};
+	return GlmScoreBlocksRun(c, out);
 }
 
 } // namespace
@@ -1565,6 +1716,19 @@ extern "C" int pgh_glm_score_sparse_firth(const pgh_dataset *ds, const pgh_subse
 
 namespace {
 
+// The phenotype checks of the block routes: every phenotype binary with a case and a control, the failing one named.
+int GlmCheckBinaryEach(const double *phenotypes, uint32_t n_pheno, uint32_t n_out, char *errbuf) {
+	for (uint32_t p = 0; p < n_pheno; p++) {
+		char why[PGH_ERRBUF_LEN];
+		why[0] = '\0';
+		if (GlmCheckBinary(phenotypes + static_cast<size_t>(p) * n_out, n_out, why) != PGH_OK) {
+			SetErr(errbuf, std::string(why) + " (phenotype " + std::to_string(p) + ")");
+			return PGH_ERR_ARG;
+		}
+	}
+	return PGH_OK;
+}
+
 // pgh_glm_score_multi, pgh_glm_score_multi_spa and pgh_glm_score_multi_firth after the latter two's own argument
 // checks.
 int GlmScoreMultiEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
@@ -1578,15 +1742,7 @@ int GlmScoreMultiEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_t
 		SetErr(errbuf, "hardcalls only: the dataset holds " + std::to_string(ds->dos_rows) + " dosage tracks");
 		return PGH_ERR_ARG;
 	}
-	const uint32_t n_out = subset ? subset->n_out : ds->sample_ct;
-	for (uint32_t p = 0; p < n_pheno; p++) {
-		char why[PGH_ERRBUF_LEN];
-		why[0] = '\0';
-		if (GlmCheckBinary(phenotypes + static_cast<size_t>(p) * n_out, n_out, why) != PGH_OK) {
-			SetErr(errbuf, std::string(why) + " (phenotype " + std::to_string(p) + ")");
-			return PGH_ERR_ARG;
-		}
-	}
+	PGH_TRY(GlmCheckBinaryEach(phenotypes, n_pheno, subset ? subset->n_out : ds->sample_ct, errbuf));
 	if (v_end == v_begin) {
 		return PGH_OK;
 	}
@@ -1594,6 +1750,20 @@ int GlmScoreMultiEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_t
 }
 
 } // namespace
+
+extern "C" int pgh_glm_score_sparse_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin,
+                                          uint32_t v_end, uint32_t n_pheno, const double *phenotypes, uint32_t n_covar,
+                                          const double *covariates, pgh_glm_row *out, char *errbuf) {
+	PGH_ONE_DEVICE(ds);
+	PGH_SPARSE_ROWS(ds);
+	PGH_TRY(GlmCheckCommon(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, PGH_GLM_LOGISTIC, out,
+	                       errbuf));
+	PGH_TRY(GlmCheckBinaryEach(phenotypes, n_pheno, subset ? subset->n_out : ds->sample_ct, errbuf));
+	if (v_end == v_begin) {
+		return PGH_OK;
+	}
+	return GlmScoreSparseMultiOne(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, errbuf);
+}
 
 extern "C" int pgh_glm_score_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                                    uint32_t n_pheno, const double *phenotypes, uint32_t n_covar,

@@ -198,6 +198,26 @@ hipError_t LaunchGlmScoreDense(const RowView &view, uint32_t v0, uint32_t nv, co
                                uint32_t k, const double *hg, double *sums, uint32_t *nmiss, double *hgn,
                                hipStream_t stream);
 
+// ---- pgh_glm_score_sparse_multi (glm_score_sparse_multi.hip): the score test from a sparse row's entries for a block
+// of phenotypes ----
+// At most kGlmScoreSparsePb phenotypes share a pair block and a walk of the entries.  No number depends on the block's
+// size, on a phenotype's place in it or on the chunk.
+constexpr uint32_t kGlmScoreSparsePb = 64;
+// The pair block of pb phenotypes: pair[s][j] = (r, w) of raw sample s and block phenotype j, sample_ct x pb double2.
+// Clear sets every pair to (NaN, 0): outside S_j or the subset.
+hipError_t LaunchGlmScoreSparsePairClear(uint32_t sample_ct, uint32_t pb, double *pair, hipStream_t stream);
+// Phenotype j's pairs of the subset's samples from LaunchGlmScoreNull's r_raw / w_raw.
+hipError_t LaunchGlmScoreSparsePairs(uint32_t n_out, const uint32_t *sel, const double *r_raw, const double *w_raw,
+                                     uint32_t pb, uint32_t j, double *pair, hipStream_t stream);
+// For the rows v_first + i (i < nv) of `sv`, sparse or held in the dense form, and the block's phenotypes p < pb:
+// sums[p][i][kp + 6] and hgn[p][i] in LaunchGlmScoreSparse's layouts, ready for LaunchGlmScoreSolve phenotype by
+// phenotype.  n_y[p] = |S_p|; z0: the UNCENTRED covariates in raw-sample order (sample_ct x kp); mz: pb x kp means over
+// S_p, the ones the null fits' covariates were centred on; hg: pb x (entries of hg).  nlist: nv words of scratch.
+hipError_t LaunchGlmScoreSparseMulti(const SparseView &sv, uint32_t v_first, uint32_t nv, const double *pair,
+                                     const uint32_t *n_y, uint32_t pb, const double *z0, const double *mz, uint32_t kp,
+                                     uint32_t k, const double *hg, double *sums, uint32_t *nlist, double *hgn,
+                                     hipStream_t stream);
+
 // ---- pgh_glm_score_sparse_spa (glm_score_spa.hip): saddlepoint p-values of the score test's rows ----
 // Bytes of the private stash one workgroup of the workgroup form needs for `sample_ct` samples (a pair of doubles each).
 inline uint64_t GlmScoreSpaStashPerGroup(uint32_t sample_ct) {

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """One SHA-256 per case over the result bytes of the GLM family (pgh_glm, pgh_glm_multi, pgh_glm_sparse,
-pgh_glm_score_sparse, pgh_glm_score_sparse_spa, pgh_glm_score_sparse_firth, pgh_glm_score_multi, pgh_glm_score_multi_spa,
+pgh_glm_score_sparse, pgh_glm_score_sparse_spa, pgh_glm_score_sparse_firth, pgh_glm_score_sparse_multi, pgh_glm_score_multi, pgh_glm_score_multi_spa,
 pgh_glm_score_multi_firth, pgh_burden_sparse), pgh_score_sparse, and the plink_ld pair sums and sparse counts that share their wave sums: the
 paths a change to the family's kernels, host staging, scratch layout or chunk loops can touch.  Two builds of the library
 compute the same rows bit for bit exactly when their outputs of this tool are equal line for line; PGENHIP_LIB names
@@ -288,3 +288,32 @@ for n in (4096, 4099, 8209):  # one full step of the walk, a second step of thre
         score_family(f"n={n} k=13 P=17", dense, Yl, Zl)
     for d in [dense] + [sp for _, sp in forms]:
         d.close()
+
+# ---- pgh_glm_score_sparse_multi, on the inputs of its tests.  These cases come last and draw from generators of their
+# own, so that the lines above are those of a build without the entry point ---------------------------------------------
+import test_glm_score_sparse_multi as SM  # noqa: E402
+
+n = 4099
+geno, kinds = SM._matrix(SM.M_R, n, n)
+path = os.path.join(out_dir, f"score_sparse_multi_{n}.pgen")
+W.write_pgen(path, geno, kinds)
+keep_m = np.random.default_rng(12).random(n) < 0.5
+for max_minor, form in ((n, "entries only"), (1, "with dense-form rows")):
+    sp = L.Dataset.open(path, sparse=True, max_minor=max_minor)
+    for k in (0, 3):
+        Zk, Yk, _ = SM.parity_inputs(n, k)
+        emit(f"glm_score_sparse_multi {form}, k={k} P=6", sp.glm_score_sparse_multi(Yk, Zk if k else None))
+    Z3, Y3, _ = SM.parity_inputs(n, 3)
+    emit(f"glm_score_sparse_multi {form}, k=3 P=65",
+         sp.glm_score_sparse_multi(np.stack([Y3[i % len(Y3)] for i in range(65)]), Z3))
+    sub = sp.subset(keep_m)
+    emit(f"glm_score_sparse_multi {form}, k=3 subset",
+         sp.glm_score_sparse_multi(np.ascontiguousarray(Y3[:, keep_m]), np.ascontiguousarray(Z3[:, keep_m]), subset=sub))
+    sub.close()
+    if max_minor == n:
+        for k in (4, 20):
+            rng_k = np.random.default_rng(3000 + k)
+            Zk = SM._covariates(rng_k, k, n)
+            Yk = np.stack([SM.O.pheno(rng_k, n, Zk), SM.O.pheno(rng_k, n, Zk, case_rate=0.35, missing=0.1)])
+            emit(f"glm_score_sparse_multi {form}, k={k} P=2", sp.glm_score_sparse_multi(Yk, Zk))
+    sp.close()
