@@ -682,7 +682,7 @@ int pgh_glm_score_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32
  * with the phenotypes and variants in flight; the result does not depend on it.
  * Saddlepoint p-values over this route: pgh_glm_score_multi_spa.  Approximate Firth estimates over this route:
  * pgh_glm_score_multi_firth (from carrier lists: pgh_glm_score_sparse_firth).  Many phenotypes over a sparse-resident
- * dataset: pgh_glm_score_sparse_multi.  Not offered: a Firth-penalised null fit, Firth and saddlepoint in one call, dosage
+ * dataset: pgh_glm_score_sparse_multi, with saddlepoint p-values pgh_glm_score_sparse_multi_spa.  Not offered: a Firth-penalised null fit, Firth and saddlepoint in one call, dosage
  * tracks, shard groups, a table function. */
 int pgh_glm_score_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                         uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
@@ -715,9 +715,9 @@ int pgh_glm_score_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_
  * PGH_GLM_SCORE_SCRATCH_BYTES (environment, read at every call, default 6 GiB) bounds the device scratch that grows
  * with the phenotypes and variants in flight (16 bytes per sample and block phenotype, then the chunk's sums); the
  * result does not depend on it.
- * Not offered: saddlepoint p-values and approximate Firth estimates over this route (one phenotype at a time:
- * pgh_glm_score_sparse_spa, pgh_glm_score_sparse_firth), quantitative phenotypes, dosage tracks, shard groups, a table
- * function. */
+ * Saddlepoint p-values over this route: pgh_glm_score_sparse_multi_spa.  Not offered: approximate Firth estimates
+ * over this route (one phenotype at a time: pgh_glm_score_sparse_firth), quantitative phenotypes, dosage tracks, shard
+ * groups, a table function. */
 int pgh_glm_score_sparse_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                                uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
                                pgh_glm_row *out, char *errbuf);
@@ -758,7 +758,8 @@ int pgh_glm_score_sparse_multi(const pgh_dataset *ds, const pgh_subset *subset, 
  * rounding only for the rows whose E is the same set, and within the quality of the approximation otherwise.  A row's
  * (out, p_spa, spa_state) is a function of its variant's entries, the phenotype, the covariates, the subset and
  * spa_cutoff only: not of v_begin, the chunk, the window the dataset was opened with or the rows around it, and the
- * same call returns the same bytes every time. */
+ * same call returns the same bytes every time.  Many phenotypes in one walk of the entries, with this p-value:
+ * pgh_glm_score_sparse_multi_spa. */
 int pgh_glm_score_sparse_spa(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                              const double *phenotype, uint32_t n_covar, const double *covariates, double spa_cutoff,
                              pgh_glm_row *out, double *p_spa, uint8_t *spa_state, char *errbuf);
@@ -794,6 +795,40 @@ int pgh_glm_score_sparse_spa(const pgh_dataset *ds, const pgh_subset *subset, ui
 int pgh_glm_score_multi_spa(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                             uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
                             double spa_cutoff, pgh_glm_row *out, double *p_spa, uint8_t *spa_state, char *errbuf);
+/* pgh_glm_score_sparse_multi with pgh_glm_score_sparse_spa's SADDLEPOINT p-value beside the normal one, for every
+ * (variant, phenotype) row of the sparse many-phenotype route.  Arguments, argument checks, error texts and refusals
+ * are pgh_glm_score_sparse_multi's: a dataset that is not sparse-resident, a shard group, n_pheno == 0, "phenotype must
+ * be 0 or 1" and "no cases or no controls", each followed by the phenotype's index.  In addition spa_cutoff must be at
+ * least 0.1 (+infinity: never apply it; NaN or a smaller value is PGH_ERR_ARG, "spa_cutoff must be at least 0.1"), and
+ * p_spa and spa_state must not be NULL ("null p_spa or spa_state"); they have out's layout, element
+ * (v - v_begin) * n_pheno + p.  On any error all three outputs are untouched.  v_begin == v_end is PGH_OK.
+ *
+ * out is pgh_glm_score_sparse_multi's result for the same arguments bit for bit; its p stays the normal p-value.
+ * spa_state and p_spa mean what they mean for pgh_glm_score_sparse_spa: 0 = not applied (the row is not fitted: p_spa
+ * NaN; or |stat| <= spa_cutoff: p_spa = out.p bit for bit), 1 = applied (p_spa is the saddlepoint p), 2 = attempted and
+ * failed (p_spa = out.p bit for bit).
+ *
+ * Definition: pgh_glm_score_sparse_spa's, word for word, per (variant, phenotype) row.  E = the samples of that
+ * phenotype's N that the row holds as called entries; a row held in the dense form counts as a base-0 row, and a
+ * missing-majority row (b = 3) has E = N and V_rest = 0 by rule.  gt = d - Zt t with Zt centred on that phenotype's own
+ * pattern means; mu = r > 0 ? 1 - r : -r; K, K', K'' with one exp(-|gt s|) per entry; the safeguarded Newton iteration
+ * for q+ and q- = +-|U| from |q| / V with the 1/sqrt(V) step cap that doubles; the three stopping rules and the cap of
+ * 64 evaluations; omega, nu and the two tails; the state-2 conditions.
+ *
+ * Against pgh_glm_score_sparse_spa for the same phenotype alone over the same dataset, E is the same set: the states
+ * agree and p_spa agrees to rounding, not bit for bit (t, U and V come from sums taken in another order).  Against
+ * pgh_glm_score_multi_spa over the same file, agreement holds where the sparse base code equals the dense b, as that
+ * contract says.
+ *
+ * A row's (out, p_spa, spa_state) is a function of its variant's entries, its own phenotype, the covariates, the subset
+ * and spa_cutoff only: not of the other phenotypes of the call or its place among them, of n_pheno, the phenotype
+ * block, the rows that share a wave, a workgroup or a work list with it, v_begin, the variant chunk, the window the
+ * dataset was opened with, PGH_GLM_SCORE_SCRATCH_BYTES (which here also bounds the saddlepoint kernel's stashes and
+ * work lists) or the grid, and the same call returns the same bytes every time.
+ * Not offered: approximate Firth estimates over this route (one phenotype at a time: pgh_glm_score_sparse_firth). */
+int pgh_glm_score_sparse_multi_spa(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                                   uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
+                                   double spa_cutoff, pgh_glm_row *out, double *p_spa, uint8_t *spa_state, char *errbuf);
 /* One (variant, phenotype) result of pgh_glm_score_multi_firth. */
 typedef struct pgh_glm_firth_row {
 	double beta, se, p;

@@ -1153,7 +1153,7 @@ int GlmCheckBinary(const double *phenotype, uint32_t n_out, char *errbuf) {
 	return PGH_OK;
 }
 
-// pgh_glm_score_sparse_spa's and pgh_glm_score_multi_spa's own arguments.
+// pgh_glm_score_sparse_spa's, pgh_glm_score_multi_spa's and pgh_glm_score_sparse_multi_spa's own arguments.
 int GlmCheckSpa(double spa_cutoff, const double *p_spa, const uint8_t *spa_state, char *errbuf) {
 	if (!(spa_cutoff >= 0.1)) { // (NaN too)
 		SetErr(errbuf, "spa_cutoff must be at least 0.1");
@@ -1306,32 +1306,56 @@ GlmScoreMultiPlan GlmScoreMultiPlanFor(uint32_t n_raw, uint32_t n_pheno, uint32_
 	return plan;
 }
 
-// pgh_glm_score_sparse_multi: how a call splits the same budget.  The pair block takes 16 n_raw bytes per phenotype; it
-// gets the most phenotypes, kGlmScoreSparsePb at most, that leave one chunk variant's arrays within the budget (one
-// phenotype whatever the budget), and what it leaves bounds the chunk at GlmScoreMultiChunkArrays' bytes per variant.
-// The rounding and the block's own small arrays are not charged, as in GlmScoreMultiPlanFor.
+// pgh_glm_score_sparse_multi_spa's work lists of a chunk (glm_score_sparse_multi_spa.hip): the applied rows of the wave
+// form and of the workgroup form, and the list kernels' counts per tile.  AddTo is their one declaration, as above.
+struct GlmScoreSparseMultiSpaLists {
+	uint32_t *wave = nullptr, *group = nullptr, *tile_ct = nullptr;
+	void AddTo(ScratchLayout &lay, uint64_t pb_max, uint64_t c, bool present) {
+		lay.Add(&wave, pb_max * c, present);
+		lay.Add(&group, pb_max * c, present);
+		lay.Add(&tile_ct, pgh::GlmScoreSparseMultiSpaTileWords(pb_max * c), present);
+	}
+};
+
+// pgh_glm_score_sparse_multi*: how a call splits the same budget.  The pair block takes 16 n_raw bytes per phenotype; it
+// gets the most phenotypes, kGlmScoreSparsePb at most, that leave one chunk variant's arrays (and, with a follow-up,
+// one stash) within the budget (one phenotype whatever the budget).  kSpa: the stashes of the workgroup form take up to
+// a quarter of what the block leaves (StashGroupsFor: at least one stash, at most four workgroups per compute unit); a
+// quarter and not GlmScoreMultiPlanFor's three, because only the rows of more than kGlmSparseLong entries and the
+// dense-form rows use one, and the chunk, which every row needs, should not shrink for them.  What is left bounds the
+// chunk at the bytes per variant of GlmScoreMultiChunkArrays and, with kSpa, of the work lists.  The rounding and the
+// block's own small arrays are not charged, as in GlmScoreMultiPlanFor.
 GlmScoreMultiPlan GlmScoreSparseMultiPlanFor(uint32_t n_raw, uint32_t n_pheno, uint32_t k, uint32_t nv_all,
-                                             uint64_t budget) {
+                                             uint64_t budget, int cus, GlmScoreFollowUp::Kind kind) {
 	const uint32_t kp = pgh::GlmPadCovar(k);
+	const bool spa = kind == GlmScoreFollowUp::kSpa;
+	const uint64_t per_group = spa ? pgh::GlmScoreSpaStashPerGroup(n_raw) : 0;
 	const auto block_bytes = [&](uint32_t pb) { return 16ull * n_raw * pb; };
 	const auto variant_bytes = [&](uint32_t pb) {
 		GlmScoreMultiChunkArrays unit;
+		GlmScoreSparseMultiSpaLists lists;
 		ScratchLayout one_variant;
-		unit.AddTo(one_variant, pb, 1, kp, k, GlmScoreFollowUp::kNone);
+		unit.AddTo(one_variant, pb, 1, kp, k, kind);
+		lists.AddTo(one_variant, pb, 1, spa);
 		return one_variant.payload;
 	};
 	GlmScoreMultiPlan plan;
 	plan.pb_max = std::min(pgh::kGlmScoreSparsePb, n_pheno);
-	while (plan.pb_max > 1 && block_bytes(plan.pb_max) + variant_bytes(plan.pb_max) > budget) {
+	while (plan.pb_max > 1 && block_bytes(plan.pb_max) + variant_bytes(plan.pb_max) + per_group > budget) {
 		plan.pb_max--;
 	}
-	const uint64_t left = budget > block_bytes(plan.pb_max) ? budget - block_bytes(plan.pb_max) : 0;
+	uint64_t left = budget > block_bytes(plan.pb_max) ? budget - block_bytes(plan.pb_max) : 0;
 	const uint32_t nv_most = std::min(kGlmScoreMultiChunk, nv_all);
+	if (spa) {
+		plan.n_groups = StashGroupsFor(static_cast<uint64_t>(nv_most) * plan.pb_max, 4, per_group, left / 4, cus);
+		plan.stash_bytes = per_group * plan.n_groups;
+		left = left > plan.stash_bytes ? left - plan.stash_bytes : 0;
+	}
 	plan.chunk = static_cast<uint32_t>(std::min<uint64_t>(nv_most, std::max<uint64_t>(1, left / variant_bytes(plan.pb_max))));
 	return plan;
 }
 
-// What one call of pgh_glm_score_multi* (a dense-resident dataset) and of pgh_glm_score_sparse_multi (a sparse-resident
+// What one call of pgh_glm_score_multi* (a dense-resident dataset) and of pgh_glm_score_sparse_multi* (a sparse-resident
 // one) share after the argument checks: the pattern order, the staging of a pattern group, the null fit of a block
 // phenotype, the solve of a chunk's rows phenotype by phenotype and their scatter into the caller's rows.
 // The null models are fitted phenotype by phenotype by GlmScoreNullFit, as GlmScoreSparseOne fits its one: on the
@@ -1605,11 +1629,17 @@ int GlmScoreMultiCall::RunChunk(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t 
 	return PGH_OK;
 }
 
-// One call of pgh_glm_score_sparse_multi on one sparse-resident dataset.  Each fit's r and w go into the phenotype's
+// One call of pgh_glm_score_sparse_multi* on one sparse-resident dataset.  Each fit's r and w go into the phenotype's
 // column of the pair block (glm_score_sparse_multi.hip); the entry kernel centres the raw-order covariates per lane on
-// the block's means d_mz.
+// the block's means d_mz.  fu.kind == kSpa: after a chunk's rows, the applied ones are listed and
+// GlmScoreSparseMultiSpaKernel (glm_score_sparse_multi_spa.hip) replaces their p_spa.
 struct GlmScoreSparseMultiCall : GlmScoreBlockCall {
 	double *d_pair;
+	uint8_t *d_stash;
+	GlmScoreSparseMultiSpaLists lists;
+	uint32_t wave_groups = 0; // workgroups of the wave form's grid
+	std::vector<double> hp_spa;
+	std::vector<uint8_t> hstate;
 
 	int Prepare();
 	int StageBlock(uint32_t b0, uint32_t pb);
@@ -1618,14 +1648,27 @@ struct GlmScoreSparseMultiCall : GlmScoreBlockCall {
 
 int GlmScoreSparseMultiCall::Prepare() {
 	PatternOrder();
-	plan = GlmScoreSparseMultiPlanFor(n_raw, n_pheno, k, nv_all, EnvBytes(kGlmScoreScratchEnv, kGlmScoreScratchBytes));
+	const bool spa = fu.kind == GlmScoreFollowUp::kSpa;
+	int cus = 0;
+	if (spa) {
+		PGH_TRY(DeviceCus(&cus, "glm_score_sparse_multi stash", errbuf));
+		// the wave form keeps two workgroups on a compute unit (their stashes are LDS): a few rounds of them, so that the
+		// rows' unequal lengths even out
+		wave_groups = 8u * static_cast<uint32_t>(std::max(cus, 1));
+	}
+	plan = GlmScoreSparseMultiPlanFor(n_raw, n_pheno, k, nv_all, EnvBytes(kGlmScoreScratchEnv, kGlmScoreScratchBytes), cus,
+	                                  fu.kind);
 	ScratchLayout lay;
 	AddShared(lay);
 	lay.Add(&d_pair, 2ull * n_raw * plan.pb_max);
-	ch.AddTo(lay, plan.pb_max, plan.chunk, kp, k, GlmScoreFollowUp::kNone);
+	ch.AddTo(lay, plan.pb_max, plan.chunk, kp, k, fu.kind);
+	lists.AddTo(lay, plan.pb_max, plan.chunk, spa);
+	lay.Add(&d_stash, plan.stash_bytes, spa);
 	void *scratch = nullptr;
 	PGH_HIP(PghThreadScratch(lay.total, st, &scratch), "glm_score_sparse_multi scratch");
 	lay.Bind(scratch);
+	hp_spa.resize(spa ? hrows.size() : 0);
+	hstate.resize(spa ? hrows.size() : 0);
 	return PGH_OK;
 }
 
@@ -1647,8 +1690,23 @@ int GlmScoreSparseMultiCall::RunChunk(uint32_t b0, uint32_t pb, uint32_t c0, uin
 	                                       ch.hgn, st),
 	        "glm_score_sparse_multi kernels");
 	PGH_TRY(SolveRows(pb, nv));
+	if (fu.kind == GlmScoreFollowUp::kSpa) {
+		const size_t n_rows = static_cast<size_t>(nv) * pb;
+		PGH_HIP(pgh::LaunchGlmScoreSparseMultiSpa(ds->Sparse(), l0, nv, d_pair, pb, d_zr0, d_mz, kp, ch.rows, ch.so.t, fu.cutoff,
+		                                          lists.wave, lists.group, lists.tile_ct, wave_groups, plan.n_groups, d_stash,
+		                                          ch.so.p_spa, ch.so.state, st),
+		        "glm_score_sparse_multi_spa kernels");
+		PGH_HIP(hipMemcpyAsync(hp_spa.data(), ch.so.p_spa, 8ull * n_rows, hipMemcpyDeviceToHost, st),
+		        "glm_score_sparse_multi_spa p copy");
+		PGH_HIP(hipMemcpyAsync(hstate.data(), ch.so.state, n_rows, hipMemcpyDeviceToHost, st),
+		        "glm_score_sparse_multi_spa state copy");
+	}
 	PGH_HIP(hipStreamSynchronize(st), "glm_score_sparse_multi sync");
 	Scatter(b0, pb, c0, nv, hrows, out);
+	if (fu.kind == GlmScoreFollowUp::kSpa) {
+		Scatter(b0, pb, c0, nv, hp_spa, fu.p_spa);
+		Scatter(b0, pb, c0, nv, hstate, fu.state);
+	}
 	return PGH_OK;
 }
 
@@ -1681,9 +1739,9 @@ int GlmScoreMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v
 
 int GlmScoreSparseMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                            uint32_t n_pheno, const double *phenotypes, uint32_t k, const double *covariates,
-                           pgh_glm_row *out, char *errbuf) {
+                           pgh_glm_row *out, char *errbuf, const GlmScoreFollowUp &fu) {
 	PGH_ENTER(ds);
-	GlmScoreSparseMultiCall c {{ds, subset, v_begin, v_end - v_begin, n_pheno, k, phenotypes, covariates, {}, errbuf,
+	GlmScoreSparseMultiCall c {{ds, subset, v_begin, v_end - v_begin, n_pheno, k, phenotypes, covariates, fu, errbuf,
 	                            "glm_score_sparse_multi", false}};
 	return GlmScoreBlocksRun(c, out);
 }
@@ -1751,9 +1809,12 @@ int GlmScoreMultiEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_t
 
 } // namespace
 
-extern "C" int pgh_glm_score_sparse_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin,
-                                          uint32_t v_end, uint32_t n_pheno, const double *phenotypes, uint32_t n_covar,
-                                          const double *covariates, pgh_glm_row *out, char *errbuf) {
+namespace {
+
+// pgh_glm_score_sparse_multi and pgh_glm_score_sparse_multi_spa after the latter's own argument checks.
+int GlmScoreSparseMultiEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                             uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
+                             pgh_glm_row *out, const GlmScoreFollowUp &fu, char *errbuf) {
 	PGH_ONE_DEVICE(ds);
 	PGH_SPARSE_ROWS(ds);
 	PGH_TRY(GlmCheckCommon(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, PGH_GLM_LOGISTIC, out,
@@ -1762,7 +1823,24 @@ extern "C" int pgh_glm_score_sparse_multi(const pgh_dataset *ds, const pgh_subse
 	if (v_end == v_begin) {
 		return PGH_OK;
 	}
-	return GlmScoreSparseMultiOne(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, errbuf);
+	return GlmScoreSparseMultiOne(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, errbuf, fu);
+}
+
+} // namespace
+
+extern "C" int pgh_glm_score_sparse_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin,
+                                          uint32_t v_end, uint32_t n_pheno, const double *phenotypes, uint32_t n_covar,
+                                          const double *covariates, pgh_glm_row *out, char *errbuf) {
+	return GlmScoreSparseMultiEntry(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, {}, errbuf);
+}
+
+extern "C" int pgh_glm_score_sparse_multi_spa(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin,
+                                              uint32_t v_end, uint32_t n_pheno, const double *phenotypes,
+                                              uint32_t n_covar, const double *covariates, double spa_cutoff,
+                                              pgh_glm_row *out, double *p_spa, uint8_t *spa_state, char *errbuf) {
+	PGH_TRY(GlmCheckSpa(spa_cutoff, p_spa, spa_state, errbuf));
+	const GlmScoreFollowUp fu = {GlmScoreFollowUp::kSpa, spa_cutoff, p_spa, spa_state, nullptr};
+	return GlmScoreSparseMultiEntry(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, fu, errbuf);
 }
 
 extern "C" int pgh_glm_score_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,

@@ -232,6 +232,23 @@ hipError_t LaunchGlmScoreSpa(const SparseView &sv, uint32_t v_first, uint32_t nv
                              double cutoff, uint32_t n_groups, void *stash, double *p_spa, uint8_t *state,
                              hipStream_t stream);
 
+// ---- pgh_glm_score_sparse_multi_spa (glm_score_sparse_multi_spa.hip): saddlepoint p-values of the pair block's rows ----
+// Words of tile_ct for a chunk of n_rows = nv * pb (variant, phenotype) rows.
+uint64_t GlmScoreSparseMultiSpaTileWords(uint64_t n_rows);
+// For the rows (phenotype p < pb, chunk variant i < nv) at p * nv + i that are fitted with |stat| > cutoff: p_spa and
+// state = 1, or state = 2 with p_spa left as it is; the other rows are not touched.  sv, v_first, nv, pair, pb, z0, mz
+// and kp are LaunchGlmScoreSparseMulti's; rows and t ([pb][nv][kp + 3]) are LaunchGlmScoreSolve's, phenotype by
+// phenotype.  list_wave, list_group: nv * pb words each and tile_ct: GlmScoreSparseMultiSpaTileWords words, whatever
+// they hold (the applied rows of either form, listed first).  n_wave_groups: the workgroups of the wave form's grid;
+// stash: n_groups x GlmScoreSpaStashPerGroup bytes, whatever they hold.  Nothing in the output depends on
+// n_wave_groups or n_groups (both >= 1).
+hipError_t LaunchGlmScoreSparseMultiSpa(const SparseView &sv, uint32_t v_first, uint32_t nv, const double *pair,
+                                        uint32_t pb, const double *z0, const double *mz, uint32_t kp,
+                                        const pgh_glm_row *rows, const double *t, double cutoff, uint32_t *list_wave,
+                                        uint32_t *list_group, uint32_t *tile_ct, uint32_t n_wave_groups,
+                                        uint32_t n_groups, void *stash, double *p_spa, uint8_t *state,
+                                        hipStream_t stream);
+
 // ---- pgh_glm_score_sparse_firth (glm_score_sparse_firth.hip): approximate Firth estimates of the score test's rows ----
 // For every row v_first + i (i < nv) of `sv`: firth[i], the contract's triple and state (the score row's beta, se and p
 // with state 0 where the row is not fitted or |stat| <= cutoff).  r: LaunchGlmScoreSparse's; rows: LaunchGlmScoreSolve's.

@@ -1,6 +1,8 @@
-// glm_spa.hpp -- the saddlepoint arithmetic that GlmScoreSpaKernel (glm_score_spa.hip) and GlmScoreDenseSpaKernel
-// (glm_score_dense_spa.hip) share: pi, K, the safeguarded Newton step, a tail, and phase B, the iteration of one team
-// over its stash of (g, mu) pairs (the contract is pgh_glm_score_sparse_spa's in include/pgenhip.h).
+// glm_spa.hpp -- the saddlepoint arithmetic that GlmScoreSpaKernel (glm_score_spa.hip), GlmScoreDenseSpaKernel
+// (glm_score_dense_spa.hip) and GlmScoreSparseMultiSpaKernel (glm_score_sparse_multi_spa.hip) share: pi, K, the
+// safeguarded Newton step, a tail, and phase B, the iteration of one team over its stash of (g, mu) pairs (the contract
+// is pgh_glm_score_sparse_spa's in include/pgenhip.h); and SpaSparseRow, the walk of one sparse-resident row into the
+// stash that the first and the last instantiate with how they read a sample.
 #pragma once
 
 #include "glm_team.hpp"
@@ -135,6 +137,113 @@ __device__ __forceinline__ bool SpaSolveStash(Stash st, uint32_t count, bool ok,
 	}
 	*p_out = p;
 	return ok;
+}
+
+// One sparse-resident row by one team: phase A, the walk of the row's entries into the team's stash, and phase B,
+// for GlmScoreSpaKernel (glm_score_spa.hip) and GlmScoreSparseMultiSpaKernel (glm_score_sparse_multi_spa.hip).
+// i: the chunk variant; at: where the row's values stand in out, tv (rows of KP + 3: t, U, V), p_spa and state.
+// st: the team's stash of at least `cap` pairs (LDS or global).  A Src is how a kernel reads a sample:
+//   Sample, Load(s, &v): what the staged r of sample s needs (false: s is outside S);  R(v), W(s, v);
+//   Z(s, j): covariate j of sample s, centred.
+// The team returns from a row of the other form (a wave takes the sparse rows of at most kGlmSparseLong entries, the
+// workgroup the longer ones and the dense-form rows) and from one that is not fitted with |stat| > cutoff.
+template <int KP, int TEAM, class Src, class Stash>
+__device__ __forceinline__ void SpaSparseRow(const SparseRows &rows, uint32_t i, uint32_t at, const Src &src,
+                                             const pgh_glm_row *__restrict__ out, const double *__restrict__ tv,
+                                             double cutoff, Stash st, uint32_t cap, double *__restrict__ p_spa,
+                                             uint8_t *__restrict__ state) {
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const int tid = TEAM == kTeamBlock ? static_cast<int>(threadIdx.x) : lane;
+	const uint32_t r = rows.v_first + i;
+	const int32_t ro = rows.row_of[r];
+	const bool dense = ro >= 0;
+	uint64_t e0 = 0, e1 = rows.sample_ct;
+	if (dense) {
+		if (TEAM != kTeamBlock) {
+			return;
+		}
+	} else {
+		e0 = rows.off[r];
+		e1 = rows.off[r + 1];
+		if ((e1 - e0 > kGlmSparseLong) != (TEAM == kTeamBlock)) {
+			return;
+		}
+	}
+	if (out[at].errcode != PGH_GLM_OK || !(fabs(out[at].stat) > cutoff)) {
+		return;
+	}
+	const uint8_t *prow = dense ? rows.pool + static_cast<uint64_t>(ro) * rows.pitch : nullptr;
+	const bool base3 = ro == -4;
+	const int bx = (dense || base3) ? 0 : -1 - ro;
+	double t[KP + 1];
+#pragma unroll
+	for (int j = 0; j <= KP; j++) {
+		t[j] = tv[static_cast<uint64_t>(at) * (KP + 3) + j];
+		// the row is the same for the whole workgroup, which would make t, and below U, V and the state of the
+		// iteration, scalar registers, more than there are: keep them in vector registers
+		asm volatile("" : "+v"(t[j]));
+	}
+	double q = fabs(tv[static_cast<uint64_t>(at) * (KP + 3) + KP + 1]), v = tv[static_cast<uint64_t>(at) * (KP + 3) + KP + 2];
+	asm volatile("" : "+v"(q), "+v"(v));
+
+	// phase A
+	uint32_t count = 0;
+	double sums[4] = {0.0, 0.0, 0.0, 0.0};
+	long long none[4] = {0, 0, 0, 0};
+	for (uint64_t p0 = e0; p0 < e1; p0 += TEAM) {
+		const uint64_t p = p0 + tid;
+		bool take = false;
+		double g = 0.0, mu = 0.0;
+		if (p < e1) {
+			uint32_t code, s;
+			bool entry;
+			if (dense) {
+				s = static_cast<uint32_t>(p);
+				code = (prow[s >> 2] >> (2 * (s & 3u))) & 3u;
+				entry = code != 0u;
+			} else {
+				const uint32_t x = rows.entries[p];
+				s = x >> 2;
+				code = x & 3u;
+				entry = s < rows.sample_ct;
+			}
+			if (entry && code != 3u) {
+				typename Src::Sample sv;
+				if (src.Load(s, &sv)) {
+					const double ri = src.R(sv);
+					take = true;
+					g = static_cast<double>(static_cast<int>(code) - bx) - t[0];
+#pragma unroll
+					for (int j = 0; j < KP; j++) {
+						g = fma(-src.Z(s, j), t[1 + j], g);
+					}
+					mu = ri > 0.0 ? 1.0 - ri : -ri;
+					sums[0] = fma(src.W(s, sv) * g, g, sums[0]);
+				}
+			}
+		}
+		uint32_t total;
+		const uint32_t pos = count + TeamRank<TEAM>(take, lane, wave, &total);
+		if (take && pos < cap) {
+			st[pos] = make_double2(g, mu);
+		}
+		count += total;
+		TeamSync<TEAM>(); // TeamRank's counts are rewritten by the next step
+	}
+	TeamSums<TEAM>(sums, none, lane, wave);
+	TeamSync<TEAM>(); // the pairs before their readers, and TeamSums' LDS before it is written again
+	bool ok = count <= cap;
+	const double v_rest = base3 ? 0.0 : fmax(v - sums[0], 0.0);
+
+	// phase B
+	double p;
+	ok = SpaSolveStash<TEAM>(st, count, ok, q, v, v_rest, tid, lane, wave, &p);
+	if (tid == 0) {
+		if (ok) {
+			p_spa[at] = p;
+		}
+		state[at] = ok ? 1 : 2;
+	}
 }
 
 } // namespace
