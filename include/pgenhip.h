@@ -682,8 +682,9 @@ int pgh_glm_score_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32
  * with the phenotypes and variants in flight; the result does not depend on it.
  * Saddlepoint p-values over this route: pgh_glm_score_multi_spa.  Approximate Firth estimates over this route:
  * pgh_glm_score_multi_firth (from carrier lists: pgh_glm_score_sparse_firth).  Many phenotypes over a sparse-resident
- * dataset: pgh_glm_score_sparse_multi, with saddlepoint p-values pgh_glm_score_sparse_multi_spa.  Not offered: a Firth-penalised null fit, Firth and saddlepoint in one call, dosage
- * tracks, shard groups, a table function. */
+ * dataset: pgh_glm_score_sparse_multi, with saddlepoint p-values pgh_glm_score_sparse_multi_spa, with approximate Firth
+ * estimates pgh_glm_score_sparse_multi_firth.  Not offered: a Firth-penalised null fit, Firth and saddlepoint in one
+ * call, dosage tracks, shard groups, a table function. */
 int pgh_glm_score_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                         uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
                         pgh_glm_row *out, char *errbuf);
@@ -715,9 +716,9 @@ int pgh_glm_score_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_
  * PGH_GLM_SCORE_SCRATCH_BYTES (environment, read at every call, default 6 GiB) bounds the device scratch that grows
  * with the phenotypes and variants in flight (16 bytes per sample and block phenotype, then the chunk's sums); the
  * result does not depend on it.
- * Saddlepoint p-values over this route: pgh_glm_score_sparse_multi_spa.  Not offered: approximate Firth estimates
- * over this route (one phenotype at a time: pgh_glm_score_sparse_firth), quantitative phenotypes, dosage tracks, shard
- * groups, a table function. */
+ * Saddlepoint p-values over this route: pgh_glm_score_sparse_multi_spa.  Approximate Firth estimates over this route:
+ * pgh_glm_score_sparse_multi_firth.  Not offered: quantitative phenotypes, dosage tracks, shard groups, a table
+ * function. */
 int pgh_glm_score_sparse_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                                uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
                                pgh_glm_row *out, char *errbuf);
@@ -825,7 +826,8 @@ int pgh_glm_score_multi_spa(const pgh_dataset *ds, const pgh_subset *subset, uin
  * block, the rows that share a wave, a workgroup or a work list with it, v_begin, the variant chunk, the window the
  * dataset was opened with, PGH_GLM_SCORE_SCRATCH_BYTES (which here also bounds the saddlepoint kernel's stashes and
  * work lists) or the grid, and the same call returns the same bytes every time.
- * Not offered: approximate Firth estimates over this route (one phenotype at a time: pgh_glm_score_sparse_firth). */
+ * Approximate Firth estimates over this route: pgh_glm_score_sparse_multi_firth.  Not offered: Firth and saddlepoint in
+ * one call. */
 int pgh_glm_score_sparse_multi_spa(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                                    uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
                                    double spa_cutoff, pgh_glm_row *out, double *p_spa, uint8_t *spa_state, char *errbuf);
@@ -945,12 +947,47 @@ int pgh_glm_score_multi_firth(const pgh_dataset *ds, const pgh_subset *subset, u
  *
  * A row's (out, firth) is a function of its variant's entries, the phenotype, the covariates, the subset and
  * firth_cutoff only: not of v_begin, the chunk, the window the dataset was opened with, the grid or the rows around
- * it, and the same call returns the same bytes every time.  Not offered: a Firth-penalised null fit, Firth and
- * saddlepoint in one call, the dense route's coding for base-1 and base-2 rows, dosage tracks, shard groups, a table
- * function. */
+ * it, and the same call returns the same bytes every time.  Many phenotypes in one walk of the entries, with this
+ * estimate: pgh_glm_score_sparse_multi_firth.  Not offered: a Firth-penalised null fit, Firth and saddlepoint in one
+ * call, the dense route's coding for base-1 and base-2 rows, dosage tracks, shard groups, a table function. */
 int pgh_glm_score_sparse_firth(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                                const double *phenotype, uint32_t n_covar, const double *covariates,
                                double firth_cutoff, pgh_glm_row *out, pgh_glm_firth_row *firth, char *errbuf);
+/* pgh_glm_score_sparse_multi with pgh_glm_score_sparse_firth's APPROXIMATE FIRTH estimate beside the one-step score
+ * estimate, for every (variant, phenotype) row of the sparse many-phenotype route beyond a cutoff.  Arguments, argument
+ * checks, error texts and refusals are pgh_glm_score_sparse_multi's: a dataset that is not sparse-resident, a shard
+ * group, n_pheno == 0, "phenotype must be 0 or 1" and "no cases or no controls", each followed by the phenotype's index.
+ * In addition firth_cutoff must be at least 0.1 (+infinity: never apply it; NaN or a smaller value is PGH_ERR_ARG,
+ * "firth_cutoff must be at least 0.1"), and firth must not be NULL ("null firth"); it has out's layout, element
+ * (v - v_begin) * n_pheno + p.  On any error both outputs are untouched.  v_begin == v_end is PGH_OK.
+ *
+ * out is pgh_glm_score_sparse_multi's result for the same arguments bit for bit.  Its firth byte stays 0: that byte
+ * records pgh_glm's full Firth fallback, which this is not.
+ *
+ * firth[...].state and values mean what they mean for pgh_glm_score_multi_firth: state 0 with NaN for a row that is not
+ * fitted, state 0 with out's beta, se, p bit for bit where |stat| <= cutoff, state 1 with the Firth values, state 2 with
+ * out's beta, se, p bit for bit; pad is zero.
+ *
+ * Definition: pgh_glm_score_sparse_firth's, word for word, per (variant, phenotype) row.  b is the row's base code, 0
+ * for a missing-majority row and for a row held in the dense form; d = x - b; E is that phenotype's used called entries
+ * with d != 0; mu is recovered from that phenotype's r; G = sum_E d r.  The iteration, the stopping rules, the cap of 64
+ * evaluations, the state-2 conditions and the result are unchanged.  What follows from d carries over: base-1 and
+ * base-2 rows use another reference level than the dense route.
+ *
+ * Against pgh_glm_score_sparse_firth for the same phenotype alone over the same dataset, E is the same set: the states
+ * agree and the values agree to rounding.  Against pgh_glm_score_multi_firth over the same file opened dense,
+ * agreement holds for base-0, missing-majority and dense-form rows, as that contract says.
+ *
+ * A row's (out, firth) is a function of its variant's entries, its own phenotype, the covariates, the subset and
+ * firth_cutoff only: not of the other phenotypes of the call or its place among them, of n_pheno, the phenotype block,
+ * the rows that share a wave, a workgroup or a work list with it, v_begin, the variant chunk, the window the dataset
+ * was opened with, PGH_GLM_SCORE_SCRATCH_BYTES (which here also bounds this call's stashes and work lists) or the grid,
+ * and the same call returns the same bytes every time.
+ * Not offered: Firth and saddlepoint in one call, a Firth-penalised null fit, quantitative phenotypes, dosage tracks,
+ * shard groups, a table function. */
+int pgh_glm_score_sparse_multi_firth(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                                     uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
+                                     double firth_cutoff, pgh_glm_row *out, pgh_glm_firth_row *firth, char *errbuf);
 /* Gene-set BURDEN tests over a SPARSE-RESIDENT dataset (pgh_open_sparse), from the variants' entries: per set, the
  * variants are collapsed into one weighted burden per sample and the phenotype is regressed on it (linear).
  *

@@ -4,8 +4,9 @@
 // (burden_sparse.hip); pgh_glm_score_sparse: the logistic score test over such a dataset, from its entries
 // (glm_score_sparse.hip); pgh_glm_score_multi: that test over a dense-resident dataset for many phenotypes in one
 // call, on the FP64 matrix cores (glm_score_dense.hip); pgh_glm_score_sparse_multi: that test over a sparse-resident
-// dataset for many phenotypes in one walk of its entries (glm_score_sparse_multi.hip); pgh_skat_sparse: SKAT and burden score tests of variant sets under that test's null model
-// (skat_sparse.hip, skat_math.hpp, linalg.cpp).
+// dataset for many phenotypes in one walk of its entries (glm_score_sparse_multi.hip), with its saddlepoint and
+// approximate Firth follow-ups (glm_score_sparse_multi_spa.hip, glm_score_sparse_multi_firth.hip); pgh_skat_sparse: SKAT
+// and burden score tests of variant sets under that test's null model (skat_sparse.hip, skat_math.hpp, linalg.cpp).
 #include "api_internal.hpp"
 #include "glm.hpp"
 #include "glm_math.hpp"
@@ -619,10 +620,11 @@ int GlmScoreNullFit(uint32_t n_out, const double *d_y, const double *d_z, uint32
 }
 
 // What a call of a score-test route does after a chunk of rows: nothing; the saddlepoint kernel (GlmScoreSpaKernel,
-// GlmScoreDenseSpaKernel), which replaces the p-value of the rows beyond the cutoff (pgh_glm_score_sparse_spa,
-// pgh_glm_score_multi_spa); or the Firth kernel (GlmScoreSparseFirthKernel, GlmScoreDenseFirthKernel), which writes every
-// row's pgh_glm_firth_row (pgh_glm_score_sparse_firth, pgh_glm_score_multi_firth).  One of the three; the outputs
-// belong to the kind.
+// GlmScoreDenseSpaKernel, GlmScoreSparseMultiSpaKernel), which replaces the p-value of the rows beyond the cutoff
+// (pgh_glm_score_sparse_spa, pgh_glm_score_multi_spa, pgh_glm_score_sparse_multi_spa); or the Firth kernel
+// (GlmScoreSparseFirthKernel, GlmScoreDenseFirthKernel, GlmScoreSparseMultiFirthKernel), which leaves every row's
+// pgh_glm_firth_row (pgh_glm_score_sparse_firth, pgh_glm_score_multi_firth, pgh_glm_score_sparse_multi_firth).  One of
+// the three; the outputs belong to the kind.
 struct GlmScoreFollowUp {
 	enum Kind { kNone, kSpa, kFirth };
 	Kind kind = kNone;
@@ -1166,7 +1168,7 @@ int GlmCheckSpa(double spa_cutoff, const double *p_spa, const uint8_t *spa_state
 	return PGH_OK;
 }
 
-// pgh_glm_score_sparse_firth's and pgh_glm_score_multi_firth's own arguments.
+// pgh_glm_score_sparse_firth's, pgh_glm_score_multi_firth's and pgh_glm_score_sparse_multi_firth's own arguments.
 int GlmCheckFirth(double firth_cutoff, const pgh_glm_firth_row *firth, char *errbuf) {
 	if (!(firth_cutoff >= 0.1)) { // (NaN too)
 		SetErr(errbuf, "firth_cutoff must be at least 0.1");
@@ -1306,37 +1308,38 @@ GlmScoreMultiPlan GlmScoreMultiPlanFor(uint32_t n_raw, uint32_t n_pheno, uint32_
 	return plan;
 }
 
-// pgh_glm_score_sparse_multi_spa's work lists of a chunk (glm_score_sparse_multi_spa.hip): the applied rows of the wave
-// form and of the workgroup form, and the list kernels' counts per tile.  AddTo is their one declaration, as above.
-struct GlmScoreSparseMultiSpaLists {
+// The work lists of a chunk of pgh_glm_score_sparse_multi_spa and pgh_glm_score_sparse_multi_firth
+// (glm_score_sparse_lists.hpp): the applied rows of the wave form and of the workgroup form, and the list kernels'
+// counts per tile.  AddTo is their one declaration, as above.
+struct GlmScoreSparseMultiLists {
 	uint32_t *wave = nullptr, *group = nullptr, *tile_ct = nullptr;
 	void AddTo(ScratchLayout &lay, uint64_t pb_max, uint64_t c, bool present) {
 		lay.Add(&wave, pb_max * c, present);
 		lay.Add(&group, pb_max * c, present);
-		lay.Add(&tile_ct, pgh::GlmScoreSparseMultiSpaTileWords(pb_max * c), present);
+		lay.Add(&tile_ct, pgh::GlmScoreSparseMultiTileWords(pb_max * c), present);
 	}
 };
 
 // pgh_glm_score_sparse_multi*: how a call splits the same budget.  The pair block takes 16 n_raw bytes per phenotype; it
 // gets the most phenotypes, kGlmScoreSparsePb at most, that leave one chunk variant's arrays (and, with a follow-up,
-// one stash) within the budget (one phenotype whatever the budget).  kSpa: the stashes of the workgroup form take up to
-// a quarter of what the block leaves (StashGroupsFor: at least one stash, at most four workgroups per compute unit); a
-// quarter and not GlmScoreMultiPlanFor's three, because only the rows of more than kGlmSparseLong entries and the
-// dense-form rows use one, and the chunk, which every row needs, should not shrink for them.  What is left bounds the
-// chunk at the bytes per variant of GlmScoreMultiChunkArrays and, with kSpa, of the work lists.  The rounding and the
-// block's own small arrays are not charged, as in GlmScoreMultiPlanFor.
+// one stash) within the budget (one phenotype whatever the budget).  A follow-up (kSpa, kFirth): the stashes of its
+// workgroup form take up to a quarter of what the block leaves (StashGroupsFor: at least one stash, at most four
+// workgroups per compute unit); a quarter and not GlmScoreMultiPlanFor's three, because only the rows of more than
+// kGlmSparseLong entries and the dense-form rows use one, and the chunk, which every row needs, should not shrink for
+// them.  What is left bounds the chunk at the bytes per variant of GlmScoreMultiChunkArrays and, with a follow-up, of
+// the work lists.  The rounding and the block's own small arrays are not charged, as in GlmScoreMultiPlanFor.
 GlmScoreMultiPlan GlmScoreSparseMultiPlanFor(uint32_t n_raw, uint32_t n_pheno, uint32_t k, uint32_t nv_all,
                                              uint64_t budget, int cus, GlmScoreFollowUp::Kind kind) {
 	const uint32_t kp = pgh::GlmPadCovar(k);
-	const bool spa = kind == GlmScoreFollowUp::kSpa;
-	const uint64_t per_group = spa ? pgh::GlmScoreSpaStashPerGroup(n_raw) : 0;
+	const bool follow = kind != GlmScoreFollowUp::kNone;
+	const uint64_t per_group = follow ? pgh::GlmScoreSpaStashPerGroup(n_raw) : 0;
 	const auto block_bytes = [&](uint32_t pb) { return 16ull * n_raw * pb; };
 	const auto variant_bytes = [&](uint32_t pb) {
 		GlmScoreMultiChunkArrays unit;
-		GlmScoreSparseMultiSpaLists lists;
+		GlmScoreSparseMultiLists lists;
 		ScratchLayout one_variant;
 		unit.AddTo(one_variant, pb, 1, kp, k, kind);
-		lists.AddTo(one_variant, pb, 1, spa);
+		lists.AddTo(one_variant, pb, 1, follow);
 		return one_variant.payload;
 	};
 	GlmScoreMultiPlan plan;
@@ -1346,7 +1349,7 @@ GlmScoreMultiPlan GlmScoreSparseMultiPlanFor(uint32_t n_raw, uint32_t n_pheno, u
 	}
 	uint64_t left = budget > block_bytes(plan.pb_max) ? budget - block_bytes(plan.pb_max) : 0;
 	const uint32_t nv_most = std::min(kGlmScoreMultiChunk, nv_all);
-	if (spa) {
+	if (follow) {
 		plan.n_groups = StashGroupsFor(static_cast<uint64_t>(nv_most) * plan.pb_max, 4, per_group, left / 4, cus);
 		plan.stash_bytes = per_group * plan.n_groups;
 		left = left > plan.stash_bytes ? left - plan.stash_bytes : 0;
@@ -1631,15 +1634,17 @@ int GlmScoreMultiCall::RunChunk(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t 
 
 // One call of pgh_glm_score_sparse_multi* on one sparse-resident dataset.  Each fit's r and w go into the phenotype's
 // column of the pair block (glm_score_sparse_multi.hip); the entry kernel centres the raw-order covariates per lane on
-// the block's means d_mz.  fu.kind == kSpa: after a chunk's rows, the applied ones are listed and
-// GlmScoreSparseMultiSpaKernel (glm_score_sparse_multi_spa.hip) replaces their p_spa.
+// the block's means d_mz.  With a follow-up, after a chunk's rows the applied ones are listed, and
+// GlmScoreSparseMultiSpaKernel (kSpa, glm_score_sparse_multi_spa.hip) replaces their p_spa, or
+// GlmScoreSparseMultiFirthKernel (kFirth, glm_score_sparse_multi_firth.hip) their pgh_glm_firth_row.
 struct GlmScoreSparseMultiCall : GlmScoreBlockCall {
 	double *d_pair;
 	uint8_t *d_stash;
-	GlmScoreSparseMultiSpaLists lists;
+	GlmScoreSparseMultiLists lists;
 	uint32_t wave_groups = 0; // workgroups of the wave form's grid
 	std::vector<double> hp_spa;
 	std::vector<uint8_t> hstate;
+	std::vector<pgh_glm_firth_row> hfirth;
 
 	int Prepare();
 	int StageBlock(uint32_t b0, uint32_t pb);
@@ -1648,9 +1653,9 @@ struct GlmScoreSparseMultiCall : GlmScoreBlockCall {
 
 int GlmScoreSparseMultiCall::Prepare() {
 	PatternOrder();
-	const bool spa = fu.kind == GlmScoreFollowUp::kSpa;
+	const bool spa = fu.kind == GlmScoreFollowUp::kSpa, follow = fu.kind != GlmScoreFollowUp::kNone;
 	int cus = 0;
-	if (spa) {
+	if (follow) {
 		PGH_TRY(DeviceCus(&cus, "glm_score_sparse_multi stash", errbuf));
 		// the wave form keeps two workgroups on a compute unit (their stashes are LDS): a few rounds of them, so that the
 		// rows' unequal lengths even out
@@ -1662,13 +1667,14 @@ int GlmScoreSparseMultiCall::Prepare() {
 	AddShared(lay);
 	lay.Add(&d_pair, 2ull * n_raw * plan.pb_max);
 	ch.AddTo(lay, plan.pb_max, plan.chunk, kp, k, fu.kind);
-	lists.AddTo(lay, plan.pb_max, plan.chunk, spa);
-	lay.Add(&d_stash, plan.stash_bytes, spa);
+	lists.AddTo(lay, plan.pb_max, plan.chunk, follow);
+	lay.Add(&d_stash, plan.stash_bytes, follow);
 	void *scratch = nullptr;
 	PGH_HIP(PghThreadScratch(lay.total, st, &scratch), "glm_score_sparse_multi scratch");
 	lay.Bind(scratch);
 	hp_spa.resize(spa ? hrows.size() : 0);
 	hstate.resize(spa ? hrows.size() : 0);
+	hfirth.resize(fu.kind == GlmScoreFollowUp::kFirth ? hrows.size() : 0);
 	return PGH_OK;
 }
 
@@ -1690,8 +1696,8 @@ int GlmScoreSparseMultiCall::RunChunk(uint32_t b0, uint32_t pb, uint32_t c0, uin
 	                                       ch.hgn, st),
 	        "glm_score_sparse_multi kernels");
 	PGH_TRY(SolveRows(pb, nv));
+	const size_t n_rows = static_cast<size_t>(nv) * pb;
 	if (fu.kind == GlmScoreFollowUp::kSpa) {
-		const size_t n_rows = static_cast<size_t>(nv) * pb;
 		PGH_HIP(pgh::LaunchGlmScoreSparseMultiSpa(ds->Sparse(), l0, nv, d_pair, pb, d_zr0, d_mz, kp, ch.rows, ch.so.t, fu.cutoff,
 		                                          lists.wave, lists.group, lists.tile_ct, wave_groups, plan.n_groups, d_stash,
 		                                          ch.so.p_spa, ch.so.state, st),
@@ -1700,12 +1706,20 @@ int GlmScoreSparseMultiCall::RunChunk(uint32_t b0, uint32_t pb, uint32_t c0, uin
 		        "glm_score_sparse_multi_spa p copy");
 		PGH_HIP(hipMemcpyAsync(hstate.data(), ch.so.state, n_rows, hipMemcpyDeviceToHost, st),
 		        "glm_score_sparse_multi_spa state copy");
+	} else if (fu.kind == GlmScoreFollowUp::kFirth) {
+		PGH_HIP(pgh::LaunchGlmScoreSparseMultiFirth(ds->Sparse(), l0, nv, d_pair, pb, ch.rows, fu.cutoff, lists.wave, lists.group,
+		                                            lists.tile_ct, wave_groups, plan.n_groups, d_stash, ch.firth, st),
+		        "glm_score_sparse_multi_firth kernels");
+		PGH_HIP(hipMemcpyAsync(hfirth.data(), ch.firth, sizeof(pgh_glm_firth_row) * n_rows, hipMemcpyDeviceToHost, st),
+		        "glm_score_sparse_multi_firth rows copy");
 	}
 	PGH_HIP(hipStreamSynchronize(st), "glm_score_sparse_multi sync");
 	Scatter(b0, pb, c0, nv, hrows, out);
 	if (fu.kind == GlmScoreFollowUp::kSpa) {
 		Scatter(b0, pb, c0, nv, hp_spa, fu.p_spa);
 		Scatter(b0, pb, c0, nv, hstate, fu.state);
+	} else if (fu.kind == GlmScoreFollowUp::kFirth) {
+		Scatter(b0, pb, c0, nv, hfirth, fu.firth);
 	}
 	return PGH_OK;
 }
@@ -1811,7 +1825,8 @@ int GlmScoreMultiEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_t
 
 namespace {
 
-// pgh_glm_score_sparse_multi and pgh_glm_score_sparse_multi_spa after the latter's own argument checks.
+// pgh_glm_score_sparse_multi, pgh_glm_score_sparse_multi_spa and pgh_glm_score_sparse_multi_firth after the latter two's
+// own argument checks.
 int GlmScoreSparseMultiEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                              uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
                              pgh_glm_row *out, const GlmScoreFollowUp &fu, char *errbuf) {
@@ -1840,6 +1855,15 @@ extern "C" int pgh_glm_score_sparse_multi_spa(const pgh_dataset *ds, const pgh_s
                                               pgh_glm_row *out, double *p_spa, uint8_t *spa_state, char *errbuf) {
 	PGH_TRY(GlmCheckSpa(spa_cutoff, p_spa, spa_state, errbuf));
 	const GlmScoreFollowUp fu = {GlmScoreFollowUp::kSpa, spa_cutoff, p_spa, spa_state, nullptr};
+	return GlmScoreSparseMultiEntry(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, fu, errbuf);
+}
+
+extern "C" int pgh_glm_score_sparse_multi_firth(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin,
+                                                uint32_t v_end, uint32_t n_pheno, const double *phenotypes,
+                                                uint32_t n_covar, const double *covariates, double firth_cutoff,
+                                                pgh_glm_row *out, pgh_glm_firth_row *firth, char *errbuf) {
+	PGH_TRY(GlmCheckFirth(firth_cutoff, firth, errbuf));
+	const GlmScoreFollowUp fu = {GlmScoreFollowUp::kFirth, firth_cutoff, nullptr, nullptr, firth};
 	return GlmScoreSparseMultiEntry(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, fu, errbuf);
 }
 

@@ -232,13 +232,22 @@ hipError_t LaunchGlmScoreSpa(const SparseView &sv, uint32_t v_first, uint32_t nv
                              double cutoff, uint32_t n_groups, void *stash, double *p_spa, uint8_t *state,
                              hipStream_t stream);
 
+// ---- the work lists of the pair block's follow-ups (glm_score_sparse_lists.hpp) ----
+// Elements of a workgroup of the list kernels, and the tiles of a chunk of n_rows = nv * pb (variant, phenotype) rows.
+constexpr uint32_t kGlmScoreSparseListTile = 2048;
+inline uint64_t GlmScoreSparseListTiles(uint64_t n_rows) {
+	return (n_rows + kGlmScoreSparseListTile - 1) / kGlmScoreSparseListTile;
+}
+// Words of tile_ct for such a chunk: two counts per tile, then the two lists' lengths.
+inline uint64_t GlmScoreSparseMultiTileWords(uint64_t n_rows) {
+	return 2 * GlmScoreSparseListTiles(n_rows) + 2;
+}
+
 // ---- pgh_glm_score_sparse_multi_spa (glm_score_sparse_multi_spa.hip): saddlepoint p-values of the pair block's rows ----
-// Words of tile_ct for a chunk of n_rows = nv * pb (variant, phenotype) rows.
-uint64_t GlmScoreSparseMultiSpaTileWords(uint64_t n_rows);
 // For the rows (phenotype p < pb, chunk variant i < nv) at p * nv + i that are fitted with |stat| > cutoff: p_spa and
 // state = 1, or state = 2 with p_spa left as it is; the other rows are not touched.  sv, v_first, nv, pair, pb, z0, mz
 // and kp are LaunchGlmScoreSparseMulti's; rows and t ([pb][nv][kp + 3]) are LaunchGlmScoreSolve's, phenotype by
-// phenotype.  list_wave, list_group: nv * pb words each and tile_ct: GlmScoreSparseMultiSpaTileWords words, whatever
+// phenotype.  list_wave, list_group: nv * pb words each and tile_ct: GlmScoreSparseMultiTileWords words, whatever
 // they hold (the applied rows of either form, listed first).  n_wave_groups: the workgroups of the wave form's grid;
 // stash: n_groups x GlmScoreSpaStashPerGroup bytes, whatever they hold.  Nothing in the output depends on
 // n_wave_groups or n_groups (both >= 1).
@@ -257,6 +266,19 @@ hipError_t LaunchGlmScoreSparseMultiSpa(const SparseView &sv, uint32_t v_first, 
 hipError_t LaunchGlmScoreSparseFirth(const SparseView &sv, uint32_t v_first, uint32_t nv, const double *r,
                                      const pgh_glm_row *rows, double cutoff, uint32_t n_groups, void *stash,
                                      pgh_glm_firth_row *firth, hipStream_t stream);
+
+// ---- pgh_glm_score_sparse_multi_firth (glm_score_sparse_multi_firth.hip): approximate Firth estimates of the pair
+// block's rows ----
+// For every row (phenotype p < pb, chunk variant i < nv) at p * nv + i: firth[p * nv + i], the contract's triple and
+// state (the score row's beta, se and p with state 0 where the row is not fitted or |stat| <= cutoff).  sv, v_first, nv,
+// pair and pb are LaunchGlmScoreSparseMulti's; rows are LaunchGlmScoreSolve's, phenotype by phenotype.  list_wave,
+// list_group, tile_ct, n_wave_groups, n_groups and stash are LaunchGlmScoreSparseMultiSpa's.  Nothing in the output
+// depends on n_wave_groups or n_groups (both >= 1).
+hipError_t LaunchGlmScoreSparseMultiFirth(const SparseView &sv, uint32_t v_first, uint32_t nv, const double *pair,
+                                          uint32_t pb, const pgh_glm_row *rows, double cutoff, uint32_t *list_wave,
+                                          uint32_t *list_group, uint32_t *tile_ct, uint32_t n_wave_groups,
+                                          uint32_t n_groups, void *stash, pgh_glm_firth_row *firth,
+                                          hipStream_t stream);
 
 // ---- pgh_glm_score_multi_spa (glm_score_dense_spa.hip): saddlepoint p-values of the dense route's rows ----
 // For the rows (phenotype p < pb, chunk variant i < nv) at p * nv + i that are fitted with |stat| > cutoff: p_spa and

@@ -1,7 +1,9 @@
-// glm_firth.hpp -- phase B of GlmScoreDenseFirthKernel (glm_score_dense_firth.hip) and GlmScoreSparseFirthKernel
-// (glm_score_sparse_firth.hip): the approximate Firth estimate of a row's own coefficient from one team's stash of
-// (x, mu) pairs, with glm_spa.hpp's pi and K (the contract is pgh_glm_score_multi_firth's in include/pgenhip.h;
-// pgh_glm_score_sparse_firth's pairs hold d = x - b in x's place).
+// glm_firth.hpp -- phase B of GlmScoreDenseFirthKernel (glm_score_dense_firth.hip), GlmScoreSparseFirthKernel
+// (glm_score_sparse_firth.hip) and GlmScoreSparseMultiFirthKernel (glm_score_sparse_multi_firth.hip): the approximate
+// Firth estimate of a row's own coefficient from one team's stash of (x, mu) pairs, with glm_spa.hpp's pi and K (the
+// contract is pgh_glm_score_multi_firth's in include/pgenhip.h; pgh_glm_score_sparse_firth's pairs hold d = x - b in
+// x's place).  And SparseFirthRow, the sparse kernels' row: the walk of a sparse-resident row's entries into the stash,
+// then phase B.
 #pragma once
 
 #include "glm_spa.hpp"
@@ -99,6 +101,105 @@ __device__ __forceinline__ bool FirthSolveStash(Stash st, uint32_t count, bool o
 		u = un;
 	}
 	return ok && done;
+}
+
+// One sparse-resident row by one team: phase A, the walk of the row's entries into the team's stash, and phase B, for
+// GlmScoreSparseFirthKernel (glm_score_sparse_firth.hip) and GlmScoreSparseMultiFirthKernel
+// (glm_score_sparse_multi_firth.hip).  i: the chunk variant; at: where the row stands in out and firth.  st: the team's
+// stash of at least `cap` pairs (LDS or global).  r_of(s): the staged r of raw sample s, NaN where s is outside S.
+// The team returns from a row of the other form (a wave takes the sparse rows of at most kGlmSparseLong entries, the
+// workgroup the longer ones and the dense-form rows); of every other row it writes firth[at]: the score row's beta, se
+// and p with state 0 where the row is not fitted or |stat| <= cutoff.
+template <int TEAM, class R, class Stash>
+__device__ __forceinline__ void SparseFirthRow(const SparseRows &rows, uint32_t i, uint32_t at, const R &r_of,
+                                               const pgh_glm_row *__restrict__ out, double cutoff, Stash st,
+                                               uint32_t cap, pgh_glm_firth_row *__restrict__ firth) {
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const int tid = TEAM == kTeamBlock ? static_cast<int>(threadIdx.x) : lane;
+	const uint32_t r = rows.v_first + i;
+	const int32_t ro = rows.row_of[r];
+	const bool dense = ro >= 0;
+	uint64_t e0 = 0, e1 = rows.sample_ct;
+	if (dense) {
+		if (TEAM != kTeamBlock) {
+			return; // the workgroup launch's row
+		}
+	} else {
+		e0 = rows.off[r];
+		e1 = rows.off[r + 1];
+		if ((e1 - e0 > kGlmSparseLong) != (TEAM == kTeamBlock)) {
+			return; // the other launch's row
+		}
+	}
+	const bool fitted = out[at].errcode == PGH_GLM_OK;
+	pgh_glm_firth_row res {};
+	res.beta = fitted ? out[at].beta : NAN;
+	res.se = fitted ? out[at].se : NAN;
+	res.p = fitted ? out[at].p : NAN;
+	if (fitted && fabs(out[at].stat) > cutoff) { // (the whole team)
+		const uint8_t *prow = dense ? rows.pool + static_cast<uint64_t>(ro) * rows.pitch : nullptr;
+		const int bx = (dense || ro == -4) ? 0 : -1 - ro;
+
+		// phase A
+		uint32_t count = 0;
+		double sums[1] = {0.0};
+		long long none[4] = {0, 0, 0, 0};
+		for (uint64_t p0 = e0; p0 < e1; p0 += TEAM) {
+			const uint64_t p = p0 + tid;
+			bool take = false;
+			double d = 0.0, mu = 0.0;
+			if (p < e1) {
+				uint32_t code, s;
+				bool entry;
+				if (dense) {
+					s = static_cast<uint32_t>(p);
+					code = (prow[s >> 2] >> (2 * (s & 3u))) & 3u;
+					entry = code != 0u;
+				} else {
+					const uint32_t x = rows.entries[p];
+					s = x >> 2;
+					code = x & 3u;
+					entry = s < rows.sample_ct;
+				}
+				// (a base-3 row holds its hom-ref calls as entries: d = 0, a constant of l*, not in E)
+				if (entry && code != 3u && static_cast<int>(code) != bx) {
+					const double ri = r_of(s);
+					if (ri == ri) {
+						take = true;
+						d = static_cast<double>(static_cast<int>(code) - bx);
+						mu = ri > 0.0 ? 1.0 - ri : -ri;
+						sums[0] = fma(d, ri, sums[0]);
+					}
+				}
+			}
+			uint32_t total;
+			const uint32_t pos = count + TeamRank<TEAM>(take, lane, wave, &total);
+			if (take && pos < cap) {
+				st[pos] = make_double2(d, mu);
+			}
+			count += total;
+			TeamSync<TEAM>(); // TeamRank's counts are rewritten by the next step
+		}
+		TeamSums<TEAM>(sums, none, lane, wave);
+		TeamSync<TEAM>(); // the pairs before their readers, and TeamSums' LDS before it is written again
+		// (the row is the same for the whole workgroup, which would make G and the state of the iteration scalar
+		// registers: keep them in vector registers, as GlmScoreDenseFirthKernel does)
+		double g = sums[0];
+		asm volatile("" : "+v"(g));
+
+		// phase B
+		FirthFit fit;
+		const bool ok = FirthSolveStash<TEAM>(st, count, count <= cap, g, tid, lane, wave, &fit);
+		if (ok) {
+			res.beta = fit.beta;
+			res.se = fit.se;
+			res.p = fit.p;
+		}
+		res.state = ok ? 1 : 2;
+	}
+	if (tid == 0) {
+		firth[at] = res;
+	}
 }
 
 } // namespace

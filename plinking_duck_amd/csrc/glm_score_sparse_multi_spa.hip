@@ -5,16 +5,11 @@
 // GlmScoreSolveKernel (glm_score_sparse.hip) has left per (block phenotype j, chunk variant i), at j * nv + i, its row,
 // [t = H_N^-1 c, U, V], and p_spa = p with state 0.
 //
-// The work lists.  The rows that are applied (fitted with |stat| > cutoff) are few, so no team is launched per possible
-// row: three small kernels list them first, in [variant][phenotype] order (element e = i * pb + j), so that the
-// phenotypes applied for one variant run next to each other in time and find the variant's entry words and covariate
-// rows in L2.  The wave-form list holds the sparse rows of at most kGlmSparseLong entries, the workgroup-form list the
-// longer ones and the dense-form rows: the entry kernel's split.  A workgroup of the count kernel takes kListTile
-// consecutive elements, a thread kListOwn consecutive ones of them, and leaves the tile's two counts; one workgroup
-// turns the tiles' counts into their offsets and the lists' lengths; the write kernel ranks its tile again in thread
-// order (TeamRankCounts) and writes the elements at offset + rank.  No atomics: a list is the applied elements of its
-// form in ascending order, whatever the grid.  No result depends on that order either: a row is computed from its own
-// inputs alone.
+// The work lists (glm_score_sparse_lists.hpp, shared with glm_score_sparse_multi_firth.hip).  The rows that are applied
+// (fitted with |stat| > cutoff) are few, so no team is launched per possible row: three small kernels list them first,
+// in [variant][phenotype] order (element e = i * pb + j), one list per team form, without atomics.  The phenotypes
+// applied for one variant then run next to each other in time and find the variant's entry words and covariate rows in
+// L2.
 //
 // One row by one team: SpaSparseRow (glm_spa.hpp), GlmScoreSpaKernel's walk and iteration, reading a sample through
 // PairSrc: (r, w) is one double2 of the pair block at s * pb + j, and the covariate row is the raw-order one with
@@ -23,6 +18,7 @@
 // bounded grid whose teams stride over their list, whose length they read from the device.  Nothing depends on which
 // team takes a row, on the grids, on the chunk, on the phenotype block or on where the range starts.
 #include "glm.hpp"
+#include "glm_score_sparse_lists.hpp"
 #include "glm_spa.hpp"
 #include "glm_team.hpp"
 
@@ -36,8 +32,6 @@ namespace {
 
 constexpr int kBlock = kTeamBlock;
 constexpr uint32_t kSpaWaveStash = kGlmSparseLong; // pairs per wave
-constexpr uint32_t kListOwn = 8;                   // consecutive elements of a thread of the list kernels
-constexpr uint32_t kListTile = kBlock * kListOwn;  // elements of a workgroup of the list kernels
 
 struct SparseMultiSpaArgs {
 	SparseRows rows;
@@ -54,89 +48,6 @@ struct SparseMultiSpaArgs {
 	double *p_spa;  // [pb][nv]
 	uint8_t *state; // [pb][nv]
 };
-
-// ---------------------------------------------------------------------------
-// the work lists
-// ---------------------------------------------------------------------------
-
-// A thread's kListOwn elements: bit u of *mw / *mg set where element e0 + u is applied and of the wave / workgroup form.
-__device__ __forceinline__ void ListFlags(const SparseMultiSpaArgs &a, uint32_t e0, uint32_t *mw, uint32_t *mg) {
-	const uint32_t n = a.rows.nv * a.pb;
-	*mw = *mg = 0;
-#pragma unroll
-	for (uint32_t u = 0; u < kListOwn; u++) {
-		const uint32_t e = e0 + u;
-		if (e < n) {
-			const uint32_t i = e / a.pb, j = e - i * a.pb;
-			const pgh_glm_row &row = a.out[static_cast<uint64_t>(j) * a.rows.nv + i];
-			if (row.errcode == PGH_GLM_OK && fabs(row.stat) > a.cutoff) {
-				const uint32_t r = a.rows.v_first + i;
-				const bool wide = a.rows.row_of[r] >= 0 || a.rows.off[r + 1] - a.rows.off[r] > kGlmSparseLong;
-				*mw |= wide ? 0u : 1u << u;
-				*mg |= wide ? 1u << u : 0u;
-			}
-		}
-	}
-}
-
-__global__ void __launch_bounds__(kBlock) GlmScoreSparseMultiSpaCountKernel(const SparseMultiSpaArgs a) {
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	uint32_t mw, mg, tw, tg;
-	ListFlags(a, blockIdx.x * kListTile + threadIdx.x * kListOwn, &mw, &mg);
-	TeamRankCounts(static_cast<uint32_t>(__popc(mw)), 0, lane, wave, &tw);
-	TeamRankCounts(static_cast<uint32_t>(__popc(mg)), 1, lane, wave, &tg);
-	if (threadIdx.x == 0) {
-		a.tile_ct[2 * blockIdx.x] = tw;
-		a.tile_ct[2 * blockIdx.x + 1] = tg;
-	}
-}
-
-// One workgroup: tile_ct[tile][f] becomes the number of list f's elements before the tile, tile_ct[n_tiles][f] the
-// list's length.  A thread takes consecutive tiles, so the offsets are those of the ascending order.
-__global__ void __launch_bounds__(kBlock) GlmScoreSparseMultiSpaOffsetKernel(const SparseMultiSpaArgs a) {
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const uint32_t per = (a.n_tiles + kBlock - 1) / kBlock;
-	const uint32_t t0 = threadIdx.x * per, t1 = t0 + per < a.n_tiles ? t0 + per : a.n_tiles;
-	for (uint32_t f = 0; f < 2u; f++) {
-		uint32_t mine = 0;
-		for (uint32_t t = t0; t < t1; t++) {
-			mine += a.tile_ct[2 * t + f];
-		}
-		uint32_t total;
-		uint32_t before = TeamRankCounts(mine, f, lane, wave, &total);
-		for (uint32_t t = t0; t < t1; t++) {
-			const uint32_t c = a.tile_ct[2 * t + f];
-			a.tile_ct[2 * t + f] = before;
-			before += c;
-		}
-		if (threadIdx.x == 0) {
-			a.tile_ct[2 * a.n_tiles + f] = total;
-		}
-	}
-}
-
-// The elements of the set bits of a thread's mask m, the first of them at list[pos]; n: the list's room.
-__device__ __forceinline__ void ListWrite(uint32_t m, uint32_t e0, uint32_t pos, uint32_t n, uint32_t *__restrict__ list) {
-	while (m) {
-		const uint32_t u = static_cast<uint32_t>(__ffs(static_cast<int>(m)) - 1);
-		m &= m - 1u;
-		if (pos < n) { // (it is: a list holds no more than the chunk's elements)
-			list[pos] = e0 + u;
-		}
-		pos++;
-	}
-}
-
-__global__ void __launch_bounds__(kBlock) GlmScoreSparseMultiSpaListKernel(const SparseMultiSpaArgs a) {
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const uint32_t e0 = blockIdx.x * kListTile + threadIdx.x * kListOwn, n = a.rows.nv * a.pb;
-	uint32_t mw, mg, total;
-	ListFlags(a, e0, &mw, &mg);
-	const uint32_t pw = TeamRankCounts(static_cast<uint32_t>(__popc(mw)), 0, lane, wave, &total);
-	const uint32_t pg = TeamRankCounts(static_cast<uint32_t>(__popc(mg)), 1, lane, wave, &total);
-	ListWrite(mw, e0, a.tile_ct[2 * blockIdx.x] + pw, n, a.list_wave);
-	ListWrite(mg, e0, a.tile_ct[2 * blockIdx.x + 1] + pg, n, a.list_group);
-}
 
 // ---------------------------------------------------------------------------
 // the rows
@@ -203,10 +114,6 @@ __global__ void __launch_bounds__(kBlock) GlmScoreSparseMultiSpaKernel(const Spa
 
 } // namespace
 
-uint64_t GlmScoreSparseMultiSpaTileWords(uint64_t n_rows) {
-	return 2 * ((n_rows + kListTile - 1) / kListTile) + 2;
-}
-
 hipError_t LaunchGlmScoreSparseMultiSpa(const SparseView &sv, uint32_t v_first, uint32_t nv, const double *pair,
                                         uint32_t pb, const double *z0, const double *mz, uint32_t kp,
                                         const pgh_glm_row *rows, const double *t, double cutoff, uint32_t *list_wave,
@@ -235,13 +142,11 @@ hipError_t LaunchGlmScoreSparseMultiSpa(const SparseView &sv, uint32_t v_first, 
 	a.list_wave = list_wave;
 	a.list_group = list_group;
 	a.tile_ct = tile_ct;
-	a.n_tiles = static_cast<uint32_t>((n_rows + kListTile - 1) / kListTile);
+	a.n_tiles = static_cast<uint32_t>(GlmScoreSparseListTiles(n_rows));
 	a.stash = static_cast<double2 *>(stash);
 	a.p_spa = p_spa;
 	a.state = state;
-	GlmScoreSparseMultiSpaCountKernel<<<a.n_tiles, kBlock, 0, stream>>>(a);
-	GlmScoreSparseMultiSpaOffsetKernel<<<1, kBlock, 0, stream>>>(a);
-	GlmScoreSparseMultiSpaListKernel<<<a.n_tiles, kBlock, 0, stream>>>(a);
+	LaunchGlmScoreSparseMultiLists(a, stream);
 	const uint64_t wave_most = (n_rows + kTeamWaves - 1) / kTeamWaves;
 	return GlmForWidth(kp, [&](auto width) {
 		constexpr int KP = decltype(width)::value;

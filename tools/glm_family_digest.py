@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """One SHA-256 per case over the result bytes of the GLM family (pgh_glm, pgh_glm_multi, pgh_glm_sparse,
-pgh_glm_score_sparse, pgh_glm_score_sparse_spa, pgh_glm_score_sparse_firth, pgh_glm_score_sparse_multi, pgh_glm_score_sparse_multi_spa, pgh_glm_score_multi, pgh_glm_score_multi_spa,
+pgh_glm_score_sparse, pgh_glm_score_sparse_spa, pgh_glm_score_sparse_firth, pgh_glm_score_sparse_multi, pgh_glm_score_sparse_multi_spa, pgh_glm_score_sparse_multi_firth, pgh_glm_score_multi, pgh_glm_score_multi_spa,
 pgh_glm_score_multi_firth, pgh_burden_sparse), pgh_score_sparse, and the plink_ld pair sums and sparse counts that share their wave sums: the
 paths a change to the family's kernels, host staging, scratch layout or chunk loops can touch.  Two builds of the library
 compute the same rows bit for bit exactly when their outputs of this tool are equal line for line; PGENHIP_LIB names
@@ -340,4 +340,28 @@ for max_minor, form in ((n, "entries only"), (1, "with dense-form rows")):
             Yk = np.stack([SM.O.pheno(rng_k, n, Zk), SM.O.pheno(rng_k, n, Zk, case_rate=0.35, missing=0.1)])
             res = sp.glm_score_sparse_multi_spa(Yk, Zk, spa_cutoff=CUT)
             emit(f"glm_score_sparse_multi_spa {form}, k={k} P=2", res, note=share(res, "spa_state"))
+    sp.close()
+
+# ---- pgh_glm_score_sparse_multi_firth, on the same files and inputs at the lowest cutoff.  Again last, after every line
+# of a build without the entry point -------------------------------------------------------------------------------------
+for max_minor, form in ((n, "entries only"), (1, "with dense-form rows")):
+    sp = L.Dataset.open(path, sparse=True, max_minor=max_minor)
+    for k in (0, 3):
+        Zk, Yk, _ = SM.parity_inputs(n, k)
+        res = sp.glm_score_sparse_multi_firth(Yk, Zk if k else None, firth_cutoff=CUT)
+        emit(f"glm_score_sparse_multi_firth {form}, k={k} P=6", res, note=share(res, "firth_state"))
+    res = sp.glm_score_sparse_multi_firth(np.stack([Y3[i % len(Y3)] for i in range(65)]), Z3, firth_cutoff=CUT)
+    emit(f"glm_score_sparse_multi_firth {form}, k=3 P=65", res, note=share(res, "firth_state"))
+    sub = sp.subset(keep_m)
+    res = sp.glm_score_sparse_multi_firth(np.ascontiguousarray(Y3[:, keep_m]), np.ascontiguousarray(Z3[:, keep_m]),
+                                          firth_cutoff=CUT, subset=sub)
+    emit(f"glm_score_sparse_multi_firth {form}, k=3 subset", res, note=share(res, "firth_state"))
+    sub.close()
+    if max_minor == n:
+        for k in (4, 20):
+            rng_k = np.random.default_rng(3000 + k)
+            Zk = SM._covariates(rng_k, k, n)
+            Yk = np.stack([SM.O.pheno(rng_k, n, Zk), SM.O.pheno(rng_k, n, Zk, case_rate=0.35, missing=0.1)])
+            res = sp.glm_score_sparse_multi_firth(Yk, Zk, firth_cutoff=CUT)
+            emit(f"glm_score_sparse_multi_firth {form}, k={k} P=2", res, note=share(res, "firth_state"))
     sp.close()
