@@ -608,10 +608,31 @@ int pgh_glm_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_be
  * the phenotype, the covariates and the subset only: not of v_begin, the chunk or the rows around it, and the same
  * call returns the same bytes every time.  Logistic Wald fits and pgh_glm's full Firth fits over a sparse-resident
  * dataset are not offered (the logistic score test is: pgh_glm_score_sparse; its approximate Firth estimate is:
- * pgh_glm_score_sparse_firth). */
+ * pgh_glm_score_sparse_firth).  Many phenotypes in one walk of the entries: pgh_glm_sparse_multi. */
 int pgh_glm_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                    const double *phenotype, uint32_t n_covar, const double *covariates,
                    pgh_glm_row *out, char *errbuf);
+/* pgh_glm_sparse for MANY PHENOTYPES in one walk of the entries of a SPARSE-RESIDENT dataset (pgh_open_sparse): up to
+ * 64 quantitative phenotypes, each with its own missing-value pattern, share the reads of every entry word and
+ * covariate row.  Arguments, argument checks and the layout of `out` are pgh_glm_multi's (model LINEAR): phenotypes is
+ * [n_pheno][n_out], NaN = missing; covariates is covariate-major; out[(v - v_begin) * n_pheno + p] is phenotype p's row
+ * for variant v.  A dataset that is not sparse-resident ("needs a sparse-resident dataset") and a shard group are
+ * PGH_ERR_ARG with `out` untouched; v_begin == v_end is PGH_OK; a phenotype with every value missing is legal, its
+ * rows are TOO_FEW_SAMPLES.
+ * Each row is the row pgh_glm_sparse returns for that phenotype alone over the same dataset: errcode, obs_ct, firth (0)
+ * and a1_freq bit for bit, beta, se, stat and p to rounding.  The rows of variants held in the dense form
+ * (pgh_sparse_info.dense_variant_ct) are walked from their pool rows as base-0 rows and obey the same contract: to
+ * rounding, not bit for bit against pgh_glm.  A row is a function of its variant's entries, its own phenotype, the
+ * covariates and the subset only: not of the other phenotypes of the call, its place among them, n_pheno, the rows
+ * around it, v_begin, the chunk, the window the dataset was opened with or the scratch budget, and the same call
+ * returns the same bytes every time.
+ * PGH_GLM_SCORE_SCRATCH_BYTES (environment, read at every call, default 6 GiB) bounds the device scratch that grows
+ * with the phenotypes and variants in flight (8 bytes per raw sample and 8 per subset sample and block phenotype, then
+ * the chunk's sums); the result does not depend on it.
+ * Not offered: dosage tracks, shard groups, a table function. */
+int pgh_glm_sparse_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                         uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
+                         pgh_glm_row *out, char *errbuf);
 /* The logistic SCORE TEST of every variant of [v_begin, v_end) of a SPARSE-RESIDENT dataset (pgh_open_sparse), from
  * the variants' entries: the covariates-only model is fitted once, and a variant then costs in proportion to the
  * samples that differ from its base code.  Arguments, argument checks, row layout and error codes are
@@ -717,8 +738,8 @@ int pgh_glm_score_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_
  * with the phenotypes and variants in flight (16 bytes per sample and block phenotype, then the chunk's sums); the
  * result does not depend on it.
  * Saddlepoint p-values over this route: pgh_glm_score_sparse_multi_spa.  Approximate Firth estimates over this route:
- * pgh_glm_score_sparse_multi_firth.  Not offered: quantitative phenotypes, dosage tracks, shard groups, a table
- * function. */
+ * pgh_glm_score_sparse_multi_firth.  Quantitative phenotypes over this route: pgh_glm_sparse_multi.  Not offered:
+ * dosage tracks, shard groups, a table function. */
 int pgh_glm_score_sparse_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                                uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
                                pgh_glm_row *out, char *errbuf);

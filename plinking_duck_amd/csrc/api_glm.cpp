@@ -5,8 +5,10 @@
 // (glm_score_sparse.hip); pgh_glm_score_multi: that test over a dense-resident dataset for many phenotypes in one
 // call, on the FP64 matrix cores (glm_score_dense.hip); pgh_glm_score_sparse_multi: that test over a sparse-resident
 // dataset for many phenotypes in one walk of its entries (glm_score_sparse_multi.hip), with its saddlepoint and
-// approximate Firth follow-ups (glm_score_sparse_multi_spa.hip, glm_score_sparse_multi_firth.hip); pgh_skat_sparse: SKAT
-// and burden score tests of variant sets under that test's null model (skat_sparse.hip, skat_math.hpp, linalg.cpp).
+// approximate Firth follow-ups (glm_score_sparse_multi_spa.hip, glm_score_sparse_multi_firth.hip); pgh_glm_sparse_multi:
+// the linear fit over such a dataset for many phenotypes in one walk of its entries (glm_sparse_multi.hip);
+// pgh_skat_sparse: SKAT and burden score tests of variant sets under that test's null model (skat_sparse.hip,
+// skat_math.hpp, linalg.cpp).
 #include "api_internal.hpp"
 #include "glm.hpp"
 #include "glm_math.hpp"
@@ -1328,6 +1330,27 @@ struct GlmScoreSparseMultiLists {
 // kGlmSparseLong entries and the dense-form rows use one, and the chunk, which every row needs, should not shrink for
 // them.  What is left bounds the chunk at the bytes per variant of GlmScoreMultiChunkArrays and, with a follow-up, of
 // the work lists.  The rounding and the block's own small arrays are not charged, as in GlmScoreMultiPlanFor.
+// The split itself, shared with pgh_glm_sparse_multi: block_bytes(pb) the block of pb phenotypes, variant_bytes(pb) a
+// chunk variant's arrays, per_group a follow-up's stash (0: there is no follow-up).
+template <class BlockBytes, class VariantBytes>
+GlmScoreMultiPlan GlmSparseBlockPlanFor(uint32_t pb_most, uint32_t n_pheno, uint32_t nv_all, uint64_t budget, int cus,
+                                        uint64_t per_group, BlockBytes block_bytes, VariantBytes variant_bytes) {
+	GlmScoreMultiPlan plan;
+	plan.pb_max = std::min(pb_most, n_pheno);
+	while (plan.pb_max > 1 && block_bytes(plan.pb_max) + variant_bytes(plan.pb_max) + per_group > budget) {
+		plan.pb_max--;
+	}
+	uint64_t left = budget > block_bytes(plan.pb_max) ? budget - block_bytes(plan.pb_max) : 0;
+	const uint32_t nv_most = std::min(kGlmScoreMultiChunk, nv_all);
+	if (per_group) {
+		plan.n_groups = StashGroupsFor(static_cast<uint64_t>(nv_most) * plan.pb_max, 4, per_group, left / 4, cus);
+		plan.stash_bytes = per_group * plan.n_groups;
+		left = left > plan.stash_bytes ? left - plan.stash_bytes : 0;
+	}
+	plan.chunk = static_cast<uint32_t>(std::min<uint64_t>(nv_most, std::max<uint64_t>(1, left / variant_bytes(plan.pb_max))));
+	return plan;
+}
+
 GlmScoreMultiPlan GlmScoreSparseMultiPlanFor(uint32_t n_raw, uint32_t n_pheno, uint32_t k, uint32_t nv_all,
                                              uint64_t budget, int cus, GlmScoreFollowUp::Kind kind) {
 	const uint32_t kp = pgh::GlmPadCovar(k);
@@ -1342,20 +1365,7 @@ GlmScoreMultiPlan GlmScoreSparseMultiPlanFor(uint32_t n_raw, uint32_t n_pheno, u
 		lists.AddTo(one_variant, pb, 1, follow);
 		return one_variant.payload;
 	};
-	GlmScoreMultiPlan plan;
-	plan.pb_max = std::min(pgh::kGlmScoreSparsePb, n_pheno);
-	while (plan.pb_max > 1 && block_bytes(plan.pb_max) + variant_bytes(plan.pb_max) + per_group > budget) {
-		plan.pb_max--;
-	}
-	uint64_t left = budget > block_bytes(plan.pb_max) ? budget - block_bytes(plan.pb_max) : 0;
-	const uint32_t nv_most = std::min(kGlmScoreMultiChunk, nv_all);
-	if (follow) {
-		plan.n_groups = StashGroupsFor(static_cast<uint64_t>(nv_most) * plan.pb_max, 4, per_group, left / 4, cus);
-		plan.stash_bytes = per_group * plan.n_groups;
-		left = left > plan.stash_bytes ? left - plan.stash_bytes : 0;
-	}
-	plan.chunk = static_cast<uint32_t>(std::min<uint64_t>(nv_most, std::max<uint64_t>(1, left / variant_bytes(plan.pb_max))));
-	return plan;
+	return GlmSparseBlockPlanFor(pgh::kGlmScoreSparsePb, n_pheno, nv_all, budget, cus, per_group, block_bytes, variant_bytes);
 }
 
 // What one call of pgh_glm_score_multi* (a dense-resident dataset) and of pgh_glm_score_sparse_multi* (a sparse-resident
@@ -1742,6 +1752,156 @@ int GlmScoreBlocksRun(Call &c, pgh_glm_row *out) {
 	return PGH_OK;
 }
 
+// The device arrays of pgh_glm_sparse_multi that scale with the chunk, per (chunk variant, block phenotype).  AddTo is
+// their one declaration, as GlmScoreMultiChunkArrays' is.
+struct GlmSparseMultiChunkArrays {
+	double *sums = nullptr, *corr = nullptr;
+	uint32_t *nlist = nullptr;
+	pgh_glm_row *rows = nullptr;
+	void AddTo(ScratchLayout &lay, uint64_t pb_max, uint64_t c, uint32_t kp, uint32_t k) {
+		const uint64_t n = pb_max * c, q = k + 2;
+		lay.Add(&sums, n * (kp + 4));
+		lay.Add(&corr, n * (q * (q + 1) / 2));
+		lay.Add(&nlist, c);
+		lay.Add(&rows, n);
+	}
+};
+
+// One call of pgh_glm_sparse_multi on one sparse-resident dataset (glm_sparse_multi.hip), run by GlmScoreBlocksRun.  The
+// phenotypes are taken in the caller's order, blocks of consecutive ones: a block's values are uploaded as they are and
+// written into the value block centred on each phenotype's own mean; the covariates stay as they are on the device and
+// the kernels centre them per phenotype on d_mz, the means over the phenotype's own samples (GlmStage's sums, so the
+// numbers are pgh_glm_sparse's).  A chunk's rows come back variant-major and go into `out` with one strided copy.
+struct GlmSparseMultiCall {
+	const pgh_dataset *ds;
+	const pgh_subset *subset;
+	uint32_t v_begin, nv_all, n_pheno, k;
+	const double *phenotypes, *covariates;
+	char *errbuf;
+	hipStream_t st = PghThreadStream();
+	uint32_t n_out = subset ? subset->n_out : ds->sample_ct, n_raw = ds->sample_ct;
+	uint32_t kp = pgh::GlmPadCovar(k), ne = (k + 2) * (k + 3) / 2;
+	const uint32_t *d_sel = subset ? subset->d_sel : nullptr;
+	GlmScoreMultiPlan plan;
+	const GlmStaged *staged = nullptr; // the covariates, sample-major (UploadCovariates)
+
+	double *d_z0, *d_zr0, *d_yb, *d_yv, *d_my, *d_mz, *d_part, *d_gram;
+	uint32_t *d_ny;
+	GlmSparseMultiChunkArrays ch;
+	std::vector<double> h_my, h_mz;
+	std::vector<uint32_t> h_ny;
+
+	int Prepare();
+	int UploadCovariates(const GlmStaged &sg);
+	int StageBlock(uint32_t b0, uint32_t pb);
+	int RunChunk(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t nv, pgh_glm_row *out);
+};
+
+// The plan (the value block and the uploaded phenotypes take 8 (n_raw + n_out) bytes per phenotype), the scratch block
+// and the host buffers.
+int GlmSparseMultiCall::Prepare() {
+	const auto block_bytes = [&](uint32_t pb) { return 8ull * (static_cast<uint64_t>(n_raw) + n_out) * pb; };
+	const auto variant_bytes = [&](uint32_t pb) {
+		GlmSparseMultiChunkArrays unit;
+		ScratchLayout one_variant;
+		unit.AddTo(one_variant, pb, 1, kp, k);
+		return one_variant.payload;
+	};
+	plan = GlmSparseBlockPlanFor(pgh::kGlmSparseMultiPb, n_pheno, nv_all, EnvBytes(kGlmScoreScratchEnv, kGlmScoreScratchBytes),
+	                             0, 0, block_bytes, variant_bytes);
+	const uint64_t n = n_out, nr = n_raw, pbm = plan.pb_max;
+	ScratchLayout lay;
+	lay.Add(&d_z0, n * kp + 1); // one element of slack, here and in d_zr0, d_mz
+	lay.Add(&d_zr0, nr * kp + 1, subset != nullptr);
+	lay.Add(&d_yb, n * pbm);
+	lay.Add(&d_yv, nr * pbm);
+	lay.Add(&d_my, pbm);
+	lay.Add(&d_mz, pbm * kp + 1);
+	lay.Add(&d_part, pbm * pgh::kGlmSparseMultiParts * ne);
+	lay.Add(&d_gram, pbm * ne);
+	lay.Add(&d_ny, pbm);
+	ch.AddTo(lay, plan.pb_max, plan.chunk, kp, k);
+	void *scratch = nullptr;
+	PGH_HIP(PghThreadScratch(lay.total, st, &scratch), "glm_sparse_multi scratch");
+	lay.Bind(scratch);
+	h_my.resize(plan.pb_max);
+	h_mz.resize(static_cast<size_t>(plan.pb_max) * kp + 1);
+	h_ny.resize(plan.pb_max);
+	return PGH_OK;
+}
+
+// sg.hz (and hz_raw): the covariates as they are
+int GlmSparseMultiCall::UploadCovariates(const GlmStaged &sg) {
+	staged = &sg;
+	if (!subset) {
+		d_zr0 = d_z0;
+	}
+	if (kp) {
+		PGH_HIP(hipMemcpyAsync(d_z0, sg.hz.data(), 8ull * sg.hz.size(), hipMemcpyHostToDevice, st),
+		        "glm_sparse_multi covariate upload");
+	}
+	if (sg.raw && kp) {
+		PGH_HIP(hipMemcpyAsync(d_zr0, sg.hz_raw.data(), 8ull * sg.hz_raw.size(), hipMemcpyHostToDevice, st),
+		        "glm_sparse_multi covariate upload (raw order)");
+	}
+	return PGH_OK;
+}
+
+// The block of the phenotypes b0 .. b0 + pb: per phenotype |S|, its mean and the covariates' means over S, each summed
+// in sample order as GlmStage sums them; then the value block and the whole-call Grams.  Every upload of the previous
+// block has completed: each chunk ends with a stream synchronisation.
+int GlmSparseMultiCall::StageBlock(uint32_t b0, uint32_t pb) {
+	const double *yb = phenotypes + static_cast<size_t>(b0) * n_out;
+	const double *hz = staged->hz.data();
+	for (uint32_t j = 0; j < pb; j++) {
+		const double *y = yb + static_cast<size_t>(j) * n_out;
+		uint32_t n_y = 0;
+		for (uint32_t i = 0; i < n_out; i++) {
+			n_y += std::isnan(y[i]) ? 0u : 1u;
+		}
+		h_ny[j] = n_y;
+		h_my[j] = n_y ? GlmMean(y, n_out, n_y) : 0.0;
+		double *mz = h_mz.data() + static_cast<size_t>(j) * kp;
+		std::fill_n(mz, kp, 0.0);
+		if (n_y) {
+			for (uint32_t i = 0; i < n_out; i++) {
+				if (!std::isnan(y[i])) {
+					for (uint32_t t = 0; t < k; t++) {
+						mz[t] += hz[static_cast<size_t>(i) * kp + t];
+					}
+				}
+			}
+			for (uint32_t t = 0; t < k; t++) {
+				mz[t] /= n_y;
+			}
+		}
+	}
+	PGH_HIP(hipMemcpyAsync(d_yb, yb, 8ull * n_out * pb, hipMemcpyHostToDevice, st), "glm_sparse_multi phenotype upload");
+	PGH_HIP(hipMemcpyAsync(d_my, h_my.data(), 8ull * pb, hipMemcpyHostToDevice, st), "glm_sparse_multi mean upload");
+	if (kp) {
+		PGH_HIP(hipMemcpyAsync(d_mz, h_mz.data(), 8ull * pb * kp, hipMemcpyHostToDevice, st),
+		        "glm_sparse_multi covariate mean upload");
+	}
+	PGH_HIP(hipMemcpyAsync(d_ny, h_ny.data(), 4ull * pb, hipMemcpyHostToDevice, st), "glm_sparse_multi count upload");
+	PGH_HIP(pgh::LaunchGlmSparseMultiValues(n_raw, n_out, d_sel, d_yb, d_my, pb, d_yv, st), "glm_sparse_multi value kernels");
+	PGH_HIP(pgh::LaunchGlmSparseMultiGram(n_raw, d_yv, pb, d_zr0, d_mz, kp, k, d_part, d_gram, st),
+	        "glm_sparse_multi gram kernels");
+	return PGH_OK;
+}
+
+// The variants c0 .. c0 + nv - 1 of the range against the staged block; the rows [nv][pb] go into out[.][b0 .. b0 + pb).
+int GlmSparseMultiCall::RunChunk(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t nv, pgh_glm_row *out) {
+	const uint32_t l0 = v_begin + c0 - ds->v_begin;
+	PGH_HIP(pgh::LaunchGlmSparseMulti(ds->Sparse(), l0, nv, d_yv, d_ny, pb, d_zr0, d_mz, kp, k, d_gram, ch.sums, ch.nlist,
+	                                  ch.corr, ch.rows, st),
+	        "glm_sparse_multi kernels");
+	PGH_HIP(hipMemcpy2DAsync(out + static_cast<size_t>(c0) * n_pheno + b0, sizeof(pgh_glm_row) * n_pheno, ch.rows,
+	                         sizeof(pgh_glm_row) * pb, sizeof(pgh_glm_row) * pb, nv, hipMemcpyDeviceToHost, st),
+	        "glm_sparse_multi rows copy");
+	PGH_HIP(hipStreamSynchronize(st), "glm_sparse_multi sync");
+	return PGH_OK;
+}
+
 int GlmScoreMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end, uint32_t n_pheno,
                      const double *phenotypes, uint32_t k, const double *covariates, pgh_glm_row *out, char *errbuf,
                      const GlmScoreFollowUp &fu) {
@@ -1757,6 +1917,13 @@ int GlmScoreSparseMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint
 	PGH_ENTER(ds);
 	GlmScoreSparseMultiCall c {{ds, subset, v_begin, v_end - v_begin, n_pheno, k, phenotypes, covariates, fu, errbuf,
 	                            "glm_score_sparse_multi", false}};
+	return GlmScoreBlocksRun(c, out);
+}
+
+int GlmSparseMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end, uint32_t n_pheno,
+                      const double *phenotypes, uint32_t k, const double *covariates, pgh_glm_row *out, char *errbuf) {
+	PGH_ENTER(ds);
+	GlmSparseMultiCall c {ds, subset, v_begin, v_end - v_begin, n_pheno, k, phenotypes, covariates, errbuf};
 	return GlmScoreBlocksRun(c, out);
 }
 
@@ -1784,6 +1951,18 @@ extern "C" int pgh_glm_score_sparse_firth(const pgh_dataset *ds, const pgh_subse
 	PGH_TRY(GlmCheckFirth(firth_cutoff, firth, errbuf));
 	const GlmScoreFollowUp fu = {GlmScoreFollowUp::kFirth, firth_cutoff, nullptr, nullptr, firth};
 	return GlmScoreSparseEntry(ds, subset, v_begin, v_end, phenotype, n_covar, covariates, out, fu, errbuf);
+}
+
+extern "C" int pgh_glm_sparse_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                                    uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
+                                    pgh_glm_row *out, char *errbuf) {
+	PGH_ONE_DEVICE(ds);
+	PGH_SPARSE_ROWS(ds);
+	PGH_TRY(GlmCheckCommon(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, PGH_GLM_LINEAR, out, errbuf));
+	if (v_end == v_begin) {
+		return PGH_OK;
+	}
+	return GlmSparseMultiOne(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, errbuf);
 }
 
 namespace {

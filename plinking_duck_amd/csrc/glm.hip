@@ -13,6 +13,7 @@
 // variant's sums do not depend on its place in a tile, chunk or shard.
 #include "device_utils.hpp"
 #include "glm.hpp"
+#include "glm_linear_solve.hpp"
 #include "glm_math.hpp"
 #include "glm_team.hpp"
 
@@ -26,7 +27,7 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
-constexpr int kMaxP = 22; // intercept + genotype + PGH_GLM_MAX_COVAR
+constexpr int kMaxP = kGlmSolveMaxP;
 
 __device__ inline double GlmValue(const GlmX &g, uint32_t v, uint32_t i) {
 	const int32_t s = g.slot ? g.slot[v] : -1;
@@ -58,10 +59,6 @@ __device__ inline void BlockSums(const double (&acc)[NE], double *lds, double *o
 		}
 		out[e] = s;
 	}
-}
-
-__device__ inline int PackIdx(int a, int b, int q) { // a <= b < q
-	return a * q - a * (a - 1) / 2 + (b - a);
 }
 
 // ---------------------------------------------------------------------------
@@ -178,14 +175,6 @@ __global__ void __launch_bounds__(kBlock) GlmGramKernel(GlmX g, int per_variant,
 // linear solve: one thread per variant
 // ---------------------------------------------------------------------------
 
-__device__ inline void SetRowNull(pgh_glm_row &r) {
-	r.beta = r.se = r.stat = r.p = r.a1_freq = NAN;
-	r.obs_ct = 0;
-	r.errcode = PGH_GLM_OK;
-	r.firth = 0;
-	r.pad[0] = r.pad[1] = 0;
-}
-
 // FLAGGED (pgh_burden_sparse): x is not on the dosage grid, so CONST_ALLELE is decided by the caller (x_const[v] != 0)
 // and the correction Gram is zero (corr is not read).  FLAGGED == false is the kernel of pgh_glm and pgh_glm_sparse.
 template <bool FLAGGED>
@@ -198,79 +187,12 @@ __global__ void GlmLinearSolveKernel(uint32_t nv, const double *__restrict__ sum
 	}
 	const uint32_t ns = kp + 4, q = k + 2, ne = q * (q + 1) / 2;
 	const double *s = sums + static_cast<uint64_t>(v) * ns;
-	const double *c = corr + static_cast<uint64_t>(v) * ne;
-	pgh_glm_row r;
-	SetRowNull(r);
-	const double n = s[0];
-	const int p = static_cast<int>(k) + 2;
-	r.obs_ct = static_cast<uint32_t>(n);
-	if (n < p + 1) {
-		r.errcode = PGH_GLM_TOO_FEW_SAMPLES;
-		rows[v] = r;
-		return;
-	}
-	r.a1_freq = s[1] / (2.0 * n);
-	// with no covariates the reference takes its one-pass closed form, and its test with it
-	bool constant;
 	if constexpr (FLAGGED) {
-		constant = x_const[v] != 0;
+		rows[v] = GlmLinearSolveRow<true>(s, k, [&](int e) { return gram[e]; }, x_const[v] != 0);
 	} else {
-		constant = k ? GlmConstant(n, s[1], s[2]) : s[2] - s[1] * s[1] / n < 1e-20;
+		const double *c = corr + static_cast<uint64_t>(v) * ne;
+		rows[v] = GlmLinearSolveRow<false>(s, k, [&](int e) { return gram[e] - c[e]; }, false);
 	}
-	if (constant) {
-		r.errcode = PGH_GLM_CONST_ALLELE;
-		rows[v] = r;
-		return;
-	}
-	// augmented matrix, order [1, z_1..z_k, x, y]; u = [1, z, y] is the Gram's order
-	constexpr int M = kMaxP + 1;
-	double a[M * M];
-	const int xi = p - 1, yi = p;
-	auto uidx = [&](int j) { return j <= static_cast<int>(k) ? j : yi; }; // u index -> matrix index
-	for (int ua = 0; ua < static_cast<int>(q); ua++) {
-		for (int ub = ua; ub < static_cast<int>(q); ub++) {
-			const int e = PackIdx(ua, ub, q);
-			const double val = FLAGGED ? gram[e] : gram[e] - c[e];
-			const int ia = uidx(ua), ib = uidx(ub);
-			a[ib * M + ia] = val; // lower triangle: ib >= ia
-		}
-	}
-	a[xi * M + 0] = s[1];
-	for (int j = 0; j < static_cast<int>(k); j++) {
-		a[xi * M + 1 + j] = s[4 + j];
-	}
-	a[xi * M + xi] = s[2];
-	a[yi * M + xi] = s[3];
-	if (!GlmCholesky(a, p, M, k ? 1e-10 : 0.0, nullptr)) {
-		r.errcode = PGH_GLM_SINGULAR_MATRIX;
-		rows[v] = r;
-		return;
-	}
-	double rss = a[yi * M + yi];
-	for (int j = 0; j < p; j++) {
-		double l = a[yi * M + j];
-		for (int t = 0; t < j; t++) {
-			l -= a[yi * M + t] * a[j * M + t];
-		}
-		l /= a[j * M + j];
-		a[yi * M + j] = l;
-		rss -= l * l;
-	}
-	rss = rss < 0.0 ? 0.0 : rss;
-	const double lxx = a[xi * M + xi];
-	const double df = n - p;
-	const double se2 = rss / df / (lxx * lxx);
-	const double beta = a[yi * M + xi] / lxx;
-	r.beta = beta;
-	if (se2 < 1e-30) {
-		r.errcode = PGH_GLM_ZERO_VARIANCE;
-		rows[v] = r;
-		return;
-	}
-	r.se = sqrt(se2);
-	r.stat = beta / r.se;
-	r.p = GlmPFromT(r.stat, df);
-	rows[v] = r;
 }
 
 // ---------------------------------------------------------------------------

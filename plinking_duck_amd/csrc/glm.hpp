@@ -133,6 +133,30 @@ hipError_t LaunchGlmSparse(const SparseView &sv, uint32_t v_first, uint32_t nv, 
                            uint32_t kp, uint32_t k, uint32_t n_y, const double *gram, double *sums, double *corr,
                            hipStream_t stream);
 
+// ---- pgh_glm_sparse_multi (glm_sparse_multi.hip): the linear fit from a sparse row's entries for a block of
+// phenotypes ----
+// At most kGlmSparseMultiPb phenotypes share a value block and a walk of the entries.  No number depends on the block's
+// size, on a phenotype's place in it or on the chunk.
+constexpr uint32_t kGlmSparseMultiPb = 64;
+// Partial sums per entry of a whole-call Gram: a fixed shape, so G_j is a function of its phenotype, z and the subset.
+constexpr uint32_t kGlmSparseMultiParts = 64;
+// The value block of pb phenotypes: yv[s][j] = yb[j][i] - my[j] for the subset's samples s = sel[i] (sel == null: i),
+// NaN everywhere else (and where yb is NaN); sample_ct x pb doubles.  yb: pb x n_out doubles, phenotype-major.
+hipError_t LaunchGlmSparseMultiValues(uint32_t sample_ct, uint32_t n_out, const uint32_t *sel, const double *yb,
+                                      const double *my, uint32_t pb, double *yv, hipStream_t stream);
+// gram[j]: the packed upper Gram of u = [1, z - mz[j], yv[.][j]] ((k+2)(k+3)/2 entries) over the samples with a value
+// of j.  z: sample_ct x kp doubles, raw sample-major, uncentred; mz: pb x kp means.  part: pb x kGlmSparseMultiParts x
+// (entries) doubles of scratch.
+hipError_t LaunchGlmSparseMultiGram(uint32_t sample_ct, const double *yv, uint32_t pb, const double *z, const double *mz,
+                                    uint32_t kp, uint32_t k, double *part, double *gram, hipStream_t stream);
+// For the rows v_first + i (i < nv) of `sv`, sparse or held in the dense form, and the block's phenotypes j < pb:
+// out[i][j], the row of GlmLinearSolveKernel<false>.  n_y[j]: the samples with a value of j.  Scratch: sums
+// nv x pb x (kp + 4), corr nv x pb x (entries of a Gram) doubles, nlist nv words.
+hipError_t LaunchGlmSparseMulti(const SparseView &sv, uint32_t v_first, uint32_t nv, const double *yv,
+                                const uint32_t *n_y, uint32_t pb, const double *z, const double *mz, uint32_t kp,
+                                uint32_t k, const double *gram, double *sums, uint32_t *nlist, double *corr,
+                                pgh_glm_row *out, hipStream_t stream);
+
 // ---- pgh_glm_score_sparse (glm_score_sparse.hip): the logistic score test from a sparse row's entries ----
 // The null model y ~ Zt = [1, z_1..z_k] and its packed sums hg: H = sum_S w Zt Zt' ((k+1)(k+2)/2 entries, row-major
 // upper) followed by g_S = sum_S Zt r (k + 1 entries), S being the samples with a phenotype.

@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = [
     "pgh_reader_unpack_start", "pgh_reader_unpack_wait", "pgh_get_2bit", "pgh_get_counts", "pgh_get_missingness", "pgh_get_int8", "pgh_get_dosage_f64", "pgh_get_phased",
     "pgh_tally_start", "pgh_tally_request", "pgh_tally_wait", "pgh_tally_counts", "pgh_tally_hwe_lnp",
     "pgh_tally_sample_missing", "pgh_tally_destroy", "pgh_tally_passes_started", "pgh_host_alloc", "pgh_host_free", "pgh_trim_device_cache",
-    "pgh_reader_error", "pgh_open_sparse", "pgh_get_sparse_info", "pgh_sparse_opens_started", "pgh_glm", "pgh_glm_multi", "pgh_glm_sparse", "pgh_glm_score_sparse", "pgh_glm_score_multi", "pgh_glm_score_sparse_spa", "pgh_glm_score_multi_spa", "pgh_glm_score_multi_firth", "pgh_glm_score_sparse_firth", "pgh_glm_score_sparse_multi", "pgh_glm_score_sparse_multi_spa", "pgh_glm_score_sparse_multi_firth", "pgh_burden_sparse", "pgh_skat_sparse", "pgh_skat_p_from_lambda", "pgh_symmetric_eigenvalues", "pgh_score_sparse", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
+    "pgh_reader_error", "pgh_open_sparse", "pgh_get_sparse_info", "pgh_sparse_opens_started", "pgh_glm", "pgh_glm_multi", "pgh_glm_sparse", "pgh_glm_score_sparse", "pgh_glm_score_multi", "pgh_glm_score_sparse_spa", "pgh_glm_score_multi_spa", "pgh_glm_score_multi_firth", "pgh_glm_score_sparse_firth", "pgh_glm_score_sparse_multi", "pgh_glm_sparse_multi", "pgh_glm_score_sparse_multi_spa", "pgh_glm_score_sparse_multi_firth", "pgh_burden_sparse", "pgh_skat_sparse", "pgh_skat_p_from_lambda", "pgh_symmetric_eigenvalues", "pgh_score_sparse", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
     "pgh_king_counts", "pgh_king_table", "pgh_king_kinship",
     "pgh_ld_window_sums", "pgh_ld_prune", "pgh_ld_exceeds", "pgh_ld_scores", "pgh_ld_r2",
     "pgh_grm", "pgh_grm_standardize",
@@ -254,6 +254,7 @@ def _load():
         "pgh_glm_score_sparse": (C.c_int, [vp, vp, u32, u32, vp, u32, vp, vp, cp]),
         "pgh_glm_score_multi": (C.c_int, [vp, vp, u32, u32, u32, vp, u32, vp, vp, cp]),
         "pgh_glm_score_sparse_multi": (C.c_int, [vp, vp, u32, u32, u32, vp, u32, vp, vp, cp]),
+        "pgh_glm_sparse_multi": (C.c_int, [vp, vp, u32, u32, u32, vp, u32, vp, vp, cp]),
         "pgh_glm_score_sparse_spa": (C.c_int, [vp, vp, u32, u32, vp, u32, vp, C.c_double, vp, vp, vp, cp]),
         "pgh_glm_score_multi_spa": (C.c_int, [vp, vp, u32, u32, u32, vp, u32, vp, C.c_double, vp, vp, vp, cp]),
         "pgh_glm_score_sparse_multi_spa": (C.c_int, [vp, vp, u32, u32, u32, vp, u32, vp, C.c_double, vp, vp, vp, cp]),
@@ -988,6 +989,19 @@ class Dataset:
             "errcode": np.array([GLM_ERRCODES[c] for c in rows["errcode"]], dtype=object),
             "firth": rows["firth"].astype(bool),
         }
+
+    def glm_sparse_multi(self, phenotypes, covariates=None, v_begin: int | None = None, v_end: int | None = None,
+                         subset: Subset | None = None) -> dict:
+        """pgh_glm_sparse_multi: glm_sparse() for every row of phenotypes (P x n_out, NaN = missing, each row with its
+        own missing-value pattern) in one walk of the variants' entries per block of 64 phenotypes.  Returns
+        glm_multi()'s dict of (V, P) arrays: [v, p] is glm_sparse()'s row of phenotype p alone for variant v_begin + v,
+        to rounding."""
+        v0, v1, y, z = Dataset._score_multi_args(self, phenotypes, covariates, v_begin, v_end, subset)
+        rows = np.zeros((max(0, v1 - v0), y.shape[0]), dtype=GLM_ROW_DTYPE)
+        eb = _errbuf()
+        _check(_lib.pgh_glm_sparse_multi(self._h, subset._h if subset else None, v0, v1, y.shape[0], _ptr(y), z.shape[0],
+                                         _ptr(z) if z.size else None, _ptr(rows), eb), eb)
+        return Dataset._glm_multi_rows_dict(rows)
 
     def _score_sparse_args(self, phenotype, covariates, v_begin, v_end, subset):
         """(v0, v1, y, z) of the score-test calls, after their shape checks."""
