@@ -704,11 +704,36 @@ int pgh_glm_score_sparse(const pgh_dataset *ds, const pgh_subset *subset, uint32
  * Saddlepoint p-values over this route: pgh_glm_score_multi_spa.  Approximate Firth estimates over this route:
  * pgh_glm_score_multi_firth (from carrier lists: pgh_glm_score_sparse_firth).  Many phenotypes over a sparse-resident
  * dataset: pgh_glm_score_sparse_multi, with saddlepoint p-values pgh_glm_score_sparse_multi_spa, with approximate Firth
- * estimates pgh_glm_score_sparse_multi_firth.  Not offered: a Firth-penalised null fit, Firth and saddlepoint in one
- * call, dosage tracks, shard groups, a table function. */
+ * estimates pgh_glm_score_sparse_multi_firth.  A dataset with dosage tracks: pgh_glm_score_multi_dosage.  Not offered:
+ * a Firth-penalised null fit, Firth and saddlepoint in one call, shard groups, a table function. */
 int pgh_glm_score_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                         uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
                         pgh_glm_row *out, char *errbuf);
+/* pgh_glm_score_multi over a dense-resident dataset that may hold DOSAGE TRACKS (imputed panels).  Arguments, argument
+ * checks, error texts, the layout of `out` and the refusals are pgh_glm_score_multi's, except that a dataset whose
+ * pgh_info.dosage_variant_ct is not 0 is accepted.  On any refusal `out` is untouched; v_begin == v_end is PGH_OK.
+ *
+ * Row contract.  The row of (variant, phenotype) is the row of pgh_glm_score_sparse's contract with d = x, as
+ * pgh_glm_score_multi's is, under pgh_glm's genotype rule (pgh_dosage_unpack's): for a variant with a track,
+ * x_i = value / 16384 where sample i has an explicit dosage and the ALT count of its call otherwise; M = the samples of
+ * S with neither a dosage nor a call; N = S \ M; A = sum_N w x^2.  A variant without a track has x = its calls.  The
+ * null model, its stopping rule, the pivot rule, the order of the decisions and the NaN fields are unchanged; firth is 0.
+ * Values lie on the 2^-14 grid, so n, sum x and sum x^2 over N are exact, and obs_ct, a1_freq, TOO_FEW_SAMPLES and
+ * CONST_ALLELE equal pgh_glm's with model = PGH_GLM_LOGISTIC over the same file, bit for bit, a track that is constant
+ * at an off-integer value included.  sum x^2 is exact only while sample_ct < 2^23 (8,388,608).
+ * A variant without a track, whatever its neighbours carry, and a variant whose track restates its calls (value =
+ * 16384 x call wherever there is a call, nothing elsewhere) get pgh_glm_score_multi's row for the same calls in a file
+ * without tracks, bit for bit; a dataset without any track gets pgh_glm_score_multi's bytes.
+ *
+ * A row is a function of its variant's calls and track, its own phenotype, the covariates and the subset only: not of
+ * the other phenotypes or its place among them, of v_begin, the variant chunk, the phenotype block, which other variants
+ * carry tracks, the window the dataset was opened with or PGH_GLM_SCORE_SCRATCH_BYTES (which here also holds 144 bytes
+ * per 64 samples for every variant in flight), and the same call returns the same bytes every time.
+ * Not offered: saddlepoint and Firth follow-ups over tracks (pgh_glm_score_multi_spa's and pgh_glm_score_multi_firth's
+ * walks read 2-bit rows), shard groups, a table function. */
+int pgh_glm_score_multi_dosage(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                               uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
+                               pgh_glm_row *out, char *errbuf);
 /* The logistic score test of every variant of [v_begin, v_end) of a SPARSE-RESIDENT dataset (pgh_open_sparse) for
  * n_pheno case/control phenotypes in one call: one null fit per phenotype, then one walk of the variants' entries per
  * block of at most 64 phenotypes, in which an entry's word and covariate row are read once for the block.  The
@@ -790,7 +815,8 @@ int pgh_glm_score_sparse_spa(const pgh_dataset *ds, const pgh_subset *subset, ui
  * addition spa_cutoff must be at least 0.1 (+infinity: never apply it; NaN or a smaller value is PGH_ERR_ARG,
  * "spa_cutoff must be at least 0.1"), and p_spa and spa_state must not be NULL ("null p_spa or spa_state"); they have
  * out's layout, element (v - v_begin) * n_pheno + p.  On any error all three outputs are untouched.  The refusals are the dense route's: a
- * sparse-resident dataset, a shard group, a dataset with dosage tracks.
+ * sparse-resident dataset, a shard group, a dataset with dosage tracks (pgh_glm_score_multi_dosage gives such a
+ * dataset's score rows, without the saddlepoint: this entry's walk reads 2-bit rows).
  *
  * out is pgh_glm_score_multi's result for the same arguments bit for bit; its p stays the normal p-value.  spa_state
  * and p_spa mean what they mean for pgh_glm_score_sparse_spa: 0 = not applied (the row is not fitted: p_spa NaN; or
@@ -862,7 +888,8 @@ typedef struct pgh_glm_firth_row {
  * phenotype) row of the dense route beyond a cutoff (the "approximate Firth" of Mbatchou et al. 2021: the covariate
  * effects are held fixed at the null fit and only the variant's own coefficient is estimated, under Firth's penalty).
  * Arguments, argument checks, error texts and refusals are pgh_glm_score_multi's: a sparse-resident dataset, a shard
- * group, a dataset with dosage tracks, 0/1 phenotypes, cases and controls.  In addition firth_cutoff must be at least
+ * group, a dataset with dosage tracks (pgh_glm_score_multi_dosage gives such a dataset's score rows, without the Firth
+ * estimate: this entry's walk reads 2-bit rows), 0/1 phenotypes, cases and controls.  In addition firth_cutoff must be at least
  * 0.1 (+infinity: never apply it; NaN or a smaller value is PGH_ERR_ARG, "firth_cutoff must be at least 0.1"), and
  * firth must not be NULL ("null firth"); it has out's layout, element (v - v_begin) * n_pheno + p.  On any error both
  * outputs are untouched.  v_begin == v_end is PGH_OK.

@@ -1283,8 +1283,9 @@ struct GlmScoreMultiPlan {
 	uint32_t chunk = 0;    // variants of a chunk
 	uint64_t stash_bytes = 0;
 };
+// extra_variant_bytes: what a chunk variant takes besides (pgh_glm_score_multi_dosage's expanded rows).
 GlmScoreMultiPlan GlmScoreMultiPlanFor(uint32_t n_raw, uint32_t n_pheno, uint32_t k, uint32_t nv_all, uint64_t budget,
-                                       int cus, GlmScoreFollowUp::Kind kind) {
+                                       int cus, GlmScoreFollowUp::Kind kind, uint64_t extra_variant_bytes = 0) {
 	const uint32_t kp = pgh::GlmPadCovar(k);
 	const uint64_t n_pad = 64ull * ((static_cast<uint64_t>(n_raw) + 63) / 64), mask_words = n_pad / 16;
 	const auto block_bytes = [&](uint32_t pb) {
@@ -1306,7 +1307,8 @@ GlmScoreMultiPlan GlmScoreMultiPlanFor(uint32_t n_raw, uint32_t n_pheno, uint32_
 		plan.stash_bytes = per_group * plan.n_groups;
 		left = left > plan.stash_bytes ? left - plan.stash_bytes : 0;
 	}
-	plan.chunk = static_cast<uint32_t>(std::min<uint64_t>(nv_most, std::max<uint64_t>(1, left / one_variant.payload)));
+	plan.chunk = static_cast<uint32_t>(
+	    std::min<uint64_t>(nv_most, std::max<uint64_t>(1, left / (one_variant.payload + extra_variant_bytes))));
 	return plan;
 }
 
@@ -1421,7 +1423,8 @@ struct GlmScoreBlockCall {
 	int FitPhenotype(uint32_t b0, uint32_t j);
 	int SolveRows(uint32_t pb, uint32_t nv);
 	template <class T>
-	void Scatter(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t nv, const std::vector<T> &from, T *to) const;
+	void Scatter(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t nv, const std::vector<T> &from, T *to,
+	             const uint32_t *pos = nullptr) const;
 };
 
 void GlmScoreBlockCall::PatternOrder() {
@@ -1541,22 +1544,31 @@ int GlmScoreBlockCall::SolveRows(uint32_t pb, uint32_t nv) {
 }
 
 // from[block phenotype j][chunk variant i] into the caller's [variant][phenotype], the phenotypes in the caller's order.
+// pos (may be null): row i belongs to variant c0 + pos[i] of the range instead of c0 + i.
 template <class T>
-void GlmScoreBlockCall::Scatter(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t nv, const std::vector<T> &from,
-                                T *to) const {
+void GlmScoreBlockCall::Scatter(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t nv, const std::vector<T> &from, T *to,
+                                const uint32_t *pos) const {
 	for (uint32_t i = 0; i < nv; i++) {
 		for (uint32_t j = 0; j < pb; j++) {
-			to[static_cast<size_t>(c0 + i) * n_pheno + order[b0 + j]] = from[static_cast<size_t>(j) * nv + i];
+			to[static_cast<size_t>(c0 + (pos ? pos[i] : i)) * n_pheno + order[b0 + j]] = from[static_cast<size_t>(j) * nv + i];
 		}
 	}
 }
 
 // One call of pgh_glm_score_multi* on one dense-resident dataset.  Each fit's r and w go straight into the phenotype's
 // columns of the block (glm_score_dense.hip).
+// tracks (pgh_glm_score_multi_dosage over a dataset that holds dosage tracks): a chunk's variants without a track go
+// through the same kernels, from the first such variant to the last; the ones with a track are listed, expanded into
+// d_u16 / d_eff and contracted by glm_score_dense_dosage.hip, and their rows replace what the first pass left for them.
 struct GlmScoreMultiCall : GlmScoreBlockCall {
 	double *d_b;
 	uint32_t *d_mask;
 	uint8_t *d_stash;
+	bool tracks = false;
+	uint16_t *d_u16;
+	uint8_t *d_eff;
+	uint32_t *d_tlist;
+	std::vector<uint32_t> tlist, tpos; // the chunk's variants with a track: resident rows, places in the chunk
 	std::vector<double> hp_spa;
 	std::vector<uint8_t> hstate;
 	std::vector<pgh_glm_firth_row> hfirth;
@@ -1564,6 +1576,8 @@ struct GlmScoreMultiCall : GlmScoreBlockCall {
 	int Prepare();
 	int StageBlock(uint32_t b0, uint32_t pb);
 	int RunChunk(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t nv, pgh_glm_row *out);
+	int RunHard(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t nv, pgh_glm_row *out);
+	int RunTracks(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t nt, pgh_glm_row *out);
 };
 
 // The pattern order, the plan, the scratch block and the host buffers.
@@ -1573,13 +1587,21 @@ int GlmScoreMultiCall::Prepare() {
 	if (fu.kind != GlmScoreFollowUp::kNone) {
 		PGH_TRY(DeviceCus(&cus, "glm_score_multi stash", errbuf));
 	}
-	plan = GlmScoreMultiPlanFor(n_raw, n_pheno, k, nv_all, EnvBytes(kGlmScoreScratchEnv, kGlmScoreScratchBytes), cus, fu.kind);
+	// every chunk variant is charged its expanded rows and its list entry, as if each had a track
+	const uint64_t row_bytes = tracks ? pgh::GlmScoreDosageRowBytes(n_raw) : 0;
+	plan = GlmScoreMultiPlanFor(n_raw, n_pheno, k, nv_all, EnvBytes(kGlmScoreScratchEnv, kGlmScoreScratchBytes), cus, fu.kind,
+	                            tracks ? row_bytes + 4 : 0);
 
 	ScratchLayout lay;
 	AddShared(lay);
 	lay.Add(&d_mask, plan.pb_max * mask_words);
 	lay.Add(&d_b, n_pad * pgh::GlmScoreDenseLayout(plan.pb_max, k).ld);
 	ch.AddTo(lay, plan.pb_max, plan.chunk, kp, k, fu.kind);
+	lay.Add(&d_u16, n_pad * plan.chunk, tracks);
+	lay.Add(&d_eff, n_pad / 4 * plan.chunk, tracks);
+	lay.Add(&d_tlist, plan.chunk, tracks);
+	tlist.resize(tracks ? plan.chunk : 0);
+	tpos.resize(tracks ? plan.chunk : 0);
 	lay.Add(&d_stash, plan.stash_bytes, fu.kind != GlmScoreFollowUp::kNone);
 	void *scratch = nullptr;
 	PGH_HIP(PghThreadScratch(lay.total, st, &scratch), "glm_score_multi scratch");
@@ -1607,9 +1629,42 @@ int GlmScoreMultiCall::StageBlock(uint32_t b0, uint32_t pb) {
 	return PGH_OK;
 }
 
-// The variants c0 .. c0 + nv - 1 of the range against the staged block: the launches, the copies, and the scatter
-// into the caller's arrays.
+// The variants c0 .. c0 + nv - 1 of the range against the staged block.
 int GlmScoreMultiCall::RunChunk(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t nv, pgh_glm_row *out) {
+	if (!tracks) {
+		return RunHard(b0, pb, c0, nv, out);
+	}
+	const uint32_t l0 = v_begin + c0 - ds->v_begin;
+	uint32_t nt = 0, hard_lo = nv, hard_hi = 0;
+	for (uint32_t i = 0; i < nv; i++) {
+		if (ds->dos_row_of[l0 + i] >= 0) {
+			tlist[nt] = l0 + i;
+			tpos[nt++] = i;
+		} else {
+			hard_lo = std::min(hard_lo, i);
+			hard_hi = i + 1;
+		}
+	}
+	if (hard_hi > hard_lo) {
+		PGH_TRY(RunHard(b0, pb, c0 + hard_lo, hard_hi - hard_lo, out));
+	}
+	return nt ? RunTracks(b0, pb, c0, nt, out) : PGH_OK;
+}
+
+// The chunk's nt listed variants, all with a track: the launches, the copy, and the scatter to their places.
+int GlmScoreMultiCall::RunTracks(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t nt, pgh_glm_row *out) {
+	PGH_HIP(hipMemcpyAsync(d_tlist, tlist.data(), 4ull * nt, hipMemcpyHostToDevice, st), "glm_score_multi_dosage list upload");
+	PGH_HIP(pgh::LaunchGlmScoreDenseDosage(ds->View(), ds->Dosage(), d_tlist, nt, d_mask, d_ny, pb, d_b, d_zr0, d_mz, kp, k,
+	                                       d_hg, d_u16, d_eff, ch.sums, ch.nmiss, ch.hgn, st),
+	        "glm_score_multi_dosage kernels");
+	PGH_TRY(SolveRows(pb, nt));
+	PGH_HIP(hipStreamSynchronize(st), "glm_score_multi_dosage sync");
+	Scatter(b0, pb, c0, nt, hrows, out, tpos.data());
+	return PGH_OK;
+}
+
+// nv variants from c0 of the range by their calls: the launches, the copies, and the scatter into the caller's arrays.
+int GlmScoreMultiCall::RunHard(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t nv, pgh_glm_row *out) {
 	const uint32_t l0 = v_begin + c0 - ds->v_begin;
 	const size_t n_rows = static_cast<size_t>(nv) * pb;
 	PGH_HIP(pgh::LaunchGlmScoreDense(ds->View(), l0, nv, d_mask, d_ny, pb, d_b, d_zr0, d_mz, kp, k, d_hg, ch.sums, ch.nmiss,
@@ -1908,6 +1963,7 @@ int GlmScoreMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v
 	PGH_ENTER(ds);
 	GlmScoreMultiCall c {{ds, subset, v_begin, v_end - v_begin, n_pheno, k, phenotypes, covariates, fu, errbuf,
 	                      "glm_score_multi", true}};
+	c.tracks = ds->dos_rows != 0; // pgh_glm_score_multi_dosage alone lets such a dataset through
 	return GlmScoreBlocksRun(c, out);
 }
 
@@ -1981,15 +2037,15 @@ int GlmCheckBinaryEach(const double *phenotypes, uint32_t n_pheno, uint32_t n_ou
 }
 
 // pgh_glm_score_multi, pgh_glm_score_multi_spa and pgh_glm_score_multi_firth after the latter two's own argument
-// checks.
+// checks, and pgh_glm_score_multi_dosage (with_tracks: a dataset that holds dosage tracks is accepted).
 int GlmScoreMultiEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                        uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
-                       pgh_glm_row *out, const GlmScoreFollowUp &fu, char *errbuf) {
+                       pgh_glm_row *out, const GlmScoreFollowUp &fu, char *errbuf, bool with_tracks = false) {
 	PGH_ONE_DEVICE(ds);
 	PGH_DENSE_ROWS(ds);
 	PGH_TRY(GlmCheckCommon(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, PGH_GLM_LOGISTIC, out,
 	                       errbuf));
-	if (ds->dos_rows) {
+	if (ds->dos_rows && !with_tracks) {
 		SetErr(errbuf, "hardcalls only: the dataset holds " + std::to_string(ds->dos_rows) + " dosage tracks");
 		return PGH_ERR_ARG;
 	}
@@ -2050,6 +2106,12 @@ extern "C" int pgh_glm_score_multi(const pgh_dataset *ds, const pgh_subset *subs
                                    uint32_t n_pheno, const double *phenotypes, uint32_t n_covar,
                                    const double *covariates, pgh_glm_row *out, char *errbuf) {
 	return GlmScoreMultiEntry(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, {}, errbuf);
+}
+
+extern "C" int pgh_glm_score_multi_dosage(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin,
+                                          uint32_t v_end, uint32_t n_pheno, const double *phenotypes, uint32_t n_covar,
+                                          const double *covariates, pgh_glm_row *out, char *errbuf) {
+	return GlmScoreMultiEntry(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, {}, errbuf, true);
 }
 
 extern "C" int pgh_glm_score_multi_spa(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin,

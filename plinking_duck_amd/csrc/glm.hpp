@@ -221,6 +221,25 @@ hipError_t LaunchGlmScoreDense(const RowView &view, uint32_t v0, uint32_t nv, co
                                uint32_t pb, const double *b, const double *z0, const double *mz, uint32_t kp,
                                uint32_t k, const double *hg, double *sums, uint32_t *nmiss, double *hgn,
                                hipStream_t stream);
+// LaunchGlmScoreDense's last step alone: hgn[p][i] from the missing calls (code 3) of the rows v0 + i of `view` and
+// nmiss[p][i] = how many of them lie in S_p.  The other arguments are LaunchGlmScoreDense's.
+hipError_t LaunchGlmScoreDenseCorr(const RowView &view, uint32_t v0, uint32_t nv, const uint32_t *mask,
+                                   const uint32_t *nmiss, uint32_t pb, const double *b, const double *z0,
+                                   const double *mz, uint32_t kp, uint32_t k, const double *hg, double *hgn,
+                                   hipStream_t stream);
+
+// ---- pgh_glm_score_multi_dosage (glm_score_dense_dosage.hip): the same over variants with a dosage track ----
+// LaunchGlmScoreDense's sums[p][i][kp + 6] and hgn[p][i] for the nt listed variants vlist[i] (rows of `view`, each with
+// a track in `dos`), with x = the explicit dosage / 16384 where there is one and the call otherwise.  u16 and eff are
+// scratch: GlmScoreDosageRowBytes(sample_ct) bytes per listed variant in all, 128 ceil(sample_ct / 64) of them in u16
+// and 16 ceil(sample_ct / 64) in eff, both 16-byte aligned.  The other arguments are LaunchGlmScoreDense's.
+struct DosageView;
+uint64_t GlmScoreDosageRowBytes(uint32_t sample_ct);
+hipError_t LaunchGlmScoreDenseDosage(const RowView &view, const DosageView &dos, const uint32_t *vlist, uint32_t nt,
+                                     const uint32_t *mask, const uint32_t *n_y, uint32_t pb, const double *b,
+                                     const double *z0, const double *mz, uint32_t kp, uint32_t k, const double *hg,
+                                     uint16_t *u16, uint8_t *eff, double *sums, uint32_t *nmiss, double *hgn,
+                                     hipStream_t stream);
 
 // ---- pgh_glm_score_sparse_multi (glm_score_sparse_multi.hip): the score test from a sparse row's entries for a block
 // of phenotypes ----

@@ -434,8 +434,23 @@ hipError_t LaunchGlmScoreDense(const RowView &view, uint32_t v0, uint32_t nv, co
 	a.kp = kp;
 	a.sums = sums;
 	GlmScoreDenseMfmaKernel<<<dim3(Blocks(nv, kTileV), c.ld / kTileC), kBlock, 0, stream>>>(a);
+	return LaunchGlmScoreDenseCorr(view, v0, nv, mask, nmiss, pb, b, z0, mz, kp, k, hg, hgn, stream);
+}
+
+hipError_t LaunchGlmScoreDenseCorr(const RowView &view, uint32_t v0, uint32_t nv, const uint32_t *mask,
+                                   const uint32_t *nmiss, uint32_t pb, const double *b, const double *z0,
+                                   const double *mz, uint32_t kp, uint32_t k, const double *hg, double *hgn,
+                                   hipStream_t stream) {
+	const uint32_t words16 = (view.sample_ct + 63u) / 64u;
+	if (k > PGH_GLM_MAX_COVAR || k > kp || pb == 0 || pb > kGlmScoreDensePb || 16ull * words16 > view.pitch) {
+		return hipErrorInvalidValue;
+	}
+	if (nv == 0) {
+		return hipSuccess;
+	}
 	GlmScoreDenseCorrKernel<<<dim3(nv, pb), kBlock, sizeof(double) * kBlock * (k + 3), stream>>>(
-	    view.rows, view.pitch, v0, nv, view.sample_ct, mask, 4u * words16, nmiss, b, c.ld, z0, kp, k, mz, hg, hgn);
+	    view.rows, view.pitch, v0, nv, view.sample_ct, mask, 4u * words16, nmiss, b, GlmScoreDenseLayout(pb, k).ld, z0, kp,
+	    k, mz, hg, hgn);
 	return hipGetLastError();
 }
 

@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = [
     "pgh_reader_unpack_start", "pgh_reader_unpack_wait", "pgh_get_2bit", "pgh_get_counts", "pgh_get_missingness", "pgh_get_int8", "pgh_get_dosage_f64", "pgh_get_phased",
     "pgh_tally_start", "pgh_tally_request", "pgh_tally_wait", "pgh_tally_counts", "pgh_tally_hwe_lnp",
     "pgh_tally_sample_missing", "pgh_tally_destroy", "pgh_tally_passes_started", "pgh_host_alloc", "pgh_host_free", "pgh_trim_device_cache",
-    "pgh_reader_error", "pgh_open_sparse", "pgh_get_sparse_info", "pgh_sparse_opens_started", "pgh_glm", "pgh_glm_multi", "pgh_glm_sparse", "pgh_glm_score_sparse", "pgh_glm_score_multi", "pgh_glm_score_sparse_spa", "pgh_glm_score_multi_spa", "pgh_glm_score_multi_firth", "pgh_glm_score_sparse_firth", "pgh_glm_score_sparse_multi", "pgh_glm_sparse_multi", "pgh_glm_score_sparse_multi_spa", "pgh_glm_score_sparse_multi_firth", "pgh_burden_sparse", "pgh_skat_sparse", "pgh_skat_p_from_lambda", "pgh_symmetric_eigenvalues", "pgh_score_sparse", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
+    "pgh_reader_error", "pgh_open_sparse", "pgh_get_sparse_info", "pgh_sparse_opens_started", "pgh_glm", "pgh_glm_multi", "pgh_glm_sparse", "pgh_glm_score_sparse", "pgh_glm_score_multi", "pgh_glm_score_multi_dosage", "pgh_glm_score_sparse_spa", "pgh_glm_score_multi_spa", "pgh_glm_score_multi_firth", "pgh_glm_score_sparse_firth", "pgh_glm_score_sparse_multi", "pgh_glm_sparse_multi", "pgh_glm_score_sparse_multi_spa", "pgh_glm_score_sparse_multi_firth", "pgh_burden_sparse", "pgh_skat_sparse", "pgh_skat_p_from_lambda", "pgh_symmetric_eigenvalues", "pgh_score_sparse", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
     "pgh_king_counts", "pgh_king_table", "pgh_king_kinship",
     "pgh_ld_window_sums", "pgh_ld_prune", "pgh_ld_exceeds", "pgh_ld_scores", "pgh_ld_r2",
     "pgh_grm", "pgh_grm_standardize",
@@ -253,6 +253,7 @@ def _load():
         "pgh_glm_sparse": (C.c_int, [vp, vp, u32, u32, vp, u32, vp, vp, cp]),
         "pgh_glm_score_sparse": (C.c_int, [vp, vp, u32, u32, vp, u32, vp, vp, cp]),
         "pgh_glm_score_multi": (C.c_int, [vp, vp, u32, u32, u32, vp, u32, vp, vp, cp]),
+        "pgh_glm_score_multi_dosage": (C.c_int, [vp, vp, u32, u32, u32, vp, u32, vp, vp, cp]),
         "pgh_glm_score_sparse_multi": (C.c_int, [vp, vp, u32, u32, u32, vp, u32, vp, vp, cp]),
         "pgh_glm_sparse_multi": (C.c_int, [vp, vp, u32, u32, u32, vp, u32, vp, vp, cp]),
         "pgh_glm_score_sparse_spa": (C.c_int, [vp, vp, u32, u32, vp, u32, vp, C.c_double, vp, vp, vp, cp]),
@@ -1050,6 +1051,18 @@ class Dataset:
         eb = _errbuf()
         _check(_lib.pgh_glm_score_multi(self._h, subset._h if subset else None, v0, v1, y.shape[0], _ptr(y), z.shape[0],
                                         _ptr(z) if z.size else None, _ptr(rows), eb), eb)
+        return Dataset._glm_multi_rows_dict(rows)
+
+    def glm_score_multi_dosage(self, phenotypes, covariates=None, v_begin: int | None = None, v_end: int | None = None,
+                               subset: Subset | None = None) -> dict:
+        """pgh_glm_score_multi_dosage: glm_score_multi() over a dataset that may hold dosage tracks, with a variant's
+        genotype value the explicit dosage / 16384 where a sample has one and its call otherwise (glm()'s rule).
+        Returns glm_score_multi()'s dict of (V, P) arrays."""
+        v0, v1, y, z = Dataset._score_multi_args(self, phenotypes, covariates, v_begin, v_end, subset)
+        rows = np.zeros((max(0, v1 - v0), y.shape[0]), dtype=GLM_ROW_DTYPE)
+        eb = _errbuf()
+        _check(_lib.pgh_glm_score_multi_dosage(self._h, subset._h if subset else None, v0, v1, y.shape[0], _ptr(y),
+                                               z.shape[0], _ptr(z) if z.size else None, _ptr(rows), eb), eb)
         return Dataset._glm_multi_rows_dict(rows)
 
     def glm_score_sparse_multi(self, phenotypes, covariates=None, v_begin: int | None = None, v_end: int | None = None,

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """One SHA-256 per case over the result bytes of the GLM family (pgh_glm, pgh_glm_multi, pgh_glm_sparse,
-pgh_glm_score_sparse, pgh_glm_score_sparse_spa, pgh_glm_score_sparse_firth, pgh_glm_score_sparse_multi, pgh_glm_score_sparse_multi_spa, pgh_glm_score_sparse_multi_firth, pgh_glm_score_multi, pgh_glm_score_multi_spa,
+pgh_glm_score_sparse, pgh_glm_score_sparse_spa, pgh_glm_score_sparse_firth, pgh_glm_score_sparse_multi, pgh_glm_score_sparse_multi_spa, pgh_glm_score_sparse_multi_firth, pgh_glm_score_multi, pgh_glm_score_multi_dosage, pgh_glm_score_multi_spa,
 pgh_glm_score_multi_firth, pgh_burden_sparse), pgh_score_sparse, and the plink_ld pair sums and sparse counts that share their wave sums: the
 paths a change to the family's kernels, host staging, scratch layout or chunk loops can touch.  Two builds of the library
 compute the same rows bit for bit exactly when their outputs of this tool are equal line for line; PGENHIP_LIB names
@@ -134,6 +134,15 @@ emit("glm_multi dosage chunks split", dd.glm_multi(phenos(rng, N_D, 3, Zd, 2), Z
 a, b = rng.integers(0, M_D, 200), rng.integers(0, M_D, 200)
 emit("ld_pairs long rows", dd.ld_pairs(a, b))
 dd.close()
+
+# pgh_glm_score_multi_dosage over the small files above, on draws of its own so that the lines around it keep theirs
+rng_t = np.random.default_rng(20261020)
+Zt, Zts = covar(rng_t, 3, N), covar(rng_t, 3, n_keep)
+Yt = phenos(rng_t, N, 7, Zt, 2, "logistic")
+emit("glm_score_multi_dosage tracks P=7 two patterns", dt.glm_score_multi_dosage(Yt, Zt), dt.glm_score_multi_dosage(Yt, None))
+emit("glm_score_multi_dosage tracks subset", dt.glm_score_multi_dosage(phenos(rng_t, n_keep, 3, Zts, 1, "logistic"), Zts,
+                                                                         subset=st, v_begin=7, v_end=M - 3))
+emit("glm_score_multi_dosage no tracks", ds.glm_score_multi_dosage(Yt, Zt))
 for d in (ss, st, ds, dt):
     d.close()
 
