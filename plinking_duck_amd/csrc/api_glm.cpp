@@ -1370,6 +1370,24 @@ GlmScoreMultiPlan GlmScoreSparseMultiPlanFor(uint32_t n_raw, uint32_t n_pheno, u
 	return GlmSparseBlockPlanFor(pgh::kGlmScoreSparsePb, n_pheno, nv_all, budget, cus, per_group, block_bytes, variant_bytes);
 }
 
+// sg.hz (and hz_raw): the covariates as they are, into d_z0 and, in raw-sample order, into *d_zr0, which without a
+// subset is d_z0 itself.  who: the entry point's name in the error texts.
+int GlmUploadCovariates(const pgh_subset *subset, uint32_t kp, const GlmStaged &sg, double *d_z0, double **d_zr0,
+                        hipStream_t st, const char *who, char *errbuf) {
+	if (!subset) {
+		*d_zr0 = d_z0;
+	}
+	if (kp) {
+		PGH_HIP(hipMemcpyAsync(d_z0, sg.hz.data(), 8ull * sg.hz.size(), hipMemcpyHostToDevice, st),
+		        (std::string(who) + " covariate upload").c_str());
+	}
+	if (sg.raw && kp) {
+		PGH_HIP(hipMemcpyAsync(*d_zr0, sg.hz_raw.data(), 8ull * sg.hz_raw.size(), hipMemcpyHostToDevice, st),
+		        (std::string(who) + " covariate upload (raw order)").c_str());
+	}
+	return PGH_OK;
+}
+
 // What one call of pgh_glm_score_multi* (a dense-resident dataset) and of pgh_glm_score_sparse_multi* (a sparse-resident
 // one) share after the argument checks: the pattern order, the staging of a pattern group, the null fit of a block
 // phenotype, the solve of a chunk's rows phenotype by phenotype and their scatter into the caller's rows.
@@ -1458,20 +1476,8 @@ void GlmScoreBlockCall::AddShared(ScratchLayout &lay) {
 	hrows.resize(static_cast<size_t>(plan.chunk) * plan.pb_max);
 }
 
-// sg.hz (and hz_raw): the covariates as they are
 int GlmScoreBlockCall::UploadCovariates(const GlmStaged &sg) {
-	if (!subset) {
-		d_zr0 = d_z0;
-	}
-	if (kp) {
-		PGH_HIP(hipMemcpyAsync(d_z0, sg.hz.data(), 8ull * sg.hz.size(), hipMemcpyHostToDevice, st),
-		        What("covariate upload").c_str());
-	}
-	if (sg.raw && kp) {
-		PGH_HIP(hipMemcpyAsync(d_zr0, sg.hz_raw.data(), 8ull * sg.hz_raw.size(), hipMemcpyHostToDevice, st),
-		        What("covariate upload (raw order)").c_str());
-	}
-	return PGH_OK;
+	return GlmUploadCovariates(subset, kp, sg, d_z0, &d_zr0, st, who, errbuf);
 }
 
 GlmScoreBlockCall::GroupStage &GlmScoreBlockCall::StageGroup(uint32_t p) {
@@ -1885,21 +1891,9 @@ int GlmSparseMultiCall::Prepare() {
 	return PGH_OK;
 }
 
-// sg.hz (and hz_raw): the covariates as they are
 int GlmSparseMultiCall::UploadCovariates(const GlmStaged &sg) {
 	staged = &sg;
-	if (!subset) {
-		d_zr0 = d_z0;
-	}
-	if (kp) {
-		PGH_HIP(hipMemcpyAsync(d_z0, sg.hz.data(), 8ull * sg.hz.size(), hipMemcpyHostToDevice, st),
-		        "glm_sparse_multi covariate upload");
-	}
-	if (sg.raw && kp) {
-		PGH_HIP(hipMemcpyAsync(d_zr0, sg.hz_raw.data(), 8ull * sg.hz_raw.size(), hipMemcpyHostToDevice, st),
-		        "glm_sparse_multi covariate upload (raw order)");
-	}
-	return PGH_OK;
+	return GlmUploadCovariates(subset, kp, sg, d_z0, &d_zr0, st, "glm_sparse_multi", errbuf);
 }
 
 // The block of the phenotypes b0 .. b0 + pb: per phenotype |S|, its mean and the covariates' means over S, each summed

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """One SHA-256 per case over the result bytes of the GLM family (pgh_glm, pgh_glm_multi, pgh_glm_sparse,
-pgh_glm_score_sparse, pgh_glm_score_sparse_spa, pgh_glm_score_sparse_firth, pgh_glm_score_sparse_multi, pgh_glm_score_sparse_multi_spa, pgh_glm_score_sparse_multi_firth, pgh_glm_score_multi, pgh_glm_score_multi_dosage, pgh_glm_score_multi_spa,
+pgh_glm_score_sparse, pgh_glm_score_sparse_spa, pgh_glm_score_sparse_firth, pgh_glm_score_sparse_multi, pgh_glm_score_sparse_multi_spa, pgh_glm_score_sparse_multi_firth, pgh_glm_sparse_multi, pgh_glm_score_multi, pgh_glm_score_multi_dosage, pgh_glm_score_multi_spa,
 pgh_glm_score_multi_firth, pgh_burden_sparse), pgh_score_sparse, and the plink_ld pair sums and sparse counts that share their wave sums: the
 paths a change to the family's kernels, host staging, scratch layout or chunk loops can touch.  Two builds of the library
 compute the same rows bit for bit exactly when their outputs of this tool are equal line for line; PGENHIP_LIB names
@@ -373,4 +373,30 @@ for max_minor, form in ((n, "entries only"), (1, "with dense-form rows")):
             Yk = np.stack([SM.O.pheno(rng_k, n, Zk), SM.O.pheno(rng_k, n, Zk, case_rate=0.35, missing=0.1)])
             res = sp.glm_score_sparse_multi_firth(Yk, Zk, firth_cutoff=CUT)
             emit(f"glm_score_sparse_multi_firth {form}, k={k} P=2", res, note=share(res, "firth_state"))
+    sp.close()
+
+# ---- pgh_glm_sparse_multi, on the same file and the phenotypes of its tests' builders (fitted rows).  Again last, on
+# generators of its own, after every line of a build without these cases ----------------------------------------------
+import test_glm_sparse_multi as LM  # noqa: E402
+
+x_l = LM._values(geno)
+for max_minor, form in ((n, "entries only"), (1, "with dense-form rows")):
+    sp = L.Dataset.open(path, sparse=True, max_minor=max_minor)
+    for k in (0, 3):
+        Zk, Yk = LM.parity_inputs(n, k)
+        rng_k = np.random.default_rng(4000 + k)
+        # the builder's five and a sixth with a missing pattern of its own
+        Yk = np.vstack([Yk, LM._phenotype(rng_k, n, Zk, 1.0, rng_k.random(n) < 0.05, x_l)])
+        emit(f"glm_sparse_multi {form}, k={k} P=6", sp.glm_sparse_multi(Yk, Zk if k else None))
+    Z3, Y3 = LM.parity_inputs(n, 3)
+    emit(f"glm_sparse_multi {form}, k=3 P=65", sp.glm_sparse_multi(np.stack([Y3[i % len(Y3)] for i in range(65)]), Z3))
+    sub = sp.subset(keep_m)
+    emit(f"glm_sparse_multi {form}, k=3 subset",
+         sp.glm_sparse_multi(np.ascontiguousarray(Y3[:, keep_m]), np.ascontiguousarray(Z3[:, keep_m]), subset=sub))
+    sub.close()
+    if max_minor == n:
+        for k in (4, 20):
+            rng_k = np.random.default_rng(5000 + k)
+            Zk = LM._covariates(rng_k, k, n)
+            emit(f"glm_sparse_multi {form}, k={k} P=2", sp.glm_sparse_multi(LM._phenotypes(rng_k, n, Zk, 2, x=x_l), Zk))
     sp.close()
