@@ -558,7 +558,7 @@ static int EnsureDosageRecords(const pgh_dataset *ds, hipStream_t st, char *errb
 	std::vector<uint64_t> off(rows + 1, 0);
 	for (uint32_t r = 0; r < rows; r++) {
 		const uint64_t have = ds->dos_row_count[r];
-		const bool sparse = have != ds->sample_ct && have * 5 < static_cast<uint64_t>(ds->sample_ct) * 2;
+		const bool sparse = pgh::DosageTrackClass(have, ds->sample_ct) == 1;
 		off[r + 1] = off[r] + (sparse ? have : 0);
 	}
 	ds->dos_rec_state = -1;
@@ -603,6 +603,55 @@ static int EnsureDosageRecords(const pgh_dataset *ds, hipStream_t st, char *errb
 	ds->d_dos_rec_off = d_off;
 	ds->dos_rec_ct = off[rows];
 	ds->dos_rec_state = 1;
+	return PGH_OK;
+}
+
+// Which hardcall codes each dosage row holds among ALL samples (the contraction runs over all of them, whatever the
+// subset), built once by the first center-mode plan that scores a track: one tally of the tracks' rows.  No room is
+// not an error: the tables then keep the entries of the codes nobody carries.
+static int EnsureDosageCodes(const pgh_dataset *ds, hipStream_t st, char *errbuf) {
+	std::lock_guard<std::mutex> lock(ds->dos_rec_mutex);
+	if (ds->dos_codes_state != 0) {
+		return PGH_OK;
+	}
+	ds->dos_codes_state = -1;
+	const uint32_t rows = ds->dos_rows;
+	std::vector<uint32_t> row_variant(rows, 0);
+	for (size_t v = 0; v < ds->dos_row_of.size(); v++) {
+		if (ds->dos_row_of[v] >= 0) {
+			row_variant[static_cast<uint32_t>(ds->dos_row_of[v])] = static_cast<uint32_t>(v);
+		}
+	}
+	uint32_t *d_row_variant = nullptr, *d_counts = nullptr;
+	uint8_t *d_codes = nullptr;
+	if (PghMalloc(reinterpret_cast<void **>(&d_counts), 16ull * rows) != hipSuccess ||
+	    PghMalloc(reinterpret_cast<void **>(&d_row_variant), 4ull * rows) != hipSuccess ||
+	    PghMalloc(reinterpret_cast<void **>(&d_codes), rows) != hipSuccess) {
+		(void)hipGetLastError();
+		(void)hipFree(d_counts);
+		(void)hipFree(d_row_variant);
+		(void)hipFree(d_codes);
+		return PGH_OK;
+	}
+	hipError_t e = hipMemcpyAsync(d_row_variant, row_variant.data(), 4ull * rows, hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) {
+		e = pgh::LaunchCounts(ds->View(), 0, d_row_variant, rows, nullptr, ds->sample_ct, d_counts, st);
+	}
+	if (e == hipSuccess) {
+		e = pgh::LaunchDosageRowCodes(d_counts, rows, d_codes, st);
+	}
+	if (e == hipSuccess) {
+		e = hipStreamSynchronize(st); // row_variant dies with this frame
+	}
+	(void)hipFree(d_row_variant);
+	(void)hipFree(d_counts);
+	if (e != hipSuccess) {
+		(void)hipFree(d_codes);
+		ds->dos_codes_state = 0; // the call fails; a later plan tries again
+		return DeviceFail(errbuf, "dosage row codes", e);
+	}
+	ds->d_dos_codes = d_codes;
+	ds->dos_codes_state = 1;
 	return PGH_OK;
 }
 
@@ -677,8 +726,7 @@ static int ScorePlanCreate(const pgh_dataset *ds, const pgh_subset *subset, uint
 			if (r < 0) {
 				return 0;
 			}
-			const uint64_t have = ds->dos_row_count[static_cast<uint32_t>(r)];
-			return have == ds->sample_ct ? 3 : (have * 5 >= static_cast<uint64_t>(ds->sample_ct) * 2 ? 2 : 1);
+			return pgh::DosageTrackClass(ds->dos_row_count[static_cast<uint32_t>(r)], ds->sample_ct);
 		};
 		uint32_t at = 0;
 		for (int want = 0; want < 4; want++) {
@@ -813,11 +861,22 @@ static int ScorePlanCreate(const pgh_dataset *ds, const pgh_subset *subset, uint
 			PGH_HIP(pgh::LaunchDosageSums(ds->View(), ds->Dosage(), 0, vlist + n_hard, n_dos,
 			                              subset ? subset->d_include : nullptr, sums, st),
 			        "dosage sums kernel");
+			// center: 1 / sd of a rare track must not set the weight columns' fixed-point scale.
+			// PGH_SCORE_DOSAGE_CODES=0 keeps every table entry (a cross-check, and what a dataset without room gets)
+			const char *codes_env = std::getenv("PGH_SCORE_DOSAGE_CODES");
+			const bool use_codes = mode == 2 && !(codes_env && *codes_env == '0');
+			if (use_codes) {
+				rc = EnsureDosageCodes(ds, st, errbuf);
+				if (rc != PGH_OK) {
+					return rc;
+				}
+			}
 			PGH_HIP(pgh::LaunchScoreTablesDosage(sums, d_flip ? d_flip + n_hard : nullptr, n_dos, mode,
 			                                     static_cast<double *>(plan->d_ts) + 4ull * n_hard,
 			                                     static_cast<double *>(plan->d_td) + 4ull * n_hard,
 			                                     static_cast<double *>(plan->d_lin),
-			                                     static_cast<uint32_t *>(plan->d_ac) + n_hard, st),
+			                                     static_cast<uint32_t *>(plan->d_ac) + n_hard, vlist + n_hard,
+			                                     ds->d_dos_row_of, use_codes ? ds->d_dos_codes : nullptr, st),
 			        "score table kernel");
 		}
 		// The contraction itself runs on the int8 matrix cores: cut the coefficients of the table-scored

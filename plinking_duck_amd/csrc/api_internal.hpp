@@ -68,6 +68,10 @@ struct pgh_dataset {
 	mutable uint32_t *d_dos_rec = nullptr;
 	mutable uint64_t *d_dos_rec_off = nullptr;
 	mutable uint64_t dos_rec_ct = 0;
+	// The hardcall codes each dosage row holds among all samples (bit g: code g occurs), built by the first
+	// center-mode plink_score plan over a track (under dos_rec_mutex).  codes_state: 0 not tried, 1 resident, -1 no room.
+	mutable int dos_codes_state = 0;
+	mutable uint8_t *d_dos_codes = nullptr;
 	// phase tracks of the resident range (phase.hpp): two bit rows per phased variant; ph_rows == 0: none
 	uint32_t ph_rows = 0;
 	std::vector<int32_t> ph_row_of;

@@ -524,10 +524,25 @@ __global__ __launch_bounds__(256) void k_dosage_unpack_transposed(const uint8_t 
 	out[static_cast<uint64_t>(blockIdx.y) * out_stride + j] = u == kNoDosage ? -9.0 : static_cast<double>(u) * 0x1p-14;
 }
 
+__global__ __launch_bounds__(256) void k_dosage_row_codes(const uint32_t *__restrict__ counts, uint32_t rows,
+                                                          uint8_t *__restrict__ codes) {
+	const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+	if (r < rows) {
+		uint32_t have = 0;
+		for (uint32_t g = 0; g < 4; g++) {
+			have |= counts[4ull * r + g] != 0u ? 1u << g : 0u;
+		}
+		codes[r] = static_cast<uint8_t>(have);
+	}
+}
+
 __global__ __launch_bounds__(256) void k_score_tables_dosage(const uint64_t *__restrict__ sums,
                                                              const uint8_t *__restrict__ flip, uint32_t n_scored,
                                                              int mode, double *__restrict__ ts, double *__restrict__ td,
-                                                             double *__restrict__ lin, uint32_t *__restrict__ ac) {
+                                                             double *__restrict__ lin, uint32_t *__restrict__ ac,
+                                                             const uint32_t *__restrict__ vlist,
+                                                             const int32_t *__restrict__ row_of,
+                                                             const uint8_t *__restrict__ codes) {
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
 	if (i >= n_scored) {
 		return;
@@ -558,6 +573,18 @@ __global__ __launch_bounds__(256) void k_score_tables_dosage(const uint64_t *__r
 				l[2] = mean_scored;
 				l[3] = 1.0 / sd;
 				inc = 2u;
+				if (codes) {
+					// entries of codes nobody carries are never read: let them continue the ones that are, so that
+					// the 1 / sd of a rare track over hom-ref calls does not set the weight column's fixed-point scale
+					const uint32_t have = codes[row_of[vlist[i]]];
+					if (!(have & 6u)) {
+						s[1] = s[0];
+						s[2] = s[0];
+					}
+					if (!(have & 8u)) {
+						s[3] = s[0] + 3.0 * (s[1] - s[0]);
+					}
+				}
 			}
 		} else {
 			for (int g = 0; g < 3; g++) {
@@ -598,7 +625,7 @@ __global__ __launch_bounds__(256) void k_score_dosage(const uint8_t *__restrict_
                                                       const uint32_t *__restrict__ ac, int mode,
                                                       double *__restrict__ score, double *__restrict__ dosage_sum,
                                                       uint32_t *__restrict__ miss) {
-	constexpr uint32_t kStage = 64;
+	constexpr uint32_t kStage = kDosageLaneStage;
 	constexpr uint32_t kGroup = 2;
 	constexpr uint32_t kPer = 4;
 	__shared__ double s_ts[kStage][4];
@@ -734,7 +761,7 @@ __global__ __launch_bounds__(256) void k_score_dosage_full(uint32_t sample_ct, D
                                                            const uint32_t *__restrict__ ac, int mode,
                                                            double *__restrict__ score,
                                                            double *__restrict__ dosage_sum) {
-	constexpr uint32_t kStage = 64;
+	constexpr uint32_t kStage = kDosageLaneStage;
 	constexpr uint32_t kGroup = 4;
 	constexpr uint32_t kPer = 4; // samples per lane: one 8-byte load of the value run (2-byte aligned)
 	__shared__ double s_lin[kStage][4];
@@ -841,15 +868,15 @@ __global__ __launch_bounds__(1024, 8) void k_score_dosage_fix(const uint8_t *__r
 	// access.  (Round 1 had [word][bit] with a row stride of 65, which sends the lanes to RANDOM banks: 22 LDS cycles
 	// per FP64 atomic instruction instead of 7.4, tools/lds_atomic_probe.hip, profiles/r02_lds_atomic.txt.)
 	constexpr uint32_t kWaves = 16;  // sixteen waves share one tile: the loop is a chain of memory latencies
-	constexpr uint32_t kChunk = 128; // variants whose constants are staged in LDS at a time
-	__shared__ double s_acc[64 * 64];
-	__shared__ double s_dsum[TRACK ? 64 * 64 : 1];
+	constexpr uint32_t kChunk = kDosageEntryStage; // variants whose constants are staged in LDS at a time
+	__shared__ double s_acc[kDosageTile];
+	__shared__ double s_dsum[TRACK ? kDosageTile : 1];
 	__shared__ uint64_t s_row[kChunk], s_bits[kChunk], s_vals[kChunk]; // row bytes / presence row / first value
 	// an explicit dosage u (in 2^-14) replaces the call's term: delta = ((l0 d + l1) - l2) l3 - ts[call], d = u 2^-14,
 	// staged as delta = a u + b[call] with a = l0 l3 2^-14 and b[call] = (l1 - l2) l3 - ts[call]
 	__shared__ double s_wt[kChunk], s_a[kChunk], s_b[kChunk][4];
 	__shared__ uint32_t s_on[kChunk];
-	for (uint32_t t = threadIdx.x; t < 64 * 64; t += 64u * kWaves) {
+	for (uint32_t t = threadIdx.x; t < kDosageTile; t += 64u * kWaves) {
 		s_acc[t] = 0.0;
 		if (TRACK) {
 			s_dsum[t] = 0.0;
@@ -857,7 +884,7 @@ __global__ __launch_bounds__(1024, 8) void k_score_dosage_fix(const uint8_t *__r
 	}
 	const uint32_t lane = threadIdx.x & 63u;
 	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-	const uint32_t w = blockIdx.x * 64u + lane;
+	const uint32_t w = blockIdx.x * kDosageTileWords + lane;
 	const bool in_row = w < dos.words;
 	const uint32_t i_begin = blockIdx.y * slice_len;
 	const uint32_t i_end = min(i_begin + slice_len, n_scored);
@@ -905,9 +932,9 @@ __global__ __launch_bounds__(1024, 8) void k_score_dosage_fix(const uint8_t *__r
 		e &= e - 1ull;                                                                                                 \
 		const uint32_t code = static_cast<uint32_t>((b < 32u ? q_lo : q_hi) >> (2u * (b & 31u))) & 3u;                 \
 		const double delta = fma(a, static_cast<double>(U), s_b[k][code]);                                             \
-		atomicAdd(&s_acc[b * 64u + lane], wt * delta);                                                                 \
+		atomicAdd(&s_acc[b * kDosageTileWords + lane], wt * delta);                                                                 \
 		if (TRACK) {                                                                                                   \
-			atomicAdd(&s_dsum[b * 64u + lane], delta);                                                                 \
+			atomicAdd(&s_dsum[b * kDosageTileWords + lane], delta);                                                                 \
 		}                                                                                                              \
 		if (miss && code == 3u) {                                                                                      \
 			atomicSub(miss + 64u * w + b, 1u); /* it has a dosage: not missing after all */                            \
@@ -931,7 +958,8 @@ __global__ __launch_bounds__(1024, 8) void k_score_dosage_fix(const uint8_t *__r
 		PGH_STEP(pa.x) PGH_STEP(pa.y) PGH_STEP(pa.z) PGH_STEP(pa.w)
 		PGH_STEP(pb.x) PGH_STEP(pb.y) PGH_STEP(pb.z) PGH_STEP(pb.w)
 #undef PGH_STEP
-		uint32_t n = 16;
+		static_assert(kDosagePreload == 16, "the two 16-byte loads above");
+		uint32_t n = kDosagePreload;
 		while (e) {
 			const uint32_t u = vals[n++];
 			PGH_DOSAGE_ENTRY(u)
@@ -940,9 +968,9 @@ __global__ __launch_bounds__(1024, 8) void k_score_dosage_fix(const uint8_t *__r
 	}
 	}
 	__syncthreads();
-	for (uint32_t t = threadIdx.x; t < 4096u; t += 64u * kWaves) {
-		const uint32_t s = blockIdx.x * 4096u + t;
-		const uint32_t at = (t & 63u) * 64u + (t >> 6); // (a 64-way bank conflict, eight times per slice: noise)
+	for (uint32_t t = threadIdx.x; t < kDosageTile; t += 64u * kWaves) {
+		const uint32_t s = blockIdx.x * kDosageTile + t;
+		const uint32_t at = (t % kDosageWord) * kDosageTileWords + t / kDosageWord; // (a 64-way bank conflict, eight times per slice: noise)
 		if (s < sample_ct) {
 			if (s_acc[at] != 0.0) {
 				unsafeAtomicAdd(score + static_cast<uint64_t>(s) * out_stride, s_acc[at]);
@@ -1003,7 +1031,7 @@ __global__ __launch_bounds__(256) void k_dosage_records(const uint8_t *__restric
 			const uint32_t b = static_cast<uint32_t>(__ffsll(static_cast<long long>(e))) - 1u;
 			e &= e - 1ull;
 			const uint32_t code = static_cast<uint32_t>((b < 32u ? q_lo : q_hi) >> (2u * (b & 31u))) & 3u;
-			out[pos] = (static_cast<uint32_t>(vals[i]) << 16) | ((b * 64u + lane) << 3) | code;
+			out[pos] = (static_cast<uint32_t>(vals[i]) << 16) | ((b * kDosageTileWords + lane) << 3) | code;
 		}
 		base += static_cast<uint32_t>(__popcll(mask));
 	}
@@ -1015,7 +1043,7 @@ __global__ __launch_bounds__(256) void k_dosage_records(const uint8_t *__restric
 // 512 entries in registers while the current ones are added.  Per 64 entries: one load, ~10 vector instructions,
 // one LDS read (the term of the hardcall the dosage replaces) and one or two FP64 LDS atomics without conflicts.
 constexpr uint32_t kRecNone = 0xffffffffu; // not a record: values stop at 32768
-constexpr uint32_t kRecGroup = 8;          // wave-loads of 64 records in flight per wave
+constexpr uint32_t kRecGroup = kDosageRecFetch / 64; // wave-loads of 64 records in flight per wave
 
 template <bool TRACK>
 __global__ __launch_bounds__(1024) void k_score_dosage_records(uint32_t sample_ct, DosageView dos,
@@ -1028,13 +1056,13 @@ __global__ __launch_bounds__(1024) void k_score_dosage_records(uint32_t sample_c
                                                                 double *__restrict__ dosage_sum,
                                                                 uint32_t *__restrict__ miss) {
 	constexpr uint32_t kWaves = 16;
-	constexpr uint32_t kChunk = 128; // variants whose constants are staged in LDS at a time
-	__shared__ double s_acc[64 * 64]; // [bit][word]
-	__shared__ double s_dsum[TRACK ? 64 * 64 : 1];
+	constexpr uint32_t kChunk = kDosageEntryStage; // variants whose constants are staged in LDS at a time
+	__shared__ double s_acc[kDosageTile]; // [bit][word]
+	__shared__ double s_dsum[TRACK ? kDosageTile : 1];
 	__shared__ uint64_t s_first[kChunk]; // the tile's first record of each variant
 	__shared__ uint32_t s_count[kChunk]; // and how many there are (0: nothing to add)
 	__shared__ double s_wt[kChunk], s_a[kChunk], s_b[kChunk][4]; // delta = a u + b[call] (k_score_dosage_fix)
-	for (uint32_t t = threadIdx.x; t < 64 * 64; t += 64u * kWaves) {
+	for (uint32_t t = threadIdx.x; t < kDosageTile; t += 64u * kWaves) {
 		s_acc[t] = 0.0;
 		if (TRACK) {
 			s_dsum[t] = 0.0;
@@ -1042,7 +1070,7 @@ __global__ __launch_bounds__(1024) void k_score_dosage_records(uint32_t sample_c
 	}
 	const uint32_t lane = threadIdx.x & 63u;
 	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-	const uint32_t w0 = blockIdx.x * 64u; // first word of the tile
+	const uint32_t w0 = blockIdx.x * kDosageTileWords; // first word of the tile
 	const uint32_t i_begin = blockIdx.y * slice_len;
 	const uint32_t i_end = min(i_begin + slice_len, n_scored);
 	for (uint32_t base = i_begin; base < i_end; base += kChunk) {
@@ -1133,9 +1161,9 @@ __global__ __launch_bounds__(1024) void k_score_dosage_records(uint32_t sample_c
 		}
 	}
 	__syncthreads();
-	for (uint32_t t = threadIdx.x; t < 4096u; t += 64u * kWaves) {
-		const uint32_t s = blockIdx.x * 4096u + t;
-		const uint32_t at = (t & 63u) * 64u + (t >> 6); // (a 64-way bank conflict, eight times per slice: noise)
+	for (uint32_t t = threadIdx.x; t < kDosageTile; t += 64u * kWaves) {
+		const uint32_t s = blockIdx.x * kDosageTile + t;
+		const uint32_t at = (t % kDosageWord) * kDosageTileWords + t / kDosageWord; // (a 64-way bank conflict, eight times per slice: noise)
 		if (s < sample_ct) {
 			if (s_acc[at] != 0.0) {
 				unsafeAtomicAdd(score + static_cast<uint64_t>(s) * out_stride, s_acc[at]);
@@ -1248,12 +1276,21 @@ hipError_t LaunchDosageUnpackTransposed(const RowView &view, const DosageView &d
 }
 
 hipError_t LaunchScoreTablesDosage(const uint64_t *sums, const uint8_t *flip, uint32_t n_scored, int mode, double *ts,
-                                   double *td, double *lin, uint32_t *ac, hipStream_t stream) {
+                                   double *td, double *lin, uint32_t *ac, const uint32_t *vlist, const int32_t *row_of,
+                                   const uint8_t *codes, hipStream_t stream) {
 	if (n_scored == 0) {
 		return hipSuccess;
 	}
 	hipLaunchKernelGGL(k_score_tables_dosage, dim3((n_scored + 255) / 256), dim3(256), 0, stream, sums, flip, n_scored,
-	                   mode, ts, td, lin, ac);
+	                   mode, ts, td, lin, ac, vlist, row_of, (vlist && row_of) ? codes : nullptr);
+	return hipGetLastError();
+}
+
+hipError_t LaunchDosageRowCodes(const uint32_t *counts, uint32_t rows, uint8_t *codes, hipStream_t stream) {
+	if (rows == 0) {
+		return hipSuccess;
+	}
+	hipLaunchKernelGGL(k_dosage_row_codes, dim3((rows + 255) / 256), dim3(256), 0, stream, counts, rows, codes);
 	return hipGetLastError();
 }
 
@@ -1267,11 +1304,11 @@ hipError_t LaunchScoreDosage(const RowView &view, const DosageView &dos, const u
 	const uint32_t sample_blocks = (view.sample_ct + 1023) / 1024; // four samples per lane
 	const uint32_t want_slices = (2048 + sample_blocks - 1) / sample_blocks;
 	uint32_t slice_len = (n_scored + want_slices - 1) / want_slices;
-	slice_len = ((slice_len + 63) / 64) * 64;
+	slice_len = ((slice_len + kDosageLaneStage - 1) / kDosageLaneStage) * kDosageLaneStage;
 	uint32_t slices = (n_scored + slice_len - 1) / slice_len;
 	if (slices > 65535u) {
 		slices = 65535u;
-		slice_len = ((n_scored + slices - 1) / slices + 63) / 64 * 64;
+		slice_len = ((n_scored + slices - 1) / slices + kDosageLaneStage - 1) / kDosageLaneStage * kDosageLaneStage;
 		slices = (n_scored + slice_len - 1) / slice_len;
 	}
 	// weight columns four at a time; the dosage sum and the missing tally ride with the first pass
@@ -1303,14 +1340,14 @@ hipError_t LaunchScoreDosageFix(const RowView &view, const DosageView &dos, cons
 	if (n_scored == 0) {
 		return hipSuccess;
 	}
-	const uint32_t tiles = (dos.words + 63) / 64;
+	const uint32_t tiles = (dos.words + kDosageTileWords - 1) / kDosageTileWords;
 	const uint32_t want_slices = (2048 + tiles - 1) / tiles;
 	uint32_t slice_len = (n_scored + want_slices - 1) / want_slices;
-	slice_len = ((slice_len + 127) / 128) * 128;
+	slice_len = ((slice_len + kDosageEntryStage - 1) / kDosageEntryStage) * kDosageEntryStage;
 	uint32_t slices = (n_scored + slice_len - 1) / slice_len;
 	if (slices > 65535u) {
 		slices = 65535u;
-		slice_len = ((n_scored + slices - 1) / slices + 127) / 128 * 128;
+		slice_len = ((n_scored + slices - 1) / slices + kDosageEntryStage - 1) / kDosageEntryStage * kDosageEntryStage;
 		slices = (n_scored + slice_len - 1) / slice_len;
 	}
 	if (dosage_sum) {
@@ -1330,7 +1367,7 @@ hipError_t LaunchDosageRecords(const RowView &view, const DosageView &dos, uint3
 	if (rows == 0 || dos.words == 0) {
 		return hipSuccess;
 	}
-	const uint32_t tiles = (dos.words + 63) / 64;
+	const uint32_t tiles = (dos.words + kDosageTileWords - 1) / kDosageTileWords;
 	for (uint32_t done = 0; done < rows; done += 65535u) { // grid.y limit
 		const uint32_t n = min(65535u, rows - done);
 		DosageView part = dos;
@@ -1353,14 +1390,14 @@ hipError_t LaunchScoreDosageRecords(const RowView &view, const DosageView &dos, 
 	if (!dos.rec || !dos.rec_off) {
 		return hipErrorInvalidValue;
 	}
-	const uint32_t tiles = (dos.words + 63) / 64;
+	const uint32_t tiles = (dos.words + kDosageTileWords - 1) / kDosageTileWords;
 	const uint32_t want_slices = (2048 + tiles - 1) / tiles;
 	uint32_t slice_len = (n_scored + want_slices - 1) / want_slices;
-	slice_len = ((slice_len + 127) / 128) * 128;
+	slice_len = ((slice_len + kDosageEntryStage - 1) / kDosageEntryStage) * kDosageEntryStage;
 	uint32_t slices = (n_scored + slice_len - 1) / slice_len;
 	if (slices > 65535u) {
 		slices = 65535u;
-		slice_len = ((n_scored + slices - 1) / slices + 127) / 128 * 128;
+		slice_len = ((n_scored + slices - 1) / slices + kDosageEntryStage - 1) / kDosageEntryStage * kDosageEntryStage;
 		slices = (n_scored + slice_len - 1) / slice_len;
 	}
 	if (dosage_sum) {
@@ -1383,11 +1420,11 @@ hipError_t LaunchScoreDosageFull(const RowView &view, const DosageView &dos, con
 	const uint32_t sample_blocks = (view.sample_ct + 1023) / 1024; // four samples per lane
 	const uint32_t want_slices = (2048 + sample_blocks - 1) / sample_blocks;
 	uint32_t slice_len = (n_scored + want_slices - 1) / want_slices;
-	slice_len = ((slice_len + 63) / 64) * 64;
+	slice_len = ((slice_len + kDosageLaneStage - 1) / kDosageLaneStage) * kDosageLaneStage;
 	uint32_t slices = (n_scored + slice_len - 1) / slice_len;
 	if (slices > 65535u) {
 		slices = 65535u;
-		slice_len = ((n_scored + slices - 1) / slices + 63) / 64 * 64;
+		slice_len = ((n_scored + slices - 1) / slices + kDosageLaneStage - 1) / kDosageLaneStage * kDosageLaneStage;
 		slices = (n_scored + slice_len - 1) / slice_len;
 	}
 	for (uint32_t c0 = 0; c0 < n_cols; c0 += 4) {

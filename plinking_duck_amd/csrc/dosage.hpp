@@ -9,6 +9,31 @@
 
 namespace pgh {
 
+// The design values of the dosage kernels, each in one place (tests/dosage_shapes.py builds its rows on them).
+constexpr uint32_t kDosageWord = 64;        // samples of a presence word
+constexpr uint32_t kDosageTile = 4096;      // samples of the LDS tile of the explicit-entry kernels: 64 words
+constexpr uint32_t kDosagePreload = 16;     // values of a word k_score_dosage_fix holds in registers before its scalar tail
+constexpr uint32_t kDosageRecFetch = 512;   // entry records a wave of k_score_dosage_records fetches at a time
+constexpr uint32_t kDosageEntryStage = 128; // variants whose constants the explicit-entry kernels stage in LDS at a time
+constexpr uint32_t kDosageLaneStage = 64;   // ... and the sample-owning kernels
+// plink_score's cut between the explicit-entry kernels and the sample-owning one: a track is sparse while fewer than
+// kDosageCutNum / kDosageCutDen of the samples are explicit.
+constexpr uint32_t kDosageCutNum = 2;
+constexpr uint32_t kDosageCutDen = 5;
+constexpr uint32_t kDosageTileWords = kDosageTile / kDosageWord;
+// a lane of a 64-wide wave per word of the tile (the bit walk, the [bit][word] LDS image, the records' 12-bit element
+// field); a wave-load per 64 records
+static_assert(kDosageTileWords == 64 && kDosageWord == 64 && kDosageRecFetch % 64 == 0, "tile shape");
+
+//! The class of a track with `have` explicit dosages: 1 sparse (entry records / the bit walk), 2 gaps (k_score_dosage),
+//! 3 every sample explicit (k_score_dosage_full).
+inline int DosageTrackClass(uint64_t have, uint32_t sample_ct) {
+	if (have == sample_ct) {
+		return 3;
+	}
+	return have * kDosageCutDen >= static_cast<uint64_t>(sample_ct) * kDosageCutNum ? 2 : 1;
+}
+
 //! A dataset's explicit dosages in HBM, in the file's own bit-array form (vrtype 0x60;
 //! the 0x20 list and 0x40 dense forms are brought to it at pgh_open): per dosage-bearing
 //! variant a presence bit per sample, and the present samples' 16-bit values (0..32768 =
@@ -89,8 +114,17 @@ hipError_t LaunchDosageUnpackTransposed(const RowView &view, const DosageView &d
 //! Per scored variant, from LaunchDosageSums' output: the contribution tables of the hardcall codes
 //! (ts / td as LaunchScoreTables writes them, with the mean taken over dosages), the affine map of an
 //! explicit dosage lin = {scale, shift}: contribution = (d * scale + shift), and the ALLELE_CT increment.
+//! codes (optional, with vlist and dos.row_of): per dosage row the hardcall codes that occur among ALL samples
+//! (LaunchDosageRowCodes).  In center mode the table entries of codes that nobody carries then continue the entries
+//! that are carried (no step without a het or hom-alt call, no jump at missing without a missing call): nothing reads
+//! them, but 1 / sd of a rare track would otherwise set the fixed-point scale of the whole weight column
+//! (score_i8.hpp: every coefficient is rounded to 2^-54 of the column's largest).
 hipError_t LaunchScoreTablesDosage(const uint64_t *sums, const uint8_t *flip, uint32_t n_scored, int mode, double *ts,
-                                   double *td, double *lin, uint32_t *ac, hipStream_t stream);
+                                   double *td, double *lin, uint32_t *ac, const uint32_t *vlist, const int32_t *row_of,
+                                   const uint8_t *codes, hipStream_t stream);
+
+//! codes[r] = bit g set when counts[r][g] != 0 (counts: LaunchCounts over the dosage rows' variants, every sample)
+hipError_t LaunchDosageRowCodes(const uint32_t *counts, uint32_t rows, uint8_t *codes, hipStream_t stream);
 
 //! plink_score over variants that carry dosages (src/plink_score.cpp:586-652): adds into score / dosage_sum and
 //! counts, per sample, the scored variants at which it has neither dosage nor call (miss, for ALLELE_CT).
