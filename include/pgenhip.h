@@ -729,8 +729,8 @@ int pgh_glm_score_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_
  * the other phenotypes or its place among them, of v_begin, the variant chunk, the phenotype block, which other variants
  * carry tracks, the window the dataset was opened with or PGH_GLM_SCORE_SCRATCH_BYTES (which here also holds 144 bytes
  * per 64 samples for every variant in flight), and the same call returns the same bytes every time.
- * Not offered: saddlepoint and Firth follow-ups over tracks (pgh_glm_score_multi_spa's and pgh_glm_score_multi_firth's
- * walks read 2-bit rows), shard groups, a table function. */
+ * Saddlepoint p-values over tracks: pgh_glm_score_multi_dosage_spa.  Not offered: a Firth follow-up over tracks
+ * (pgh_glm_score_multi_firth's walk reads 2-bit rows), shard groups, a table function. */
 int pgh_glm_score_multi_dosage(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                                uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
                                pgh_glm_row *out, char *errbuf);
@@ -815,8 +815,8 @@ int pgh_glm_score_sparse_spa(const pgh_dataset *ds, const pgh_subset *subset, ui
  * addition spa_cutoff must be at least 0.1 (+infinity: never apply it; NaN or a smaller value is PGH_ERR_ARG,
  * "spa_cutoff must be at least 0.1"), and p_spa and spa_state must not be NULL ("null p_spa or spa_state"); they have
  * out's layout, element (v - v_begin) * n_pheno + p.  On any error all three outputs are untouched.  The refusals are the dense route's: a
- * sparse-resident dataset, a shard group, a dataset with dosage tracks (pgh_glm_score_multi_dosage gives such a
- * dataset's score rows, without the saddlepoint: this entry's walk reads 2-bit rows).
+ * sparse-resident dataset, a shard group, a dataset with dosage tracks (pgh_glm_score_multi_dosage_spa gives such a
+ * dataset's rows and saddlepoint p-values: this entry's walk reads 2-bit rows).
  *
  * out is pgh_glm_score_multi's result for the same arguments bit for bit; its p stays the normal p-value.  spa_state
  * and p_spa mean what they mean for pgh_glm_score_sparse_spa: 0 = not applied (the row is not fitted: p_spa NaN; or
@@ -843,6 +843,43 @@ int pgh_glm_score_sparse_spa(const pgh_dataset *ds, const pgh_subset *subset, ui
 int pgh_glm_score_multi_spa(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                             uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
                             double spa_cutoff, pgh_glm_row *out, double *p_spa, uint8_t *spa_state, char *errbuf);
+/* pgh_glm_score_multi_dosage with pgh_glm_score_sparse_spa's SADDLEPOINT p-value beside the normal one: the saddlepoint
+ * over a dense-resident dataset that may hold DOSAGE TRACKS.  Arguments, argument checks, error texts and the layout of
+ * the three outputs are pgh_glm_score_multi_spa's, except that a dataset whose pgh_info.dosage_variant_ct is not 0 is
+ * accepted: spa_cutoff must be at least 0.1 (+infinity: never apply it; NaN or a smaller value is PGH_ERR_ARG,
+ * "spa_cutoff must be at least 0.1"), p_spa and spa_state must not be NULL ("null p_spa or spa_state").  The refusals
+ * are pgh_glm_score_multi_dosage's: a sparse-resident dataset, a shard group, a phenotype that is not 0 / 1, a phenotype
+ * without a case or a control.  On any refusal all three outputs are untouched; v_begin == v_end is PGH_OK.
+ *
+ * out is pgh_glm_score_multi_dosage's result for the same arguments bit for bit; its p stays the normal p-value.
+ * spa_state and p_spa mean what they mean for pgh_glm_score_sparse_spa: 0 = not applied (the row is not fitted: p_spa
+ * NaN; or |stat| <= spa_cutoff: p_spa = out.p bit for bit), 1 = applied (p_spa is the saddlepoint p), 2 = attempted and
+ * failed (p_spa = out.p bit for bit).
+ *
+ * Definition, in the notation of pgh_glm_score_sparse and pgh_glm_score_sparse_spa with d = x and
+ * pgh_glm_score_multi_dosage's genotype rule (x = value / 16384 where there is an explicit dosage, the call otherwise;
+ * M = neither).  n, sum x and sum x^2 over N are that route's exact integers on the 2^-14 grid.  b = 2 if sum_N x > n,
+ * otherwise 0: an exact comparison, and for a row of calls sum x - n = n2 - n0, pgh_glm_score_multi_spa's "n2 > n0".
+ * E = the samples of N whose value is not exactly b (v != b << 14 on the grid).  gt_i = x_i - Zt_i t for i in N, which
+ * does not depend on b; mu_i = r_i > 0 ? 1 - r_i : -r_i; V_E = sum_E w gt^2.  V_rest = 0 by rule when E = N, that is
+ * when no sample of N sits exactly on b, the usual case of a full track (the sparse route's rule for b = 3); otherwise
+ * V_rest = max(V - V_E, 0).  Everything else is pgh_glm_score_sparse_spa's contract word for word: K, K', K'' with one
+ * exp(-|gt s|) per entry; the safeguarded Newton iteration; the three stopping rules and the cap of 64 evaluations;
+ * omega, nu and the two tails; the state-2 conditions.
+ *
+ * A variant without a track, whatever its neighbours carry, and a variant whose track restates its calls get
+ * pgh_glm_score_multi_spa's triple (out, p_spa, spa_state) for the same calls in a file without tracks, bit for bit
+ * (for calls E = N cannot arise in a fitted row); a dataset without any track gets pgh_glm_score_multi_spa's bytes.
+ *
+ * A row's triple is a function of its variant's calls and track, its own phenotype, the covariates, the subset and
+ * spa_cutoff only: not of the other phenotypes or its place among them, of v_begin, the variant chunk, the phenotype
+ * block, which other variants carry tracks, the window the dataset was opened with, PGH_GLM_SCORE_SCRATCH_BYTES or the
+ * grid, and the same call returns the same bytes every time.  With a full track E = N, so the iteration passes over
+ * every sample of the row, not over its carriers.
+ * Not offered: Firth over tracks, shard groups, a table function. */
+int pgh_glm_score_multi_dosage_spa(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                                   uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
+                                   double spa_cutoff, pgh_glm_row *out, double *p_spa, uint8_t *spa_state, char *errbuf);
 /* pgh_glm_score_sparse_multi with pgh_glm_score_sparse_spa's SADDLEPOINT p-value beside the normal one, for every
  * (variant, phenotype) row of the sparse many-phenotype route.  Arguments, argument checks, error texts and refusals
  * are pgh_glm_score_sparse_multi's: a dataset that is not sparse-resident, a shard group, n_pheno == 0, "phenotype must

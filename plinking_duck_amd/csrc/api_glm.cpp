@@ -1566,6 +1566,9 @@ void GlmScoreBlockCall::Scatter(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t 
 // tracks (pgh_glm_score_multi_dosage over a dataset that holds dosage tracks): a chunk's variants without a track go
 // through the same kernels, from the first such variant to the last; the ones with a track are listed, expanded into
 // d_u16 / d_eff and contracted by glm_score_dense_dosage.hip, and their rows replace what the first pass left for them.
+// With the saddlepoint follow-up (pgh_glm_score_multi_dosage_spa) the first pass may leave a triple for a track variant
+// from its calls; the track pass (glm_score_dense_dosage_spa.hip over d_u16) overwrites it.  No entry point brings a
+// Firth follow-up here with tracks.
 struct GlmScoreMultiCall : GlmScoreBlockCall {
 	double *d_b;
 	uint32_t *d_mask;
@@ -1664,8 +1667,23 @@ int GlmScoreMultiCall::RunTracks(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t
 	                                       d_hg, d_u16, d_eff, ch.sums, ch.nmiss, ch.hgn, st),
 	        "glm_score_multi_dosage kernels");
 	PGH_TRY(SolveRows(pb, nt));
+	if (fu.kind == GlmScoreFollowUp::kSpa) {
+		// over the u16 rows and the sums the launches above have just left: nothing is expanded twice
+		const size_t n_rows = static_cast<size_t>(nt) * pb;
+		PGH_HIP(pgh::LaunchGlmScoreDenseDosageSpa(ds->View(), d_u16, nt, d_mask, pb, d_b, d_zr0, d_mz, kp, k, ch.sums, ch.rows,
+		                                          ch.so.t, fu.cutoff, plan.n_groups, d_stash, ch.so.p_spa, ch.so.state, st),
+		        "glm_score_multi_dosage_spa kernel");
+		PGH_HIP(hipMemcpyAsync(hp_spa.data(), ch.so.p_spa, 8ull * n_rows, hipMemcpyDeviceToHost, st),
+		        "glm_score_multi_dosage_spa p copy");
+		PGH_HIP(hipMemcpyAsync(hstate.data(), ch.so.state, n_rows, hipMemcpyDeviceToHost, st),
+		        "glm_score_multi_dosage_spa state copy");
+	}
 	PGH_HIP(hipStreamSynchronize(st), "glm_score_multi_dosage sync");
 	Scatter(b0, pb, c0, nt, hrows, out, tpos.data());
+	if (fu.kind == GlmScoreFollowUp::kSpa) {
+		Scatter(b0, pb, c0, nt, hp_spa, fu.p_spa, tpos.data());
+		Scatter(b0, pb, c0, nt, hstate, fu.state, tpos.data());
+	}
 	return PGH_OK;
 }
 
@@ -2031,7 +2049,8 @@ int GlmCheckBinaryEach(const double *phenotypes, uint32_t n_pheno, uint32_t n_ou
 }
 
 // pgh_glm_score_multi, pgh_glm_score_multi_spa and pgh_glm_score_multi_firth after the latter two's own argument
-// checks, and pgh_glm_score_multi_dosage (with_tracks: a dataset that holds dosage tracks is accepted).
+// checks, and pgh_glm_score_multi_dosage and pgh_glm_score_multi_dosage_spa (with_tracks: a dataset that holds dosage
+// tracks is accepted).
 int GlmScoreMultiEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                        uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
                        pgh_glm_row *out, const GlmScoreFollowUp &fu, char *errbuf, bool with_tracks = false) {
@@ -2106,6 +2125,16 @@ extern "C" int pgh_glm_score_multi_dosage(const pgh_dataset *ds, const pgh_subse
                                           uint32_t v_end, uint32_t n_pheno, const double *phenotypes, uint32_t n_covar,
                                           const double *covariates, pgh_glm_row *out, char *errbuf) {
 	return GlmScoreMultiEntry(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, {}, errbuf, true);
+}
+
+extern "C" int pgh_glm_score_multi_dosage_spa(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin,
+                                              uint32_t v_end, uint32_t n_pheno, const double *phenotypes,
+                                              uint32_t n_covar, const double *covariates, double spa_cutoff,
+                                              pgh_glm_row *out, double *p_spa, uint8_t *spa_state, char *errbuf) {
+	PGH_TRY(GlmCheckSpa(spa_cutoff, p_spa, spa_state, errbuf));
+	const GlmScoreFollowUp fu = {GlmScoreFollowUp::kSpa, spa_cutoff, p_spa, spa_state, nullptr};
+	return GlmScoreMultiEntry(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, fu, errbuf,
+	                          /*with_tracks=*/true);
 }
 
 extern "C" int pgh_glm_score_multi_spa(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin,

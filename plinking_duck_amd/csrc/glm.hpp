@@ -334,6 +334,17 @@ hipError_t LaunchGlmScoreDenseSpa(const RowView &view, uint32_t v0, uint32_t nv,
                                   const double *sums, const pgh_glm_row *rows, const double *t, double cutoff,
                                   uint32_t n_groups, void *stash, double *p_spa, uint8_t *state, hipStream_t stream);
 
+// ---- pgh_glm_score_multi_dosage_spa (glm_score_dense_dosage_spa.hip): the same for variants with a dosage track ----
+// LaunchGlmScoreDenseSpa for the rows (phenotype p < pb, listed variant i < nt) at p * nt + i of the chunk that
+// LaunchGlmScoreDenseDosage has just expanded: u16 and sums as it left them, rows and t ([pb][nt][kp + 3]) as
+// LaunchGlmScoreSolve did.  view gives sample_ct; its rows are not read.  The base is 2 where sum x > n and else 0, the
+// entries are the samples of N whose value is not exactly the base, and V_rest is 0 where every sample of N is an entry.
+hipError_t LaunchGlmScoreDenseDosageSpa(const RowView &view, const uint16_t *u16, uint32_t nt, const uint32_t *mask,
+                                        uint32_t pb, const double *b, const double *z0, const double *mz, uint32_t kp,
+                                        uint32_t k, const double *sums, const pgh_glm_row *rows, const double *t,
+                                        double cutoff, uint32_t n_groups, void *stash, double *p_spa, uint8_t *state,
+                                        hipStream_t stream);
+
 // ---- pgh_glm_score_multi_firth (glm_score_dense_firth.hip): approximate Firth estimates of the dense route's rows ----
 // For every row (phenotype p < pb, chunk variant i < nv) at p * nv + i: firth[p * nv + i], the contract's triple and
 // state (the score row's beta, se and p with state 0 where the row is not fitted or |stat| <= cutoff).  view, v0, nv,

@@ -1,5 +1,6 @@
 // glm_spa.hpp -- the saddlepoint arithmetic that GlmScoreSpaKernel (glm_score_spa.hip), GlmScoreDenseSpaKernel
-// (glm_score_dense_spa.hip) and GlmScoreSparseMultiSpaKernel (glm_score_sparse_multi_spa.hip) share: pi, K, the
+// (glm_score_dense_spa.hip), GlmScoreDenseDosageSpaKernel (glm_score_dense_dosage_spa.hip) and
+// GlmScoreSparseMultiSpaKernel (glm_score_sparse_multi_spa.hip) share: pi, K, the
 // safeguarded Newton step, a tail, and phase B, the iteration of one team over its stash of (g, mu) pairs (the contract
 // is pgh_glm_score_sparse_spa's in include/pgenhip.h); and SpaSparseRow, the walk of one sparse-resident row into the
 // stash that the first and the last instantiate with how they read a sample.

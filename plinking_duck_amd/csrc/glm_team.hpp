@@ -258,6 +258,60 @@ __device__ __forceinline__ uint32_t TeamStashMaskedRow(const uint32_t *row, cons
 	return count;
 }
 
+// TeamStashMaskedRow for a row of 16-bit values on the 2^-14 grid (glm_score_dense_dosage.hip's u16 row: 16 values per
+// mask word, 0xFFFF for neither a dosage nor a call), with the same geometry on purpose: a 16-sample word per thread,
+// 4,096 samples a step, TeamRankCounts over the words' popcounts, ascending sample order inside a word.  A thread loads
+// its word's 32 bytes as two 16-byte loads (row is 16-byte aligned and holds 16 mask_words values) and one mask word.
+// Sample i of the word is selected when its mask bit (bit 2 i) is set and its value is neither 0xFFFF nor `base`;
+// entry(s, v) -> the double2 that goes to st[rank] when rank < cap.  Returns the number selected, on every thread.
+//
+// The contract is TeamStashMaskedRow's, the order: for a row whose values restate 2-bit codes (v = code << 14) and the
+// selection that goes with it, the visits, the ranks and so a caller's fma chains are that walk's, bit for bit.
+template <class Entry>
+__device__ __forceinline__ uint32_t TeamStashMaskedU16Row(const uint16_t *row, const uint32_t *m, uint32_t mask_words,
+                                                          uint32_t base, double2 *__restrict__ st, uint32_t cap, int tid,
+                                                          int lane, int wave, Entry entry) {
+	const uint4 *row4 = reinterpret_cast<const uint4 *>(row);
+	uint32_t count = 0;
+	for (uint32_t w0 = 0, step = 0; w0 < mask_words; w0 += kTeamBlock, step++) {
+		const uint32_t wi = w0 + tid;
+		uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
+		uint32_t em = 0; // bit i: sample 16 wi + i is selected
+		if (wi < mask_words) {
+			lo = row4[2u * wi];
+			hi = row4[2u * wi + 1u];
+			const uint32_t mm = m[wi];
+			const uint32_t d[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+			for (uint32_t i = 0; i < 16u; i++) {
+				// bit 16 of x + 0xffff says whether the 16-bit x is not 0: integer arithmetic, because sixteen
+				// comparisons in flight hold sixteen pairs of scalar registers, more than there are to spare
+				const uint32_t v = (d[i >> 1] >> (16u * (i & 1u))) & 0xffffu;
+				const uint32_t keep = (((v ^ 0xffffu) + 0xffffu) & ((v ^ base) + 0xffffu)) >> 16;
+				em |= (keep & (mm >> (2u * i)) & 1u) << i;
+			}
+		}
+		uint32_t total;
+		uint32_t pos = count + TeamRankCounts(static_cast<uint32_t>(__popc(em)), step, lane, wave, &total);
+		while (em) {
+			const uint32_t i = static_cast<uint32_t>(__ffs(static_cast<int>(em)) - 1);
+			em &= em - 1u;
+			// (a chain of selects, not an indexed array, which would live in scratch memory)
+			const uint32_t h = i >> 1;
+			const uint32_t a = h & 1u ? lo.y : lo.x, b = h & 1u ? lo.w : lo.z, c = h & 1u ? hi.y : hi.x,
+			               e = h & 1u ? hi.w : hi.z;
+			const uint32_t pair2 = h & 4u ? (h & 2u ? e : c) : (h & 2u ? b : a);
+			const double2 pair = entry(16u * wi + i, (pair2 >> (16u * (i & 1u))) & 0xffffu);
+			if (pos < cap) {
+				st[pos] = pair;
+			}
+			pos++;
+		}
+		count += total;
+	}
+	return count;
+}
+
 // The rows of a sparse-resident dataset (SparseView's arrays) that one launch of an entry kernel covers.
 struct SparseRows {
 	const int32_t *row_of;
