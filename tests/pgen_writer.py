@@ -80,15 +80,30 @@ def _difflist(ids: np.ndarray, vals: np.ndarray | None, n_samples: int) -> bytes
 _INV = np.array([2, 1, 0, 3], dtype=np.uint8)
 
 
-def encode_record(kind: int, g: np.ndarray, base: np.ndarray | None) -> bytes:
+def _dirty(data: bytes, used_bits: int) -> bytes:
+    """data with the bits of its last byte above the `used_bits` the format reads set (used_bits in 1..7)."""
+    return data[:-1] + bytes([data[-1] | (0xFF << used_bits) & 0xFF])
+
+
+def encode_record(kind: int, g: np.ndarray, base: np.ndarray | None, pair: tuple[int, int] | None = None,
+                  dirty_tail: bool = False, keep: np.ndarray | None = None) -> bytes:
+    """pair: the (low, high) codes of a type-1 record (default: the row's two most frequent codes).
+    dirty_tail: set the bits the format leaves unused -- behind sample N-1 in the last byte of a type-0 record, or
+    in the last byte of a type-1 record's bit array.
+    keep: samples an LD record lists in its difflist even where their value equals the base's."""
     n = len(g)
     if kind == 0:
-        return _pack2(g)
+        return _dirty(_pack2(g), 2 * (n % 4)) if dirty_tail and n % 4 else _pack2(g)
     if kind == 1:
-        counts = np.bincount(g, minlength=4)
-        low, high = sorted(np.argsort(-counts, kind="stable")[:2].tolist())
+        if pair is None:
+            counts = np.bincount(g, minlength=4)
+            low, high = sorted(np.argsort(-counts, kind="stable")[:2].tolist())
+        else:
+            low, high = pair
         code = low * 4 + (high - low)
         bits = np.packbits((g == high).astype(np.uint8), bitorder="little").tobytes()
+        if dirty_tail and n % 8:
+            bits = _dirty(bits, n % 8)
         diff = np.flatnonzero((g != low) & (g != high))
         return bytes([code]) + bits + _difflist(diff, g[diff], n)
     if kind in (4, 6, 7):
@@ -99,6 +114,8 @@ def encode_record(kind: int, g: np.ndarray, base: np.ndarray | None) -> bytes:
         assert base is not None
         target = g if kind == 2 else _INV[g]  # type 3 is patched first, then inverted
         diff = np.flatnonzero(target != base)
+        if keep is not None:
+            diff = np.union1d(diff, np.asarray(keep, dtype=diff.dtype))
         return _difflist(diff, target[diff], n)
     raise ValueError(kind)
 
@@ -127,6 +144,17 @@ def phase_track(g: np.ndarray, rng: np.random.Generator) -> bytes:
     head = np.packbits(np.concatenate([[1], present]).astype(np.uint8), bitorder="little").tobytes()
     info = rng.integers(0, 2, int(present.sum())).astype(np.uint8)
     return head + np.packbits(info, bitorder="little").tobytes()
+
+
+def exact_phase_track(explicit: bool, present: np.ndarray | None, info: np.ndarray) -> bytes:
+    """The phase track of given content.  explicit False: info holds one phaseinfo bit per het (present is not read);
+    explicit True: present holds one phasepresent bit per het and info one phaseinfo bit per flagged het."""
+    if not explicit:
+        return np.packbits(np.concatenate([[0], info]).astype(np.uint8), bitorder="little").tobytes()
+    present = np.asarray(present, dtype=np.uint8)
+    assert len(info) == int(present.sum())
+    head = np.packbits(np.concatenate([[1], present]).astype(np.uint8), bitorder="little").tobytes()
+    return head + np.packbits(np.asarray(info, dtype=np.uint8), bitorder="little").tobytes()
 
 
 def dosage_track(kind: int, dos16: np.ndarray, n: int) -> bytes:
@@ -186,13 +214,16 @@ def multiallelic_track(g: np.ndarray, alleles: int, rng: np.random.Generator) ->
 
 def write_pgen(path: str, geno: np.ndarray, kinds: list[int], dosage: np.ndarray | None = None,
                dosage_kinds: list[int] | None = None, phase_rng: np.random.Generator | None = None,
-               allele_cts: list[int] | None = None, aux1_rng: np.random.Generator | None = None) -> None:
+               allele_cts: list[int] | None = None, aux1_rng: np.random.Generator | None = None,
+               phase_tracks: list | None = None, record_opts: list | None = None) -> None:
     """geno: [M][N] codes.  Writes mode 0x10 with 8-bit vrtypes and 4-byte record lengths.
     dosage: [M][N] uint16 (65535 = no explicit dosage), written per variant as dosage_kinds[v] (0 = no track).
     phase_rng: give every variant with a het a phase track (bit 0x10) of random content.
     allele_cts: alleles per variant (REF + ALTs); a variant with more than two gets a multiallelic track (0x08)
     behind its main track -- geno holds its calls with the ALT alleles collapsed, which is what PgrGet returns --
-    and the header carries one byte of ALT allele count per variant."""
+    and the header carries one byte of ALT allele count per variant.
+    phase_tracks: per variant None or the (explicit, present, info) of exact_phase_track, in place of phase_rng.
+    record_opts: per variant None or encode_record's options (pair, dirty_tail, keep)."""
     m, n = geno.shape
     records = []
     kinds = list(kinds)
@@ -200,19 +231,30 @@ def write_pgen(path: str, geno: np.ndarray, kinds: list[int], dosage: np.ndarray
     for v in range(m):
         g = geno[v].astype(np.uint8)
         k = kinds[v]
-        rec = encode_record(k, g, base)
+        rec = encode_record(k, g, base, **((record_opts[v] if record_opts is not None else None) or {}))
         if k not in (2, 3):
             base = g
         if allele_cts is not None and allele_cts[v] > 2:
             rec += multiallelic_track(g, allele_cts[v], aux1_rng or np.random.default_rng(v))
             kinds[v] |= 0x08
-        if phase_rng is not None and (g == 1).any():
+        if phase_tracks is not None and phase_tracks[v] is not None:
+            explicit, present, info = phase_tracks[v]
+            assert len(present if explicit else info) == int((g == 1).sum()), "one bit per het"
+            rec += exact_phase_track(explicit, present, info)
+            kinds[v] |= 0x10
+        elif phase_rng is not None and (g == 1).any():
             rec += phase_track(g, phase_rng)
             kinds[v] |= 0x10
         if dosage is not None and dosage_kinds[v]:
             rec += dosage_track(dosage_kinds[v], dosage[v], n)
             kinds[v] |= dosage_kinds[v]
         records.append(rec)
+    write_records(path, n, kinds, records, allele_cts)
+
+
+def write_records(path: str, n: int, kinds: list[int], records: list[bytes], allele_cts: list[int] | None = None) -> None:
+    """The file of finished records (kinds: their vrtype bytes): header, tables, record bytes."""
+    m = len(records)
     blocks = (m + 65535) // 65536
     head = bytearray([0x6C, 0x1B, 0x10]) + int(m).to_bytes(4, "little") + int(n).to_bytes(4, "little")
     ac_bytes = 1 if allele_cts is not None else 0
