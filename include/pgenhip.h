@@ -729,8 +729,8 @@ int pgh_glm_score_multi(const pgh_dataset *ds, const pgh_subset *subset, uint32_
  * the other phenotypes or its place among them, of v_begin, the variant chunk, the phenotype block, which other variants
  * carry tracks, the window the dataset was opened with or PGH_GLM_SCORE_SCRATCH_BYTES (which here also holds 144 bytes
  * per 64 samples for every variant in flight), and the same call returns the same bytes every time.
- * Saddlepoint p-values over tracks: pgh_glm_score_multi_dosage_spa.  Not offered: a Firth follow-up over tracks
- * (pgh_glm_score_multi_firth's walk reads 2-bit rows), shard groups, a table function. */
+ * Saddlepoint p-values over tracks: pgh_glm_score_multi_dosage_spa.  Approximate Firth estimates over tracks:
+ * pgh_glm_score_multi_dosage_firth.  Not offered: shard groups, a table function. */
 int pgh_glm_score_multi_dosage(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                                uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
                                pgh_glm_row *out, char *errbuf);
@@ -876,7 +876,8 @@ int pgh_glm_score_multi_spa(const pgh_dataset *ds, const pgh_subset *subset, uin
  * block, which other variants carry tracks, the window the dataset was opened with, PGH_GLM_SCORE_SCRATCH_BYTES or the
  * grid, and the same call returns the same bytes every time.  With a full track E = N, so the iteration passes over
  * every sample of the row, not over its carriers.
- * Not offered: Firth over tracks, shard groups, a table function. */
+ * Approximate Firth estimates over tracks: pgh_glm_score_multi_dosage_firth.  Not offered: Firth and saddlepoint in one
+ * call, shard groups, a table function. */
 int pgh_glm_score_multi_dosage_spa(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                                    uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
                                    double spa_cutoff, pgh_glm_row *out, double *p_spa, uint8_t *spa_state, char *errbuf);
@@ -925,8 +926,8 @@ typedef struct pgh_glm_firth_row {
  * phenotype) row of the dense route beyond a cutoff (the "approximate Firth" of Mbatchou et al. 2021: the covariate
  * effects are held fixed at the null fit and only the variant's own coefficient is estimated, under Firth's penalty).
  * Arguments, argument checks, error texts and refusals are pgh_glm_score_multi's: a sparse-resident dataset, a shard
- * group, a dataset with dosage tracks (pgh_glm_score_multi_dosage gives such a dataset's score rows, without the Firth
- * estimate: this entry's walk reads 2-bit rows), 0/1 phenotypes, cases and controls.  In addition firth_cutoff must be at least
+ * group, a dataset with dosage tracks (pgh_glm_score_multi_dosage_firth gives such a dataset's score rows and Firth
+ * estimates: this entry's walk reads 2-bit rows), 0/1 phenotypes, cases and controls.  In addition firth_cutoff must be at least
  * 0.1 (+infinity: never apply it; NaN or a smaller value is PGH_ERR_ARG, "firth_cutoff must be at least 0.1"), and
  * firth must not be NULL ("null firth"); it has out's layout, element (v - v_begin) * n_pheno + p.  On any error both
  * outputs are untouched.  v_begin == v_end is PGH_OK.
@@ -987,6 +988,39 @@ typedef struct pgh_glm_firth_row {
 int pgh_glm_score_multi_firth(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                               uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
                               double firth_cutoff, pgh_glm_row *out, pgh_glm_firth_row *firth, char *errbuf);
+/* pgh_glm_score_multi_dosage with pgh_glm_score_multi_firth's APPROXIMATE FIRTH estimate beside the one-step score
+ * estimate: the Firth follow-up over a dense-resident dataset that may hold DOSAGE TRACKS.  Arguments, argument checks,
+ * error texts and the layout of the two outputs are pgh_glm_score_multi_firth's, except that a dataset whose
+ * pgh_info.dosage_variant_ct is not 0 is accepted: firth_cutoff must be at least 0.1 (+infinity: never apply it; NaN or
+ * a smaller value is PGH_ERR_ARG, "firth_cutoff must be at least 0.1"), firth must not be NULL ("null firth").  The
+ * refusals are pgh_glm_score_multi_dosage's: a sparse-resident dataset, a shard group, a phenotype that is not 0 / 1, a
+ * phenotype without a case or a control, the latter two followed by the phenotype's index.  On any refusal both outputs
+ * are untouched; v_begin == v_end is PGH_OK.
+ *
+ * out is pgh_glm_score_multi_dosage's result for the same arguments bit for bit; its firth byte stays 0.
+ * firth[i].state and values mean what they mean for pgh_glm_score_multi_firth: state 0 with NaN for a row that is not
+ * fitted, state 0 with out's beta, se and p bit for bit where |stat| <= firth_cutoff, state 1 with the Firth values,
+ * state 2 with out's values bit for bit; pad is zero.
+ *
+ * Definition: pgh_glm_score_multi_firth's, word for word, under pgh_glm_score_multi_dosage's genotype rule
+ * (x_i = value / 16384 where there is an explicit dosage, the call's ALT count otherwise; M = the samples with neither;
+ * N = S \ M).  E = the samples of N with x_i != 0 exactly (v != 0 and v != 0xFFFF on the 2^-14 grid).  G, K through
+ * K'''', l*, F, H, the root rules 1-9, the state-2 conditions and the result are unchanged.  There is no base code
+ * here: a sample with x = 0 contributes a constant of l*, whatever the row's majority.
+ *
+ * A variant without a track, whatever its neighbours carry, and a variant whose track restates its calls get
+ * pgh_glm_score_multi_firth's pair (out, firth) for the same calls in a file without tracks, bit for bit; a dataset
+ * without any track gets pgh_glm_score_multi_firth's bytes.
+ *
+ * A row's pair is a function of its variant's calls and track, its own phenotype, the covariates, the subset and
+ * firth_cutoff only: not of the other phenotypes or its place among them, of v_begin, the variant chunk, the phenotype
+ * block, which other variants carry tracks, the window the dataset was opened with, PGH_GLM_SCORE_SCRATCH_BYTES or the
+ * grid, and the same call returns the same bytes every time.  With a full track E is usually all of N, so each
+ * evaluation of the iteration passes over every sample of the row, not over its carriers.
+ * Not offered: Firth and saddlepoint in one call, a Firth-penalised null fit, shard groups, a table function. */
+int pgh_glm_score_multi_dosage_firth(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
+                                     uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
+                                     double firth_cutoff, pgh_glm_row *out, pgh_glm_firth_row *firth, char *errbuf);
 /* pgh_glm_score_sparse with pgh_glm_score_multi_firth's APPROXIMATE FIRTH estimate beside the one-step score estimate,
  * for every variant of [v_begin, v_end) of a SPARSE-RESIDENT dataset beyond a cutoff, from the variants' entries: a
  * row costs in proportion to the samples that differ from its base code.  Arguments, argument checks, error texts and

@@ -1567,8 +1567,9 @@ void GlmScoreBlockCall::Scatter(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t 
 // through the same kernels, from the first such variant to the last; the ones with a track are listed, expanded into
 // d_u16 / d_eff and contracted by glm_score_dense_dosage.hip, and their rows replace what the first pass left for them.
 // With the saddlepoint follow-up (pgh_glm_score_multi_dosage_spa) the first pass may leave a triple for a track variant
-// from its calls; the track pass (glm_score_dense_dosage_spa.hip over d_u16) overwrites it.  No entry point brings a
-// Firth follow-up here with tracks.
+// from its calls; the track pass (glm_score_dense_dosage_spa.hip over d_u16) overwrites it.  The same holds for the
+// Firth follow-up (pgh_glm_score_multi_dosage_firth) and its pgh_glm_firth_row: the track pass
+// (glm_score_dense_dosage_firth.hip over d_u16) writes every listed row.
 struct GlmScoreMultiCall : GlmScoreBlockCall {
 	double *d_b;
 	uint32_t *d_mask;
@@ -1677,12 +1678,20 @@ int GlmScoreMultiCall::RunTracks(uint32_t b0, uint32_t pb, uint32_t c0, uint32_t
 		        "glm_score_multi_dosage_spa p copy");
 		PGH_HIP(hipMemcpyAsync(hstate.data(), ch.so.state, n_rows, hipMemcpyDeviceToHost, st),
 		        "glm_score_multi_dosage_spa state copy");
+	} else if (fu.kind == GlmScoreFollowUp::kFirth) {
+		PGH_HIP(pgh::LaunchGlmScoreDenseDosageFirth(ds->View(), d_u16, nt, d_mask, pb, d_b, k, ch.rows, fu.cutoff,
+		                                            plan.n_groups, d_stash, ch.firth, st),
+		        "glm_score_multi_dosage_firth kernel");
+		PGH_HIP(hipMemcpyAsync(hfirth.data(), ch.firth, sizeof(pgh_glm_firth_row) * nt * pb, hipMemcpyDeviceToHost, st),
+		        "glm_score_multi_dosage_firth rows copy");
 	}
 	PGH_HIP(hipStreamSynchronize(st), "glm_score_multi_dosage sync");
 	Scatter(b0, pb, c0, nt, hrows, out, tpos.data());
 	if (fu.kind == GlmScoreFollowUp::kSpa) {
 		Scatter(b0, pb, c0, nt, hp_spa, fu.p_spa, tpos.data());
 		Scatter(b0, pb, c0, nt, hstate, fu.state, tpos.data());
+	} else if (fu.kind == GlmScoreFollowUp::kFirth) {
+		Scatter(b0, pb, c0, nt, hfirth, fu.firth, tpos.data());
 	}
 	return PGH_OK;
 }
@@ -1975,7 +1984,7 @@ int GlmScoreMultiOne(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v
 	PGH_ENTER(ds);
 	GlmScoreMultiCall c {{ds, subset, v_begin, v_end - v_begin, n_pheno, k, phenotypes, covariates, fu, errbuf,
 	                      "glm_score_multi", true}};
-	c.tracks = ds->dos_rows != 0; // pgh_glm_score_multi_dosage alone lets such a dataset through
+	c.tracks = ds->dos_rows != 0; // the pgh_glm_score_multi_dosage* entries alone let such a dataset through
 	return GlmScoreBlocksRun(c, out);
 }
 
@@ -2049,8 +2058,8 @@ int GlmCheckBinaryEach(const double *phenotypes, uint32_t n_pheno, uint32_t n_ou
 }
 
 // pgh_glm_score_multi, pgh_glm_score_multi_spa and pgh_glm_score_multi_firth after the latter two's own argument
-// checks, and pgh_glm_score_multi_dosage and pgh_glm_score_multi_dosage_spa (with_tracks: a dataset that holds dosage
-// tracks is accepted).
+// checks, and pgh_glm_score_multi_dosage, pgh_glm_score_multi_dosage_spa and pgh_glm_score_multi_dosage_firth
+// (with_tracks: a dataset that holds dosage tracks is accepted).
 int GlmScoreMultiEntry(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin, uint32_t v_end,
                        uint32_t n_pheno, const double *phenotypes, uint32_t n_covar, const double *covariates,
                        pgh_glm_row *out, const GlmScoreFollowUp &fu, char *errbuf, bool with_tracks = false) {
@@ -2133,6 +2142,16 @@ extern "C" int pgh_glm_score_multi_dosage_spa(const pgh_dataset *ds, const pgh_s
                                               pgh_glm_row *out, double *p_spa, uint8_t *spa_state, char *errbuf) {
 	PGH_TRY(GlmCheckSpa(spa_cutoff, p_spa, spa_state, errbuf));
 	const GlmScoreFollowUp fu = {GlmScoreFollowUp::kSpa, spa_cutoff, p_spa, spa_state, nullptr};
+	return GlmScoreMultiEntry(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, fu, errbuf,
+	                          /*with_tracks=*/true);
+}
+
+extern "C" int pgh_glm_score_multi_dosage_firth(const pgh_dataset *ds, const pgh_subset *subset, uint32_t v_begin,
+                                                uint32_t v_end, uint32_t n_pheno, const double *phenotypes,
+                                                uint32_t n_covar, const double *covariates, double firth_cutoff,
+                                                pgh_glm_row *out, pgh_glm_firth_row *firth, char *errbuf) {
+	PGH_TRY(GlmCheckFirth(firth_cutoff, firth, errbuf));
+	const GlmScoreFollowUp fu = {GlmScoreFollowUp::kFirth, firth_cutoff, nullptr, nullptr, firth};
 	return GlmScoreMultiEntry(ds, subset, v_begin, v_end, n_pheno, phenotypes, n_covar, covariates, out, fu, errbuf,
 	                          /*with_tracks=*/true);
 }

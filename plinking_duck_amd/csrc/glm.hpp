@@ -354,6 +354,16 @@ hipError_t LaunchGlmScoreDenseFirth(const RowView &view, uint32_t v0, uint32_t n
                                     const double *b, uint32_t k, const pgh_glm_row *rows, double cutoff,
                                     uint32_t n_groups, void *stash, pgh_glm_firth_row *firth, hipStream_t stream);
 
+// ---- pgh_glm_score_multi_dosage_firth (glm_score_dense_dosage_firth.hip): the same for variants with a dosage track ----
+// LaunchGlmScoreDenseFirth for the rows (phenotype p < pb, listed variant i < nt) at p * nt + i of the chunk that
+// LaunchGlmScoreDenseDosage has just expanded: u16 as it left them, rows as LaunchGlmScoreSolve did.  view gives
+// sample_ct; its rows are not read.  The entries are the samples of N whose value is not exactly 0, x = value / 16384.
+// Every one of the nt x pb rows of firth is written.
+hipError_t LaunchGlmScoreDenseDosageFirth(const RowView &view, const uint16_t *u16, uint32_t nt, const uint32_t *mask,
+                                          uint32_t pb, const double *b, uint32_t k, const pgh_glm_row *rows,
+                                          double cutoff, uint32_t n_groups, void *stash, pgh_glm_firth_row *firth,
+                                          hipStream_t stream);
+
 // ---- pgh_burden_sparse (burden_sparse.hip): the linear fit's sums of a weighted burden per variant set ----
 // What the kernel leaves per set beside its sums row.
 struct BurdenAux {

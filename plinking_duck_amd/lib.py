@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = [
     "pgh_reader_unpack_start", "pgh_reader_unpack_wait", "pgh_get_2bit", "pgh_get_counts", "pgh_get_missingness", "pgh_get_int8", "pgh_get_dosage_f64", "pgh_get_phased",
     "pgh_tally_start", "pgh_tally_request", "pgh_tally_wait", "pgh_tally_counts", "pgh_tally_hwe_lnp",
     "pgh_tally_sample_missing", "pgh_tally_destroy", "pgh_tally_passes_started", "pgh_host_alloc", "pgh_host_free", "pgh_trim_device_cache",
-    "pgh_reader_error", "pgh_open_sparse", "pgh_get_sparse_info", "pgh_sparse_opens_started", "pgh_glm", "pgh_glm_multi", "pgh_glm_sparse", "pgh_glm_score_sparse", "pgh_glm_score_multi", "pgh_glm_score_multi_dosage", "pgh_glm_score_multi_dosage_spa", "pgh_glm_score_sparse_spa", "pgh_glm_score_multi_spa", "pgh_glm_score_multi_firth", "pgh_glm_score_sparse_firth", "pgh_glm_score_sparse_multi", "pgh_glm_sparse_multi", "pgh_glm_score_sparse_multi_spa", "pgh_glm_score_sparse_multi_firth", "pgh_burden_sparse", "pgh_skat_sparse", "pgh_skat_p_from_lambda", "pgh_symmetric_eigenvalues", "pgh_score_sparse", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
+    "pgh_reader_error", "pgh_open_sparse", "pgh_get_sparse_info", "pgh_sparse_opens_started", "pgh_glm", "pgh_glm_multi", "pgh_glm_sparse", "pgh_glm_score_sparse", "pgh_glm_score_multi", "pgh_glm_score_multi_dosage", "pgh_glm_score_multi_dosage_spa", "pgh_glm_score_sparse_spa", "pgh_glm_score_multi_spa", "pgh_glm_score_multi_firth", "pgh_glm_score_multi_dosage_firth", "pgh_glm_score_sparse_firth", "pgh_glm_score_sparse_multi", "pgh_glm_sparse_multi", "pgh_glm_score_sparse_multi_spa", "pgh_glm_score_sparse_multi_firth", "pgh_burden_sparse", "pgh_skat_sparse", "pgh_skat_p_from_lambda", "pgh_symmetric_eigenvalues", "pgh_score_sparse", "pgh_glm_p_from_t", "pgh_glm_p_from_z", "pgh_hwe_lnp", "pgh_hwe_xchr_lnp", "pgh_hwe_lnp_batch", "pgh_hwe_lnp_batch_dev", "pgh_hwe_xchr_lnp_batch",
     "pgh_king_counts", "pgh_king_table", "pgh_king_kinship",
     "pgh_ld_window_sums", "pgh_ld_prune", "pgh_ld_exceeds", "pgh_ld_scores", "pgh_ld_r2",
     "pgh_grm", "pgh_grm_standardize",
@@ -261,6 +261,7 @@ def _load():
         "pgh_glm_score_multi_dosage_spa": (C.c_int, [vp, vp, u32, u32, u32, vp, u32, vp, C.c_double, vp, vp, vp, cp]),
         "pgh_glm_score_sparse_multi_spa": (C.c_int, [vp, vp, u32, u32, u32, vp, u32, vp, C.c_double, vp, vp, vp, cp]),
         "pgh_glm_score_multi_firth": (C.c_int, [vp, vp, u32, u32, u32, vp, u32, vp, C.c_double, vp, vp, cp]),
+        "pgh_glm_score_multi_dosage_firth": (C.c_int, [vp, vp, u32, u32, u32, vp, u32, vp, C.c_double, vp, vp, cp]),
         "pgh_glm_score_sparse_multi_firth": (C.c_int, [vp, vp, u32, u32, u32, vp, u32, vp, C.c_double, vp, vp, cp]),
         "pgh_glm_score_sparse_firth": (C.c_int, [vp, vp, u32, u32, vp, u32, vp, C.c_double, vp, vp, cp]),
         "pgh_burden_sparse": (C.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, cp]),
@@ -1172,6 +1173,25 @@ class Dataset:
         _check(_lib.pgh_glm_score_multi_firth(self._h, subset._h if subset else None, v0, v1, y.shape[0], _ptr(y),
                                               z.shape[0], _ptr(z) if z.size else None, float(firth_cutoff), _ptr(rows),
                                               _ptr(firth), eb), eb)
+        return dict(Dataset._glm_multi_rows_dict(rows), beta_firth=firth["beta"].copy(), se_firth=firth["se"].copy(),
+                    p_firth=firth["p"].copy(), firth_state=firth["state"].copy())
+
+    def glm_score_multi_dosage_firth(self, phenotypes, covariates=None, firth_cutoff: float = 2.0,
+                                     v_begin: int | None = None, v_end: int | None = None,
+                                     subset: Subset | None = None) -> dict:
+        """pgh_glm_score_multi_dosage_firth: glm_score_multi_firth() over a dataset that may hold dosage tracks, with
+        glm_score_multi_dosage()'s genotype values.  Returns glm_score_multi_firth()'s dict: the rows are
+        glm_score_multi_dosage()'s, and beta_firth, se_firth, p_firth and firth_state are of shape (V, P)."""
+        v0, v1, y, z = Dataset._score_multi_args(self, phenotypes, covariates, v_begin, v_end, subset)
+        if not firth_cutoff >= 0.1:
+            raise ValueError(f"firth_cutoff must be at least 0.1, got {firth_cutoff}")
+        shape = (max(0, v1 - v0), y.shape[0])
+        rows = np.zeros(shape, dtype=GLM_ROW_DTYPE)
+        firth = np.zeros(shape, dtype=GLM_FIRTH_ROW_DTYPE)
+        eb = _errbuf()
+        _check(_lib.pgh_glm_score_multi_dosage_firth(self._h, subset._h if subset else None, v0, v1, y.shape[0], _ptr(y),
+                                                     z.shape[0], _ptr(z) if z.size else None, float(firth_cutoff),
+                                                     _ptr(rows), _ptr(firth), eb), eb)
         return dict(Dataset._glm_multi_rows_dict(rows), beta_firth=firth["beta"].copy(), se_firth=firth["se"].copy(),
                     p_firth=firth["p"].copy(), firth_state=firth["state"].copy())
 

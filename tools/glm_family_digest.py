@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """One SHA-256 per case over the result bytes of the GLM family (pgh_glm, pgh_glm_multi, pgh_glm_sparse,
-pgh_glm_score_sparse, pgh_glm_score_sparse_spa, pgh_glm_score_sparse_firth, pgh_glm_score_sparse_multi, pgh_glm_score_sparse_multi_spa, pgh_glm_score_sparse_multi_firth, pgh_glm_sparse_multi, pgh_glm_score_multi, pgh_glm_score_multi_dosage, pgh_glm_score_multi_spa,
+pgh_glm_score_sparse, pgh_glm_score_sparse_spa, pgh_glm_score_sparse_firth, pgh_glm_score_sparse_multi, pgh_glm_score_sparse_multi_spa, pgh_glm_score_sparse_multi_firth, pgh_glm_sparse_multi, pgh_glm_score_multi, pgh_glm_score_multi_dosage, pgh_glm_score_multi_dosage_firth, pgh_glm_score_multi_spa,
 pgh_glm_score_multi_firth, pgh_burden_sparse), pgh_score_sparse, and the plink_ld pair sums and sparse counts that share their wave sums: the
 paths a change to the family's kernels, host staging, scratch layout or chunk loops can touch.  Two builds of the library
 compute the same rows bit for bit exactly when their outputs of this tool are equal line for line; PGENHIP_LIB names
@@ -143,6 +143,10 @@ emit("glm_score_multi_dosage tracks P=7 two patterns", dt.glm_score_multi_dosage
 emit("glm_score_multi_dosage tracks subset", dt.glm_score_multi_dosage(phenos(rng_t, n_keep, 3, Zts, 1, "logistic"), Zts,
                                                                          subset=st, v_begin=7, v_end=M - 3))
 emit("glm_score_multi_dosage no tracks", ds.glm_score_multi_dosage(Yt, Zt))
+# pgh_glm_score_multi_dosage_firth on the same draws, at a cutoff low enough to apply rows of these small files
+firth_t = dt.glm_score_multi_dosage_firth(Yt, Zt, firth_cutoff=1.0)
+emit("glm_score_multi_dosage_firth tracks P=7", firth_t, note=f" ({int((firth_t['firth_state'] == 1).sum())} applied)")
+emit("glm_score_multi_dosage_firth no tracks", ds.glm_score_multi_dosage_firth(Yt, Zt, firth_cutoff=1.0))
 for d in (ss, st, ds, dt):
     d.close()
 
