@@ -204,7 +204,7 @@ const pgh_dataset *pgh_shard(const pgh_dataset *ds, uint32_t k);
  *     counts), pgh_dosage_sums(_dev), pgh_ld_pairs(_dev), the reader's pgh_get_counts;
  *   - per-sample products are zero-length, PGH_OK with nothing written: pgh_unpack_range, pgh_unpack_samples,
  *     pgh_dosage_unpack(_samples), the reader's per-sample calls, pgh_sample_counts, pgh_missing_per_sample,
- *     pgh_tally_sample_missing, pgh_score, pgh_score_counts, pgh_score_sparse.  A score plan made for it scores
+ *     pgh_tally_sample_missing, pgh_score, pgh_score_counts, pgh_score_sparse, pgh_het.  A score plan made for it scores
  *     nothing: pgh_score_run_dev zeroes its (raw-sample) outputs;
  *   - everything that fits or compares samples returns PGH_ERR_ARG, "the sample subset is empty ...", before any
  *     launch: pgh_glm, pgh_glm_multi, pgh_glm_sparse, pgh_glm_score_sparse(_spa), pgh_burden_sparse, pgh_skat_sparse, pgh_pca,
@@ -247,6 +247,8 @@ void pgh_subset_destroy(pgh_subset *ss);
  *                                 PGH_ERR_ARG ("too few variants ...").  pgh_pca_streamed alone wants ascending order.
  *   pgh_king_counts / _table,     any order; a repeated variant counts each time (pgh_grm: with the freq of each of
  *   pgh_grm                       its entries); n_var == 0: PGH_ERR_ARG ("n_var must be at least 1")
+ *   pgh_het                       any order, the same bytes from each; a repeated variant counts each time (with the freq
+ *                                 of each of its entries); n_var == 0: PGH_OK, every row {0.0, NaN, 0, 0, 0}
  *   pgh_ld_window_sums            any order; a repeated variant is a repeated row and column of the rectangle;
  *                                 n_var == 0: PGH_ERR_ARG (no rectangle fits: "variant rectangle ... is empty")
  *   pgh_ld_prune, pgh_ld_scores   STRICTLY INCREASING, hence no repeats: anything else is PGH_ERR_ARG ("the variant
@@ -1465,6 +1467,64 @@ int pgh_grm(const pgh_dataset *ds, const pgh_subset *subset, uint32_t variant_be
 /* The standardisation above on the host: returns p, or NaN when the variant is skipped; z[0..2] is written only when
  * it is not (z may be NULL).  pgh_grm's tables are this function of the counts, bit for bit. */
 double pgh_grm_standardize(uint32_t het, uint32_t alt, uint32_t called, double z[3]);
+
+/* ---- per-sample inbreeding coefficients, plink's --het, in exact fixed point ------- */
+
+/* Per output sample (subset order, or raw order without a subset): the observed and the expected number of homozygous
+ * calls over the variants of the call and the method-of-moments inbreeding coefficient F.  Hardcalls only (dosage and
+ * phase tracks are not read).  The formulas below are the definition; they have not been compared with plink's output.
+ *
+ * Per variant v, with het, alt and called counted over the output samples, in this exact sequence of FP64 operations
+ * on the host, one IEEE operation per statement:
+ *   p = double(het + 2 alt) / double(2 called)        or p = freq[v] when the caller supplies freq
+ * and v is SKIPPED when called == 0, or when p is not finite, p <= 0 or p >= 1 (a NaN freq[v] skips v).  Otherwise
+ *   q = 1 - p      u = (2 p) q
+ *   with PGH_HET_SMALL_SAMPLE:   r = double(2 called) / double(2 called - 1)      u = u r
+ *   e = 1 - u                                                                      (0 <= e <= 1)
+ * pgh_het_expected is this function of the counts.
+ *
+ * Fixed point.  L is the smallest integer with 2^L >= max(n_var, 1), n_var being the CALLER's count (also inside a
+ * shard group); k = 62 - L = pgh_het_scale(n_var); q_v = llrint(e_v 2^k).  Per sample i
+ *   e_sum_i = sum of q_v over the used variants at which i is called         (an exact int64, at most 2^62)
+ *   e_hom   = ldexp((double)e_sum, -k)
+ *   hom_ct  = used variants at which i's call is 0 or 2,    obs_ct = used variants at which i has a call
+ *   f       = (double(hom_ct) - e_hom) / (double(obs_ct) - e_hom)            (NaN when obs_ct == 0 or the divisor is 0)
+ * A repeated list entry counts each time; the order of the list does not matter; n_var == 0 is PGH_OK with every row
+ * {0.0, NaN, 0, 0, 0}.  Under the empty subset nothing is written to out, every variant is skipped and *n_used is 0.
+ *
+ * Determinism.  Everything summed is an integer, so the same global variants give the same BYTES from a range or the
+ * equal list, from any permutation of the list, from the whole file, a window of it or a shard group, on every run,
+ * from any thread, and whatever the kernel's grid is: PGH_HET_SLICES (environment variable, read at every call) sets
+ * the number of variant slices of the grid, 1 to 65535; by default it is chosen from the list length.  A sample's row
+ * does not depend on the samples outside the subset except through het, alt and called.
+ *
+ * out: one row per output sample.  used (unless NULL): n_var bytes, 1 where the call's entry was used, else 0.
+ * *n_used (unless NULL): the number of used entries.  PGH_ERR_ARG, every output untouched: a null ds or out ("null
+ * argument"), unknown flag bits, freq together with PGH_HET_SMALL_SAMPLE (the correction needs the counts' own n), a
+ * sparse-resident dataset ("needs a dense-resident dataset"), and the range, list and subset refusals of every entry
+ * point.  A shard group is accepted: every shard sums its share under the call's k, the integers are added and e_hom
+ * and f are formed once.  There is no _dev form: the tables are built on the host.
+ * Not offered: a table function, sparse-resident datasets, dosage-weighted heterozygosity, and the male-haploid
+ * frequency rule of plink's --check-sex (a caller passes freq and a chrX list). */
+enum { PGH_HET_SMALL_SAMPLE = 1 };
+#define PGH_HET_TILE 4096 /* samples per workgroup tile of the kernel: 1 KiB of a row, 32 KiB of sums in LDS */
+typedef struct pgh_het_row {
+	double e_hom;    /* (double)e_sum * 2^-k                                  E(HOM) */
+	double f;        /* (hom_ct - e_hom) / (obs_ct - e_hom), NaN: see above        F */
+	int64_t e_sum;   /* the fixed-point sum itself                                   */
+	uint32_t hom_ct; /* used variants at which the sample's call is 0 or 2   O(HOM)  */
+	uint32_t obs_ct; /* used variants at which the sample has a call         N(NM)   */
+} pgh_het_row;       /* 32 bytes */
+int pgh_het(const pgh_dataset *ds, const pgh_subset *subset, uint32_t variant_begin, uint32_t n_var,
+            const uint32_t *vidx, const double *freq /* NULL or n_var */, uint32_t flags,
+            pgh_het_row *out /* n_out rows, subset order */, uint8_t *used /* NULL or n_var */,
+            uint32_t *n_used /* may be NULL */, char *errbuf);
+/* e of one variant from its counts: returns 1 and stores *e when the variant is used, else 0 (also for unknown flag
+ * bits, for a freq that is not NaN together with PGH_HET_SMALL_SAMPLE, and for a null e).  freq: NaN takes p from the
+ * counts.  pgh_het's tables are this function, bit for bit. */
+int pgh_het_expected(uint32_t het, uint32_t alt, uint32_t called, double freq /* NaN: from the counts */, uint32_t flags,
+                     double *e);
+uint32_t pgh_het_scale(uint32_t n_var); /* k */
 
 /* ---- HWE exact tests (host) --------------------------------------------- */
 

@@ -226,6 +226,12 @@ void Free(pgh_dataset *ds);
 int PghOpenRows(const char *pgen_path, const char *pgi_path, uint32_t variant_begin, uint32_t variant_end,
                 bool hardcalls_only, pgh_dataset **out, char *errbuf);
 
+// pgh_het's raw integer sums over one dense-resident dataset for a given fixed-point scale k (api_het.cpp): what
+// pgh_het finishes into rows, and what a shard group adds up shard by shard
+int PghHetSums(const pgh_dataset *ds, const pgh_subset *subset, uint32_t variant_begin, uint32_t n_var,
+               const uint32_t *vidx, const double *freq, const uint32_t *pos, uint32_t flags, uint32_t k, int64_t *e_sum,
+               uint32_t *hom_ct, uint32_t *obs_ct, uint8_t *used, uint32_t *n_used, char *errbuf);
+
 // shard-group forms of the host-buffer entry points (api_sharded.cpp)
 namespace pgh_group {
 int CountsRange(const pgh_dataset *g, const pgh_subset *ss, uint32_t v_begin, uint32_t v_end, uint32_t (*out)[4],
@@ -234,6 +240,10 @@ int MissingPerSample(const pgh_dataset *g, const pgh_subset *ss, uint32_t v_begi
                      char *errbuf);
 int SampleCounts(const pgh_dataset *g, const pgh_subset *ss, uint32_t variant_begin, uint32_t n_var,
                  const uint32_t *vidx, uint32_t (*counts)[4], char *errbuf);
+//! PghHetSums over a group: the shards' integer sums added (freq and used in the caller's list order).
+int Het(const pgh_dataset *g, const pgh_subset *ss, uint32_t variant_begin, uint32_t n_var, const uint32_t *vidx,
+        const double *freq, uint32_t flags, uint32_t k, int64_t *e_sum, uint32_t *hom_ct, uint32_t *obs_ct,
+        uint8_t *used, uint32_t *n_used, char *errbuf);
 int UnpackRange(const pgh_dataset *g, const pgh_subset *ss, uint32_t v_begin, uint32_t v_end, int8_t *out,
                 uint64_t *validity, int missing_code, char *errbuf);
 int DosageSums(const pgh_dataset *g, const pgh_subset *ss, uint32_t variant_begin, uint32_t n_variants,

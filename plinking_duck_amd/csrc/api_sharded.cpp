@@ -833,6 +833,47 @@ int SampleCounts(const pgh_dataset *g, const pgh_subset *ss, uint32_t variant_be
 	return PGH_OK;
 }
 
+int Het(const pgh_dataset *g, const pgh_subset *ss, uint32_t variant_begin, uint32_t n_var, const uint32_t *vidx,
+        const double *freq, uint32_t flags, uint32_t k, int64_t *e_sum, uint32_t *hom_ct, uint32_t *obs_ct,
+        uint8_t *used, uint32_t *n_used, char *errbuf) {
+	int rc = CheckGroupSubset(g, ss, errbuf);
+	if (rc != PGH_OK) {
+		return rc;
+	}
+	const size_t n_out = ss ? ss->n_out : g->sample_ct;
+	const size_t K = g->shards.size();
+	// every shard's share under the CALL's scale k: the sums are integers, so adding them is exact and the result is
+	// that of one dataset.  A share's entries of freq and used: a slice's are contiguous, a list's stand at pos.
+	std::vector<std::vector<int64_t>> part_e(K);
+	std::vector<std::vector<uint32_t>> part_c(K);
+	std::vector<uint32_t> part_used(K, 0);
+	rc = ForShardShares(g, variant_begin, n_var, vidx, errbuf,
+	                    [&](size_t s, uint32_t begin, uint32_t n_k, const uint32_t *list, const uint32_t *pos, char *eb) {
+		const size_t at = list ? 0 : begin - variant_begin;
+		part_e[s].resize(n_out);
+		part_c[s].resize(2 * n_out);
+		return PghHetSums(g->shards[s], PartOf(ss, s), begin, n_k, list, freq ? freq + at : nullptr, pos, flags, k,
+		                  part_e[s].data(), part_c[s].data(), part_c[s].data() + n_out, used ? used + at : nullptr,
+		                  &part_used[s], eb);
+	});
+	if (rc != PGH_OK) {
+		return rc;
+	}
+	std::fill(e_sum, e_sum + n_out, int64_t {0});
+	std::fill(hom_ct, hom_ct + n_out, 0u);
+	std::fill(obs_ct, obs_ct + n_out, 0u);
+	*n_used = 0;
+	for (size_t s = 0; s < K; s++) {
+		*n_used += part_used[s];
+		for (size_t i = 0; i < part_e[s].size(); i++) {
+			e_sum[i] = static_cast<int64_t>(static_cast<uint64_t>(e_sum[i]) + static_cast<uint64_t>(part_e[s][i]));
+			hom_ct[i] += part_c[s][i];
+			obs_ct[i] += part_c[s][n_out + i];
+		}
+	}
+	return PGH_OK;
+}
+
 int Score(const pgh_dataset *g, const pgh_subset *ss, uint32_t n_scored, const uint32_t *vidx, const double *weights,
           const uint8_t *flip, uint32_t n_cols, int mode, const uint32_t (*counts)[4], double *score_sum,
           double *dosage_sum, uint32_t *allele_ct, char *errbuf) {

@@ -6,7 +6,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-result -mllvm -amdgpu-mfma-vgpr-form"
 mkdir -p build
 pids=()
-for f in tally.hip unpack.hip score.hip score_i8.hip reduce.hip pca.hip pca_i8.hip decode.hip ld.hip dosage.hip phase.hip glm.hip glm_sparse.hip glm_sparse_multi.hip glm_score_sparse.hip glm_score_sparse_multi.hip glm_score_dense.hip glm_score_dense_spa.hip glm_score_dense_firth.hip glm_score_dense_dosage.hip glm_score_dense_dosage_spa.hip glm_score_dense_dosage_firth.hip glm_score_spa.hip glm_score_sparse_multi_spa.hip glm_score_sparse_firth.hip glm_score_sparse_multi_firth.hip burden_sparse.hip skat_sparse.hip score_sparse.hip sparse.hip king.hip ldband.hip grm.hip api_dataset.cpp api_analysis.cpp api_reader.cpp api_sharded.cpp api_tally.cpp api_glm.cpp api_sparse.cpp api_king.cpp api_ldband.cpp api_grm.cpp pgen_file.cpp linalg.cpp; do
+for f in tally.hip unpack.hip score.hip score_i8.hip reduce.hip pca.hip pca_i8.hip decode.hip ld.hip dosage.hip phase.hip glm.hip glm_sparse.hip glm_sparse_multi.hip glm_score_sparse.hip glm_score_sparse_multi.hip glm_score_dense.hip glm_score_dense_spa.hip glm_score_dense_firth.hip glm_score_dense_dosage.hip glm_score_dense_dosage_spa.hip glm_score_dense_dosage_firth.hip glm_score_spa.hip glm_score_sparse_multi_spa.hip glm_score_sparse_firth.hip glm_score_sparse_multi_firth.hip burden_sparse.hip skat_sparse.hip score_sparse.hip sparse.hip king.hip ldband.hip grm.hip het.hip api_dataset.cpp api_analysis.cpp api_reader.cpp api_sharded.cpp api_tally.cpp api_glm.cpp api_sparse.cpp api_king.cpp api_ldband.cpp api_grm.cpp api_het.cpp pgen_file.cpp linalg.cpp; do
 	o=build/${f%.*}.o
 	if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ -n "$(find . -maxdepth 1 -name '*.hpp' -newer "$o")" ] || [ ../../include/pgenhip.h -nt "$o" ]; then
 		# translation units are independent: compile them side by side
@@ -29,7 +29,7 @@ done
 for p in "${pids[@]}"; do
 	wait "$p"
 done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o ../libpgenhip.so build/tally.o build/unpack.o build/score.o build/score_i8.o build/reduce.o build/pca.o build/pca_i8.o build/decode.o build/ld.o build/dosage.o build/phase.o build/glm.o build/glm_sparse.o build/glm_sparse_multi.o build/glm_score_sparse.o build/glm_score_sparse_multi.o build/glm_score_dense.o build/glm_score_dense_spa.o build/glm_score_dense_firth.o build/glm_score_dense_dosage.o build/glm_score_dense_dosage_spa.o build/glm_score_dense_dosage_firth.o build/glm_score_spa.o build/glm_score_sparse_multi_spa.o build/glm_score_sparse_firth.o build/glm_score_sparse_multi_firth.o build/burden_sparse.o build/skat_sparse.o build/score_sparse.o build/sparse.o build/king.o build/ldband.o build/grm.o build/api_dataset.o build/api_analysis.o build/api_reader.o build/api_sharded.o build/api_tally.o build/api_glm.o build/api_sparse.o build/api_king.o build/api_ldband.o build/api_grm.o build/pgen_file.o build/linalg.o
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o ../libpgenhip.so build/tally.o build/unpack.o build/score.o build/score_i8.o build/reduce.o build/pca.o build/pca_i8.o build/decode.o build/ld.o build/dosage.o build/phase.o build/glm.o build/glm_sparse.o build/glm_sparse_multi.o build/glm_score_sparse.o build/glm_score_sparse_multi.o build/glm_score_dense.o build/glm_score_dense_spa.o build/glm_score_dense_firth.o build/glm_score_dense_dosage.o build/glm_score_dense_dosage_spa.o build/glm_score_dense_dosage_firth.o build/glm_score_spa.o build/glm_score_sparse_multi_spa.o build/glm_score_sparse_firth.o build/glm_score_sparse_multi_firth.o build/burden_sparse.o build/skat_sparse.o build/score_sparse.o build/sparse.o build/king.o build/ldband.o build/grm.o build/het.o build/api_dataset.o build/api_analysis.o build/api_reader.o build/api_sharded.o build/api_tally.o build/api_glm.o build/api_sparse.o build/api_king.o build/api_ldband.o build/api_grm.o build/api_het.o build/pgen_file.o build/linalg.o
 echo "built $(cd .. && pwd)/libpgenhip.so"
 
 # host-side table-function shells (plain C++; link against the C ABI only)

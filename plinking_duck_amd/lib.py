@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "pgh_king_counts", "pgh_king_table", "pgh_king_kinship",
     "pgh_ld_window_sums", "pgh_ld_prune", "pgh_ld_exceeds", "pgh_ld_scores", "pgh_ld_r2",
     "pgh_grm", "pgh_grm_standardize",
+    "pgh_het", "pgh_het_expected", "pgh_het_scale",
 ]
 
 
@@ -82,6 +83,12 @@ class PghBurdenRow(C.Structure):
     ]
 
 
+class PghHetRow(C.Structure):
+    _fields_ = [
+        ("e_hom", C.c_double), ("f", C.c_double), ("e_sum", C.c_int64), ("hom_ct", C.c_uint32), ("obs_ct", C.c_uint32),
+    ]
+
+
 class PghSkatRow(C.Structure):
     _fields_ = [
         ("q", C.c_double), ("p_skat", C.c_double), ("beta", C.c_double), ("se", C.c_double), ("stat", C.c_double),
@@ -109,6 +116,12 @@ LD_SCORE_CHUNK_ENV = "PGH_LD_SCORE_CHUNK_TILES"
 GRM_MEANIMPUTE = 1
 GRM_TILE = 128
 GRM_BAND_ENV = "PGH_GRM_BAND_BYTES"
+# pgh_het's flag, the kernel's tile of samples (a test of tile edges names it), the environment variable that sets the
+# variant slices of its grid (results do not depend on it) and pgh_het_row
+HET_SMALL_SAMPLE = 1
+HET_TILE = 4096
+HET_SLICES_ENV = "PGH_HET_SLICES"
+HET_ROW_DTYPE = np.dtype([("e_hom", "<f8"), ("f", "<f8"), ("e_sum", "<i8"), ("hom_ct", "<u4"), ("obs_ct", "<u4")])
 GLM_ROW_DTYPE = np.dtype([("beta", "<f8"), ("se", "<f8"), ("stat", "<f8"), ("p", "<f8"), ("a1_freq", "<f8"),
                           ("obs_ct", "<u4"), ("errcode", "u1"), ("firth", "u1"), ("pad", "u1", (2,))])
 # pgh_glm_firth_row
@@ -281,6 +294,9 @@ def _load():
         "pgh_ld_r2": (C.c_int, [vp, u32, C.POINTER(C.c_double)]),
         "pgh_grm": (C.c_int, [vp, vp, u32, u32, vp, vp, u32, u32, u32, u32, u32, vp, vp, C.POINTER(u32), cp]),
         "pgh_grm_standardize": (C.c_double, [u32, u32, u32, vp]),
+        "pgh_het": (C.c_int, [vp, vp, u32, u32, vp, vp, u32, vp, vp, C.POINTER(u32), cp]),
+        "pgh_het_expected": (C.c_int, [u32, u32, u32, C.c_double, u32, C.POINTER(C.c_double)]),
+        "pgh_het_scale": (u32, [u32]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -360,6 +376,22 @@ def grm_standardize(het: int, alt: int, called: int):
     z = np.zeros(3, dtype=np.float64)
     p = _lib.pgh_grm_standardize(int(het), int(alt), int(called), _ptr(z))
     return (p, None) if p != p else (p, z)
+
+
+def het_expected(het: int, alt: int, called: int, freq: float | None = None, small_sample: bool = True):
+    """pgh_het_expected: e = 1 - (2 p)(1 - p) [times 2 called / (2 called - 1) with small_sample] of one variant, with
+    p = (het + 2 alt) / (2 called) or `freq` -- the expected homozygosity pgh_het sums per sample.  None when the
+    variant is skipped: nothing called, p not finite, p <= 0 or p >= 1 (and for freq together with small_sample)."""
+    e = C.c_double(0.0)
+    used = _lib.pgh_het_expected(int(het), int(alt), int(called), float("nan") if freq is None else float(freq),
+                                 HET_SMALL_SAMPLE if small_sample else 0, C.byref(e))
+    return e.value if used else None
+
+
+def het_scale(n_var: int) -> int:
+    """pgh_het_scale: k = 62 - L with L the smallest integer with 2^L >= max(n_var, 1) -- pgh_het's fixed-point sums
+    are multiples of 2^-k."""
+    return int(_lib.pgh_het_scale(int(n_var)))
 
 
 def ld_exceeds(sums, r2: float) -> bool:
@@ -1426,6 +1458,32 @@ class Dataset:
                             GRM_MEANIMPUTE if meanimpute else 0, _ptr(rel), _ptr(nobs) if want_nobs else None,
                             C.byref(used), eb), eb)
         return rel, nobs, int(used.value)
+
+    def het(self, v_begin: int | None = None, v_end: int | None = None, vidx=None, subset: Subset | None = None,
+            freq=None, small_sample: bool = True):
+        """pgh_het: (rows, used, n_used) -- per output sample a HET_ROW_DTYPE row (e_hom, f, e_sum, hom_ct, obs_ct):
+        the expected and observed homozygous calls over the used variants of a range or list and the inbreeding
+        coefficient f = (hom_ct - e_hom) / (obs_ct - e_hom); used: uint8 per variant of the call, 1 where it was not
+        skipped.  freq: one allele frequency per variant of the call instead of the counted one (then small_sample
+        must be False).  The same variants give the same bytes from a dataset, a window or a shard group."""
+        n_out = subset.size if subset else self.n_samples
+        v0, n, v = self._range_or_list(v_begin, v_end, vidx)
+        for x in (v0, n):
+            if not 0 <= x <= 0xFFFFFFFF:
+                raise ValueError(f"het: {x} is not an unsigned 32-bit index")
+        f = None
+        if freq is not None:
+            f = np.ascontiguousarray(freq, dtype=np.float64)
+            if f.shape != (n,):
+                raise ValueError(f"het: freq must hold one frequency per variant of the call ({n})")
+        rows = np.zeros(max(n_out, 1), dtype=HET_ROW_DTYPE)  # (never a null pointer, also under the empty subset)
+        used = np.zeros(max(n, 1), dtype=np.uint8)
+        n_used = C.c_uint32(0)
+        eb = _errbuf()
+        _check(_lib.pgh_het(self._h, subset._h if subset else None, v0, n, _ptr(v) if v is not None else None,
+                            _ptr(f) if f is not None else None, HET_SMALL_SAMPLE if small_sample else 0, _ptr(rows),
+                            _ptr(used), C.byref(n_used), eb), eb)
+        return rows[:n_out], used[:n], int(n_used.value)
 
     def ld_window_sums(self, v_begin: int | None = None, v_end: int | None = None, vidx=None,
                        subset: Subset | None = None, a_range=None, b_range=None) -> np.ndarray:
